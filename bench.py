@@ -9,8 +9,12 @@ is one full pass of StokesColor.py:537-586: 2-RHS viscous CG, two periodic-merge
 (rtol --rtol-pres), three divergences, two gradient projections, BCs, semi-Lagrangian dye
 advection and the mixing index.  Strong scaling: the mesh is fixed and partitioned into y-slabs.
 
-  python bench.py [--gpus N --steps K --warmup W --level 7]
+  python bench.py [--gpus N --steps K --warmup W --level 7] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline; --dump-outputs DIR writes
+u, p, c after the last timed step as DIR/<name>.npy; --full adds the per-kernel / roofline figures,
+the steady-state leg, the secondary workloads and the CPU baseline.
 
 Prints ONE JSON line on rank 0.
 """
@@ -54,6 +58,14 @@ def parse():
     ap.add_argument("--proj-k-visc", type=int, default=0, help="the same for the viscous solve (0: warm start)")
     ap.add_argument("--precond", default="mg", choices=["mg", "jacobi"],
                     help="pressure CG preconditioner: geometric multigrid over the refinement levels, or Jacobi")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-launch kernel events on the last timed steps and "
+                         "the roofline kernel, the back-to-back kernel table, the steady-state leg, the L5 / StokesFood / "
+                         "mesh_fine / heat legs and the CPU baseline (the options below select among these and act "
+                         "only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state the last timed step left (u, p, c at a fixed seeded "
+                         "sample of nodes) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--kernel-table", action="store_true",
                     help="per-launch events on every kernel class (default: the roofline kernel only)")
@@ -67,7 +79,13 @@ def parse():
     ap.add_argument("--steady-after", type=int, default=100,
                     help="steady-state leg: the same run continued to this step, then --steady-steps timed (0: off)")
     ap.add_argument("--steady-steps", type=int, default=20)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not a.full:  # a plain run: set up, warm up, time the steps, print the headline
+        a.no_cpu_baseline = a.no_secondary = a.no_kernel_timing = True
+        a.steady_after = 0
+    return a
 
 
 def main():
@@ -160,6 +178,19 @@ def main():
     cls1 = [sim.ctx.class_counters(k) for k in range(16)]
     elapsed = allmax(dt_local)
     log(f"[bench] timed {a.steps} steps in {elapsed:.2f}s")
+    if a.dump_outputs:  # before anything steps the simulation further
+        out = dump_outputs(sim)
+        if world > 1:  # u, p: every rank fills its owned rows (the others 0); c is replicated
+            for k in ("u", "p"):
+                t = torch.from_numpy(out[k])
+                td.all_reduce(t, op=td.ReduceOp.SUM)
+        if rank == 0:
+            import numpy as np
+
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for k, v in out.items():
+                np.save(os.path.join(a.dump_outputs, k + ".npy"), v)
+            log(f"[bench] wrote {', '.join(out)} to {a.dump_outputs}")
     names = ["k_cheb (MG smoother, finest level)", "k_cg_dir", "k_cg_upd", "k_grad_proj", "k_sl",
              "k_resid (MG residual, finest level)", "k_transfer (restriction from finest)",
              "k_transfer (prolongation to finest)", "k_sl_wq (SL second pass: general locate + rank count)",
@@ -182,7 +213,7 @@ def main():
     # the same kernels launched back to back outside the step (pucfem_bench_kernel): per-launch time
     # of a batch between two events, and the average of per-launch dispatch events
     batch = {}
-    if sim.ctx.precond == "mg" and not a.mg_double:
+    if a.full and sim.ctx.precond == "mg" and not a.mg_double:
         import ctypes as ct
 
         for kid, nm in ((0, "k_cheb"), (1, "k_resid"), (2, "k_cg_dir"), (16 * 8, "k_cheb+8 coarse launches"),
@@ -308,7 +339,7 @@ def main():
     if rank == 0 and world == 1 and not a.no_secondary:
         rec["mesh_fine"] = secondary_fine(pf, a.fine_steps)
         rec["heat_fine"] = heat_fine(pf)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         # the GPU / CPU ratios measured on this host on BOTH sides (north_star's target: >= 50x the CPU numpy
         # path on mesh_fine)
         cb, fine = rec.get("cpu_baseline"), rec.get("mesh_fine")
@@ -322,6 +353,24 @@ def main():
         print(json.dumps(rec))
     if world > 1:
         td.destroy_process_group()
+
+
+DUMP_NODES = 1 << 20  # sampled nodes: u, p, c and the node list are 40 MB in float64
+
+
+def dump_outputs(sim):
+    """What a caller of the timed path holds after its last step: the velocity u, the pressure p and the dye c
+    (the fields solve() returns), at all nodes or, on a mesh of more than DUMP_NODES nodes, at a fixed seeded
+    sample of them (`nodes`, sorted)."""
+    import numpy as np
+
+    L = importlib.import_module("puc-fluidsimulation-project_amd._lib")
+    N = sim.mesh.N
+    idx = np.arange(N) if N <= DUMP_NODES else np.sort(np.random.default_rng(20240607).choice(N, DUMP_NODES, replace=False))
+    return {"nodes": idx.astype(np.float64),
+            "u": np.ascontiguousarray(sim.u[idx]),
+            "p": np.ascontiguousarray(sim.field(L.F_P)[idx]),
+            "c": np.ascontiguousarray(sim.c[idx])}
 
 
 def gpu_l5(pf, tol, warmup=5, steps=20):

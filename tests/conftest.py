@@ -14,7 +14,8 @@ def pytest_configure(config):
 
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFERENCE = os.environ.get("PUCFEM_REFERENCE", "/root/reference")
+# the reference's original Triangle files (.node / .ele / .poly), kept as data beside the goldens made from them
+MESH_FILES = os.path.join(GOLDEN, "meshes")
 
 
 @pytest.fixture(scope="session")

@@ -8,19 +8,14 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, load_pkg
+from conftest import GOLDEN, MESH_FILES, load_pkg
 
 pf = load_pkg()
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import make_mesh  # noqa: E402
 
-REF = "/root/reference"
-FILES = {
-    "mesh1": ("code/mesh/mesh.1.node", "code/mesh/mesh.1.ele", "code/mesh/mesh.1.poly"),
-    "mesh21": ("resources/mesh2.1.node", "resources/mesh2.1.ele", "resources/mesh2.1.poly"),
-    "fine": ("resources/mesh_fine.1.node", "resources/mesh_fine.1.ele", "resources/mesh_fine.1.poly"),
-}
+FILES = {"mesh1": "mesh.1", "mesh21": "mesh2.1", "fine": "mesh_fine.1"}
 
 
 def golden(name):
@@ -55,12 +50,11 @@ def test_writer_roundtrip_matches_reference_parse(name, tmp_path):
         np.testing.assert_array_equal(segm, g["poly_markers"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (build container only)")
 @pytest.mark.parametrize("name", ["mesh1", "mesh21", "fine"])
 def test_readers_on_the_reference_files(name):
-    """Our readers on the reference's original Triangle files (read as data) = the reference's parse."""
+    """Our readers on the reference's original Triangle files (tests/golden/meshes) = the reference's parse."""
     g = golden(name)
-    node, ele, poly = (os.path.join(REF, p) for p in FILES[name])
+    node, ele, poly = (os.path.join(MESH_FILES, f"{FILES[name]}.{e}") for e in ("node", "ele", "poly"))
     X, mk = pf.readNode(node)
     np.testing.assert_array_equal(X, g["coords64"])
     np.testing.assert_array_equal(mk, g["markers"])

@@ -11,14 +11,10 @@ import pytest
 import scipy.sparse as sp
 
 import oracle as O
-from conftest import REFERENCE
+from conftest import MESH_FILES
 
 MESHES = ["mesh1", "mesh21", "fine"]
-FILES = {
-    "mesh1": "code/mesh/mesh.1",
-    "mesh21": "resources/mesh2.1",
-    "fine": "resources/mesh_fine.1",
-}
+FILES = {"mesh1": "mesh.1", "mesh21": "mesh2.1", "fine": "mesh_fine.1"}
 
 
 def dense(ij, v, N):
@@ -30,9 +26,7 @@ def dense(ij, v, N):
 @pytest.mark.parametrize("m", MESHES)
 def test_reader_on_reference_files(m, golden):
     g = golden(m)
-    base = os.path.join(REFERENCE, FILES[m])
-    if not os.path.exists(base + ".node"):
-        pytest.skip("reference mesh files not present (GPU box)")
+    base = os.path.join(MESH_FILES, FILES[m])
     X, mk = O.read_node(base + ".node")
     X32, _ = O.read_node(base + ".node", np.float32)
     T = O.read_ele(base + ".ele")

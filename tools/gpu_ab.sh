@@ -12,7 +12,7 @@ if [ -z "$SKIP_TESTS" ]; then
 fi
 i=0
 for args in "$@"; do
-  timeout -k 10 600 python bench.py --no-cpu-baseline --no-secondary $args > "$OUT/bench$i.out" 2> "$OUT/bench$i.err"
+  timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-secondary $args > "$OUT/bench$i.out" 2> "$OUT/bench$i.err"
   rc=$?; echo "bench[$args] rc=$rc" >&2; tail -2 "$OUT/bench$i.err" >&2
   python - "$OUT/bench$i.out" <<'PY' >&2
 import json, sys

@@ -12,7 +12,7 @@ for v in "$@"; do
   case "$v" in *--*) envs="${v%%--*}"; args="${v#*--}";; esac
   case "$v" in *=*) [ "$envs" = "" ] && envs="$v" && args="";; esac
   kt="--no-kernel-timing"; [ -n "$KT" ] && kt=""  # KT=1: per-launch kernel events (the kernel table below)
-  timeout -k 10 400 env $envs python bench.py --no-cpu-baseline --no-secondary $kt --warmup 5 --steps 20 \
+  timeout -k 10 400 env $envs python bench.py --full --no-cpu-baseline --no-secondary $kt --warmup 5 --steps 20 \
     $args > "$OUT/b$i.out" 2> "$OUT/b$i.err"
   rc=$?
   python - "$OUT/b$i.out" "$v" <<'PY' >&2

@@ -15,4 +15,4 @@ run() {  # name timeout cmd...
 }
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 run pytest_gpu 900 python -m pytest tests -m gpu -x -q
-run bench_l5 600 python bench.py --level 5 --steps 2 --warmup 1 --no-cpu-baseline
+run bench_l5 600 python bench.py --full --level 5 --steps 2 --warmup 1 --no-cpu-baseline

@@ -8,7 +8,7 @@ OUT=gpurun_out/$TAG; mkdir -p "$OUT"
 BARGS=${BARGS:---warmup 5 --steps 20 --steady-after 0}
 i=0
 for e in "$@"; do
-  env $e timeout -k 10 300 python bench.py --no-cpu-baseline --no-secondary $BARGS > "$OUT/bench$i.out" 2> "$OUT/bench$i.err"
+  env $e timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-secondary $BARGS > "$OUT/bench$i.out" 2> "$OUT/bench$i.err"
   rc=$?; echo "[$e] rc=$rc" >&2
   [ $rc -ne 0 ] && { tail -3 "$OUT/bench$i.err" >&2; exit $rc; }
   python - "$OUT/bench$i.out" <<'PY' >&2

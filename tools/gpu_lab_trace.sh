@@ -12,7 +12,7 @@ fi
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/tr_$TAG
 timeout -k 10 600 rocprofv3 --kernel-trace -d /tmp/tr_$TAG -o run --output-format csv -- \
-  python "$ROOT/bench.py" --no-cpu-baseline --no-secondary --no-kernel-timing --steps 20 --warmup 5 > "$OUT/bench.out" 2> "$OUT/bench.err"
+  python "$ROOT/bench.py" --full --no-cpu-baseline --no-secondary --no-kernel-timing --steps 20 --warmup 5 > "$OUT/bench.out" 2> "$OUT/bench.err"
 rc=$?; echo "rocprof rc=$rc" >&2; [ $rc -ne 0 ] && { tail -5 "$OUT/bench.err" >&2; exit $rc; }
 f=$(find /tmp/tr_$TAG -name "*kernel_trace.csv" | head -1)
 python "$ROOT/tools/trace_window.py" "$f" --warmup 5 --steps 20 --top 70 > "$OUT/step_window.txt"

@@ -12,14 +12,14 @@ if [ -z "$SKIP_TESTS" ]; then
   rc=$?; echo "pytest rc=$rc" >&2; grep -E "passed|failed|Error|error" "$OUT/pytest_gpu.out" | tail -15 >&2
   [ $rc -ne 0 ] && exit $rc
 fi
-timeout -k 10 900 python bench.py --warmup 5 --steps 20 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 900 python bench.py --full --warmup 5 --steps 20 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; echo "bench rc=$rc" >&2; tail -3 "$OUT/bench.err" >&2; cat "$OUT/bench.json" >&2
 [ $rc -ne 0 ] && exit $rc
 [ -n "$SKIP_TRACE" ] && exit 0
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/tr_$TAG
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/tr_$TAG -o run --output-format csv -- \
-  python "$ROOT/bench.py" --warmup 5 --steps 20 --no-cpu-baseline --no-secondary "$@" > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err"
+  python "$ROOT/bench.py" --full --warmup 5 --steps 20 --no-cpu-baseline --no-secondary "$@" > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err"
 rc=$?; echo "rocprof rc=$rc" >&2; [ $rc -ne 0 ] && { tail -5 "$OUT/trace_bench.err" >&2; exit $rc; }
 f=$(find /tmp/tr_$TAG -name "*kernel_trace.csv" | head -1)
 find /tmp/tr_$TAG -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;

@@ -13,5 +13,5 @@ step() {  # name timeout cmd...
 [ -z "$SKIP_TESTS" ] && step pytest_gpu 1000 python -u -m pytest tests -m gpu -x -v -rP --timeout 300 --timeout-method thread ${PYTEST_ARGS}
 [ -z "$SKIP_MARGIN" ] && step margin_100 400 python -u tools/margin_probe.py --start 100 --window 50 --rtols ${RTOLS:-1e-7,5e-8,3e-8}
 for r in ${BENCH_RTOLS:-1e-7 5e-8}; do
-  step bench_$r 300 python -u bench.py --no-cpu-baseline --no-secondary --warmup 5 --steps 20 --rtol-pres $r
+  step bench_$r 300 python -u bench.py --full --no-cpu-baseline --no-secondary --warmup 5 --steps 20 --rtol-pres $r
 done

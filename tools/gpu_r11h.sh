@@ -1,7 +1,7 @@
 #!/bin/bash
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${1:-r11h}; mkdir -p "$OUT"
-B="python -u bench.py --no-cpu-baseline --no-secondary --warmup 5 --steps 20"
+B="python -u bench.py --full --no-cpu-baseline --no-secondary --warmup 5 --steps 20"
 run() { local name=$1; shift; echo "=== $name" >&2; timeout -k 10 200 env "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || { echo "fail $name" >&2; exit 1; };
   python -c "import json; d=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print('$name', round(d['value'],2), 'steady', round(d['steady']['steps_per_s'],2), d['projection'], d['steady']['projection'], d['steady']['cg_iters_per_step'])" >&2; }
 run base $B

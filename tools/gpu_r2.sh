@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -s --timeout 300 --time
 rc=$?; echo "pytest rc=$rc" >&2; tail -30 "$OUT/pytest.out" >&2
 [ $rc -ne 0 ] && exit $rc
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 600 python -u bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+  timeout -k 10 600 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; echo "bench rc=$rc" >&2; tail -3 "$OUT/bench.err" >&2; cut -c1-600 "$OUT/bench.json" >&2
 fi
 exit $rc
