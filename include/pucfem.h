@@ -195,6 +195,33 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count);
    stats read afterwards are those of the last step, as with one stream. */
 int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats /* nsteps entries or NULL */);
 
+/* ---- ensembles: several squirmers on one mesh and fluid, stepped together ----------- */
+/* The reference's experiment is a comparison of swimmers on the same mesh (README.md:43-45: food eaten by the
+   neutral, pusher and puller squirmers, one run of StokesFood.py each).  An ensemble is M members (1..4096)
+   stepped together on ONE built context: they share everything pucfem_build_operators made (the dense inverses,
+   the gradient / divergence coefficients, the point locator, the tracer grid) and differ in their Dirichlet
+   values, their fields u / c and their tracers.  Every member's arithmetic is the single context's, operation
+   for operation, so its fields are bit-identical to a pucfem_step run with its boundary values.
+   Requirements: a single-rank STOKES_COLOR (semi-Lagrangian dye) or STOKES_FOOD context on the dense small-mesh
+   path (pucfem_path_info out[0] == out[1] == 0: N <= 1500), else PUCFEM_ESTATE; a device, else PUCFEM_ENODEV.
+   The ensemble owns its state: the context's own fields, step graph and records are not touched.  One ensemble
+   per context; pucfem_ctx_destroy and pucfem_build_operators destroy it.
+   dir_values: members x n_dirichlet x 2, each member's values in the node order given to pucfem_set_dirichlet.
+   Members start as pucfem_build_operators leaves the context: u = 0 then makeDirBCU with the member's values
+   (StokesColor.py:482-483), c = 1[x < 0.5] (:493-495), the context's current tracers with status 0. */
+int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values);
+int pucfem_ens_destroy(void* ctx);
+/* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS in the caller's numbering; member = -1: all members,
+   member-major (count = members x the field's values per member).  Setting TRACERS clears the status. */
+int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count);
+int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, int64_t count);
+/* nsteps steps of every member (StokesColor.py:537-586 / StokesFood.py:441-505 per member); stats: NULL or
+   nsteps x members entries, step s of member m at s * members + m (it_* = 0: direct solves) */
+int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats);
+/* out[0] members, [1] members per block of the dense products, [2] bytes of ensemble state on the device,
+   [3] steps taken since pucfem_ens_create */
+int pucfem_ens_info(void* ctx, int64_t* out4);
+
 /* ---- unit operations (reference-named shims and parity tests) --------------------- */
 int pucfem_apply(void* ctx, int32_t op, const double* x, double* y);
 /* op VISC: b,x are (N,2) (both velocity components, StokesColor.py:544-545);

@@ -75,6 +75,12 @@ SIGNATURES = {
     "pucfem_set_field": ([_P, ct.c_int32, _D, ct.c_int64], ct.c_int),
     "pucfem_get_field": ([_P, ct.c_int32, _D, ct.c_int64], ct.c_int),
     "pucfem_step": ([_P, ct.c_int32, ct.POINTER(StepStats)], ct.c_int),
+    "pucfem_ens_create": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_ens_destroy": ([_P], ct.c_int),
+    "pucfem_ens_set_field": ([_P, ct.c_int32, ct.c_int32, _D, ct.c_int64], ct.c_int),
+    "pucfem_ens_get_field": ([_P, ct.c_int32, ct.c_int32, _D, ct.c_int64], ct.c_int),
+    "pucfem_ens_step": ([_P, ct.c_int32, ct.POINTER(StepStats)], ct.c_int),
+    "pucfem_ens_info": ([_P, _I64], ct.c_int),
     "pucfem_apply": ([_P, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_solve": ([_P, ct.c_int32, _D, _D, ct.c_double, ct.c_int32, _I32], ct.c_int),
     "pucfem_sl_advect": ([_P, _D, _D, ct.c_double, _D, _I32], ct.c_int),

@@ -28,6 +28,7 @@
 #include "pucfem_host.hpp"
 #include "pucfem_kernels.hpp"
 #include "pucfem_kernels_impl.hpp"
+#include "pucfem_ensemble.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -128,6 +129,43 @@ struct HFace {
     return f;
   }
 };
+// An ensemble (pucfem_ens_*, pucfem_ensemble.hpp): M members stepped together on the context's shared small-mesh
+// operators.  It owns its state (member-major, the context's internal numbering), reduction buffers, record ring
+// and graphs; the context's own fields, graphs and records are not touched.
+struct Ens {
+  int32_t M = 0, ntr = 0;
+  int64_t n = 0, dstride = 0, steps = 0;
+  size_t bytes = 0;
+  double *u = nullptr, *us = nullptr, *p = nullptr, *p2 = nullptr, *braw = nullptr, *c = nullptr, *cn = nullptr;
+  double *dval = nullptr, *trx = nullptr, *try_ = nullptr, *trs = nullptr, *vals = nullptr;
+  double *part_d = nullptr, *part_sl = nullptr, *part_mx = nullptr, *ring = nullptr;
+  unsigned* cnt = nullptr;  // ticket counters: 3 launch sites (divergence, advection, mixing) x M
+  int* count = nullptr;     // per member: records in the ring
+  int ring_steps = 0;
+  int gx_dense = 1, nb_div = 1, nb_sl = 1, nb_mix = 1;
+  size_t lds_mv = 0, lds_pres = 0;
+  hipGraph_t graph = nullptr, graph_k = nullptr;
+  hipGraphExec_t gexec = nullptr, gexec_k = nullptr;
+  std::vector<void*> allocs;
+  template <class T>
+  T* alloc(size_t count_, hipStream_t st) {
+    void* q = nullptr;
+    const size_t b = sizeof(T) * std::max<size_t>(1, count_);
+    HIPCHK(hipMalloc(&q, b));
+    allocs.push_back(q);
+    HIPCHK(hipMemsetAsync(q, 0, b, st));
+    bytes += b;
+    return (T*)q;
+  }
+  ~Ens() {
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
+    if (graph_k) (void)hipGraphDestroy(graph_k);
+    for (void* a : allocs) (void)hipFree(a);
+  }
+};
+
 // f(std::true_type) when A carries int16 columns, f(std::false_type) otherwise: one launch site
 // instantiates both SpMV variants
 template <class F>
@@ -423,6 +461,7 @@ struct Ctx {
   std::vector<float> g_tri;
   pucfem_params prm{};
   bool built = false;
+  std::unique_ptr<Ens> ens;  // pucfem_ens_create (one per context)
 
   // ---- host structures (internal numbering)
   Ordering ord;
@@ -722,6 +761,7 @@ struct Ctx {
   ~Ctx() {
     if (!host_only) {
       if (st) (void)hipStreamSynchronize(st);
+      ens.reset();
       if (gexec) (void)hipGraphExecDestroy(gexec);
       if (graph) (void)hipGraphDestroy(graph);
       if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
@@ -4842,6 +4882,10 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     Ctx& c = *C(ctx);
     c.prm = *prm;
     c.built = false;
+    if (c.ens) {  // (an ensemble lives on the operators being replaced)
+      (void)hipStreamSynchronize(c.st);
+      c.ens.reset();
+    }
     if (c.gexec) {
       (void)hipGraphExecDestroy(c.gexec);
       (void)hipGraphDestroy(c.graph);
@@ -5166,6 +5210,339 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
         stats[0].it_visc = it;
       }
     }
+  });
+}
+
+// ---- ensembles: M members on the context's shared small-mesh operators (kernels: pucfem_ensemble.hpp)
+namespace {
+Ens* ens_of(Ctx& c) {
+  c.need_dev();
+  c.need_built();
+  if (!c.ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
+  return c.ens.get();
+}
+// One ensemble step: the dense small-mesh step's launches (Ctx::stokes_step in graph mode), each over every member,
+// in one chain on the context's stream.
+void ens_enqueue_step(Ctx& c) {
+  Ens& e = *c.ens;
+  const i64 n = e.n;
+  const int32_t M = e.M;
+  const int tiles = (M + ENS_TM - 1) / ENS_TM;
+  hipStream_t st = c.st;
+  const DevSell& A = c.dP;
+  hipLaunchKernelGGL(k_ens_mv2_bc<ENS_TM>, dim3(e.gx_dense, tiles), dim3(BS), e.lds_mv, st, (int64_t)n, M,
+                     (const double*)c.dVinv, (const double*)e.u, e.us, (const int32_t*)c.dbcsrc,
+                     (const int32_t*)c.dbcdir, (const double*)e.dval, (int64_t)e.dstride);
+  KCHK();
+  // max |div| into vals slot `slot`; with rhs the pressure right-hand side and its sum (slot 9)
+  auto div = [&](const double* u, int slot, bool rhs) {
+    const RedOut r{e.vals + slot, rhs ? e.vals + 9 : nullptr, e.cnt, rhs ? 2 : 1, 0, 1u};
+    with_c16(A, [&](auto c16) {
+      hipLaunchKernelGGL(k_ens_div<decltype(c16)::value>, dim3(e.nb_div, M), dim3(BS), 0, st, A.view(),
+                         (const double*)c.dGx, (const double*)c.dGy, u, (const double*)c.das1, (const double*)c.dmp,
+                         -(1.0 / c.prm.dt), rhs ? e.braw : (double*)nullptr, e.part_d, r);
+    });
+    KCHK();
+  };
+  auto pres = [&](double* pout) {
+    hipLaunchKernelGGL(k_ens_pres<ENS_TM>, dim3(e.gx_dense, tiles), dim3(BS), e.lds_pres, st, (int64_t)n, M,
+                       (const double*)c.dPinv, (const double*)e.braw, (const int32_t*)c.dslave_of,
+                       (const int32_t*)c.dmaster_of, (const double*)e.vals, 1.0 / (double)c.n_free, pout);
+    KCHK();
+  };
+  div(e.us, 0, true);
+  pres(e.p);
+  const int nbg = (int)std::max<i64>(1, std::min<i64>(1024, (A.nslices * 64 + BS - 1) / BS));
+  with_c16(A, [&](auto c16) {
+    hipLaunchKernelGGL(k_ens_grad_proj_bc<decltype(c16)::value>, dim3(nbg, M), dim3(BS), 0, st, A.view(),
+                       (const double*)c.dGx, (const double*)c.dGy, (const double*)e.p, (const double*)c.das1, c.prm.dt,
+                       (const double*)e.us, e.u, (const int32_t*)c.dbcsrc, (const int32_t*)c.dbcdir,
+                       (const int32_t*)c.dspos, (const double*)e.dval, (int64_t)e.dstride);
+  });
+  KCHK();
+  div(e.u, 8, true);  // (its maximum is not recorded: the scratch slot)
+  pres(e.p2);
+  with_c16(A, [&](auto c16) {
+    hipLaunchKernelGGL(k_ens_grad_proj1<decltype(c16)::value>, dim3(c.nb_mg(A.nslices), M), dim3(BS), 0, st, A.view(),
+                       (const double*)c.dGx, (const double*)c.dGy, (const double*)e.p2, (const double*)c.das1, c.prm.dt,
+                       (const uint8_t*)c.ddir, e.u);
+  });
+  KCHK();
+  div(e.u, 1, false);
+  if (c.scheme == PUCFEM_STOKES_COLOR) {
+    const RedOut rs{e.vals + 2, nullptr, e.cnt + M, 3, 0, 0u};
+    hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
+                       c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
+                       (const double*)c.dwmix, e.part_sl, rs);
+    KCHK();
+    const RedOut rm{e.vals + 5, nullptr, e.cnt + 2 * (size_t)M, 1, 0, 0u};
+    hipLaunchKernelGGL(k_ens_mix2, dim3(e.nb_mix, M), dim3(BS), 0, st, (int64_t)n, (const double*)e.cn,
+                       (const double*)c.dwmix, (const double*)e.vals, e.part_mx, rm, e.c);
+    KCHK();
+  } else if (e.ntr > 0) {
+    hipLaunchKernelGGL(k_ens_tracer, dim3(1, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.tgrid,
+                       (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, c.prm.dt, c.prm.center_x,
+                       c.prm.center_y, c.prm.capture_radius, e.vals);
+    KCHK();
+  }
+  hipLaunchKernelGGL(k_ens_record, dim3((M + 255) / 256), dim3(256), 0, st, M, (const double*)e.vals, e.ring, e.count);
+  KCHK();
+}
+// field -> (device array, values per member, per-row components: 2 interleaved, 1 plain, 0 not row-indexed)
+struct EnsField {
+  double* a;
+  i64 per;
+  int comp;
+};
+EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
+  switch (field) {
+    case PUCFEM_F_U: return {e.u, 2 * e.n, 2};
+    case PUCFEM_F_USTAR: return {e.us, 2 * e.n, 2};
+    case PUCFEM_F_P: return {e.p, e.n, 1};
+    case PUCFEM_F_P2: return {e.p2, e.n, 1};
+    case PUCFEM_F_C: return {e.c, e.n, 1};
+    case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
+    case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
+    default: throw Error(PUCFEM_EINVAL, "not an ensemble field (U, USTAR, P, P2, C, TRACERS, STATUS)");
+  }
+}
+}  // namespace
+
+int pucfem_ens_destroy(void* ctx) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    if (!c.ens) return;
+    HIPCHK(hipStreamSynchronize(c.st));
+    c.ens.reset();
+  });
+}
+
+int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.need_dev();
+    c.need_built();
+    auto state = [](bool ok, const char* msg) {
+      if (!ok) throw Error(PUCFEM_ESTATE, msg);
+    };
+    state(c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD, "ensembles step Stokes contexts");
+    state(!c.dist(), "ensembles run on a single-rank context");
+    state(!c.dye_impl, "ensembles step the semi-Lagrangian dye, not the implicit variant");
+    state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
+    state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
+              c.sl_rec_wave(c.lp.n_own) && (c.scheme != PUCFEM_STOKES_FOOD || c.has_tgrid),
+          "the context's small-mesh step is not in its default form (measurement knobs set?)");
+    require(members >= 1 && members <= 4096, "members must be in 1..4096");
+    require(dir_values != nullptr, "dir_values is null");
+    HIPCHK(hipStreamSynchronize(c.st));
+    c.ens.reset();
+    c.prep_grad_proj_bc();  // (the projection's position map, as the context's first step makes it)
+    auto ep = std::make_unique<Ens>();
+    Ens& e = *ep;
+    const i64 n = c.lp.n_own, N = c.mesh.N;
+    const int32_t M = members;
+    const size_t sM = (size_t)M;
+    e.M = M;
+    e.n = n;
+    e.ntr = c.scheme == PUCFEM_STOKES_FOOD ? c.ntr : 0;
+    e.dstride = 2 * (i64)std::max(1, c.ndir);
+    const int tiles = (M + ENS_TM - 1) / ENS_TM;
+    // the dense products' grid in x: enough blocks to fill the device about twice over, each staging its tile's
+    // vectors once for as many rows as that leaves (the rows' arithmetic does not depend on their block)
+    e.gx_dense = (int)std::max<i64>(std::min<i64>(8, (n + 3) / 4), std::min<i64>((n + 3) / 4, 1024 / tiles));
+    e.nb_div = c.div_grid();
+    e.nb_sl = c.nb_sl(n);
+    e.nb_mix = c.nb_rows(n);
+    e.lds_mv = sizeof(double) * 2 * (size_t)n * ENS_TM;
+    e.lds_pres = sizeof(double) * (size_t)n * ENS_TM;
+    HIPCHK(hipFuncSetAttribute((const void*)k_ens_mv2_bc<ENS_TM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sizeof(double) * 2 * DENSE_MAX * ENS_TM)));
+    HIPCHK(hipFuncSetAttribute((const void*)k_ens_pres<ENS_TM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)(sizeof(double) * DENSE_MAX * ENS_TM)));
+    hipStream_t st = c.st;
+    e.u = e.alloc<double>(sM * 2 * n, st);
+    e.us = e.alloc<double>(sM * 2 * n, st);
+    for (double** f : {&e.p, &e.p2, &e.braw, &e.c, &e.cn}) *f = e.alloc<double>(sM * n, st);
+    e.dval = e.alloc<double>(sM * e.dstride, st);
+    for (double** f : {&e.trx, &e.try_, &e.trs}) *f = e.alloc<double>(sM * (size_t)e.ntr, st);
+    e.vals = e.alloc<double>(sM * ENS_VALS, st);
+    e.part_d = e.alloc<double>(sM * 3 * e.nb_div, st);
+    e.part_sl = e.alloc<double>(sM * 3 * e.nb_sl, st);
+    e.part_mx = e.alloc<double>(sM * 3 * e.nb_mix, st);
+    e.cnt = e.alloc<unsigned>(3 * sM, st);
+    e.count = e.alloc<int>(sM, st);
+    e.ring_steps = (int)std::max<i64>(c.gk, std::min<i64>(Ctx::GRING, 65536 / M));
+    e.ring = e.alloc<double>((size_t)e.ring_steps * sM * 8, st);
+    // initial state, as build leaves the context: u = 0 then makeDirBCU with the member's values (the entries
+    // kept by build: a node's last occurrence, in list order); c = 1[x < 0.5]; the context's tracers, status 0
+    const size_t nd = c.dir_nodes.size();
+    std::vector<i64> last(N, -1);
+    for (size_t k = 0; k < nd; ++k) last[c.dir_nodes[k]] = (i64)k;
+    std::vector<size_t> keep;
+    for (size_t k = 0; k < nd; ++k)
+      if (last[c.dir_nodes[k]] == (i64)k) keep.push_back(k);
+    if ((int)keep.size() != c.ndir) throw Error(PUCFEM_ESTATE, "Dirichlet list changed since the build");
+    std::vector<double> dv(sM * e.dstride, 0.0), u0(sM * 2 * n, 0.0), c0(sM * n);
+    for (size_t m = 0; m < sM; ++m) {
+      for (size_t q = 0; q < keep.size(); ++q) {
+        const size_t k = keep[q];
+        const double vx = dir_values[(m * nd + k) * 2], vy = dir_values[(m * nd + k) * 2 + 1];
+        dv[m * e.dstride + 2 * q] = vx;
+        dv[m * e.dstride + 2 * q + 1] = vy;
+        const i64 g = c.ord.old2new[c.dir_nodes[k]];
+        u0[(m * n + g) * 2] = vx;
+        u0[(m * n + g) * 2 + 1] = vy;
+      }
+      for (i64 g = 0; g < n; ++g) c0[m * n + g] = c.mesh.x[c.ord.new2old[g]] < 0.5 ? 1.0 : 0.0;
+    }
+    c.h2d(e.dval, dv.data(), sizeof(double) * dv.size());
+    c.h2d(e.u, u0.data(), sizeof(double) * u0.size());
+    c.h2d(e.c, c0.data(), sizeof(double) * c0.size());
+    for (size_t m = 0; m < sM && e.ntr > 0; ++m) {
+      HIPCHK(hipMemcpyAsync(e.trx + m * e.ntr, c.trx, sizeof(double) * e.ntr, hipMemcpyDeviceToDevice, st));
+      HIPCHK(hipMemcpyAsync(e.try_ + m * e.ntr, c.try_, sizeof(double) * e.ntr, hipMemcpyDeviceToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    c.ens = std::move(ep);
+  });
+}
+
+int pucfem_ens_info(void* ctx, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    out4[0] = e.M;
+    out4[1] = ENS_TM;
+    out4[2] = (int64_t)e.bytes;
+    out4[3] = e.steps;
+  });
+}
+
+int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const EnsField f = ens_field(c, e, field);
+    const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+    require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
+    if (f.per == 0) return;
+    std::vector<double> x((size_t)(nm * f.per)), y;
+    if (field == PUCFEM_F_TRACERS) {
+      y.resize(x.size() / 2);
+      for (i64 k = 0; k < nm * e.ntr; ++k) {
+        x[k] = buf[2 * k];
+        y[k] = buf[2 * k + 1];
+      }
+      HIPCHK(hipMemcpyAsync(e.trx + m0 * e.ntr, x.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
+      HIPCHK(hipMemcpyAsync(e.try_ + m0 * e.ntr, y.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
+      HIPCHK(hipMemsetAsync(e.trs + m0 * e.ntr, 0, sizeof(double) * nm * e.ntr, c.st));  // (as pucfem_set_field)
+    } else {
+      for (i64 m = 0; m < nm; ++m)
+        for (i64 g = 0; g < e.n && f.comp > 0; ++g) {
+          const i64 o = c.ord.new2old[g];
+          for (int q = 0; q < f.comp; ++q) x[m * f.per + f.comp * g + q] = buf[m * f.per + f.comp * o + q];
+        }
+      const double* src = f.comp > 0 ? x.data() : buf;
+      HIPCHK(hipMemcpyAsync(f.a + m0 * f.per, src, sizeof(double) * nm * f.per, hipMemcpyHostToDevice, c.st));
+    }
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, int64_t count) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const EnsField f = ens_field(c, e, field);
+    const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+    require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
+    if (f.per == 0) return;
+    if (field == PUCFEM_F_TRACERS) {
+      std::vector<double> x((size_t)(nm * e.ntr)), y(x.size());
+      HIPCHK(hipMemcpyAsync(x.data(), e.trx + m0 * e.ntr, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
+      HIPCHK(hipMemcpyAsync(y.data(), e.try_ + m0 * e.ntr, sizeof(double) * y.size(), hipMemcpyDeviceToHost, c.st));
+      HIPCHK(hipStreamSynchronize(c.st));
+      for (size_t k = 0; k < x.size(); ++k) {
+        buf[2 * k] = x[k];
+        buf[2 * k + 1] = y[k];
+      }
+      return;
+    }
+    std::vector<double> x((size_t)(nm * f.per));
+    HIPCHK(hipMemcpyAsync(x.data(), f.a + m0 * f.per, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));
+    if (f.comp == 0) {
+      std::memcpy(buf, x.data(), sizeof(double) * x.size());
+      return;
+    }
+    for (i64 m = 0; m < nm; ++m)
+      for (i64 g = 0; g < e.n; ++g) {
+        const i64 o = c.ord.new2old[g];
+        for (int q = 0; q < f.comp; ++q) buf[m * f.per + f.comp * o + q] = x[m * f.per + f.comp * g + q];
+      }
+  });
+}
+
+int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(nsteps >= 0, "nsteps < 0");
+    if (nsteps == 0) return;
+    const size_t sM = (size_t)e.M;
+    // one step, and gk steps, captured once each as a single chain (every buffer was allocated at create)
+    auto capture = [&](int count, hipGraph_t& gr, hipGraphExec_t& ex) {
+      HIPCHK(hipStreamBeginCapture(c.st, hipStreamCaptureModeThreadLocal));
+      try {
+        for (int k = 0; k < count; ++k) ens_enqueue_step(c);
+      } catch (...) {
+        hipGraph_t g = nullptr;
+        (void)hipStreamEndCapture(c.st, &g);
+        if (g) (void)hipGraphDestroy(g);
+        throw;
+      }
+      HIPCHK(hipStreamEndCapture(c.st, &gr));
+      HIPCHK(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
+    };
+    if (!e.gexec) capture(1, e.graph, e.gexec);
+    if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
+    std::vector<double> h(stats ? 8 * sM * (size_t)nsteps : 0);
+    HIPCHK(hipMemsetAsync(e.count, 0, sizeof(int) * sM, c.st));
+    for (int s = 0, k = 0; s < nsteps;) {
+      int d = 1;
+      if (e.gexec_k && nsteps - s >= c.gk && k + c.gk <= e.ring_steps) {
+        HIPCHK(hipGraphLaunch(e.gexec_k, c.st));
+        d = c.gk;
+      } else {
+        HIPCHK(hipGraphLaunch(e.gexec, c.st));
+      }
+      s += d;
+      k += d;
+      if (k + 1 > e.ring_steps || s == nsteps) {  // the ring's records -> this call's records
+        if (stats)
+          HIPCHK(hipMemcpyAsync(h.data() + 8 * sM * (size_t)(s - k), e.ring, sizeof(double) * 8 * sM * k,
+                                hipMemcpyDeviceToHost, c.st));
+        if (s < nsteps) HIPCHK(hipMemsetAsync(e.count, 0, sizeof(int) * sM, c.st));
+        k = 0;
+      }
+    }
+    HIPCHK(hipStreamSynchronize(c.st));
+    e.steps += nsteps;
+    if (stats)
+      for (size_t k = 0; k < (size_t)nsteps * sM; ++k) {
+        pucfem_step_stats& o = stats[k];
+        const double* r = h.data() + 8 * k;
+        o.max_div_star = r[0];
+        o.max_final_div = r[1];
+        o.mix_I = r[2];
+        o.mix_mu = r[3];
+        o.mix_var = r[4];
+        o.eaten = (int64_t)std::llround(r[5]);
+        o.sl_notfound = (int32_t)std::llround(r[6]);
+        o.it_visc = o.it_p = o.it_p2 = 0;
+      }
   });
 }
 

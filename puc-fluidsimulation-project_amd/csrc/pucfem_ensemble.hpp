@@ -1,0 +1,381 @@
+// Ensemble kernels (pucfem_ens_*, include/pucfem.h): M members stepped together on one built small-mesh context
+// (Ctx::dense) -- the reference's experiment, the same mesh and fluid under several squirmers (README.md:43-45:
+// neutral / pusher / puller), in one launch chain.
+//
+// Members share every operator of the context (Vinv / Pinv, the SELL gradient / divergence coefficients, the
+// record locator, the tracer grid) and differ in their Dirichlet values, fields and tracers.  State arrays are
+// member-major in the context's internal row numbering and layouts (u / u*: interleaved pairs).  The member is
+// blockIdx.y; the dense products take a compile-time tile of ENS_TM members per block, so each loaded matrix
+// element is applied to ENS_TM members (one accumulator each) before the next is loaded.
+//
+// Arithmetic contract: per member, every kernel here performs the single path's operations in the single path's
+// order (the same j = lane, lane + 64, ... accumulation and wave_sum of the dense products, the same ax / d forms,
+// the single path's sl_* / tracer_* device functions, the same per-block partials and red_finish's order for the
+// reductions, on the single path's grid in x).  With -ffp-contract=off a member's fields are therefore the bits
+// of a single-context run with its boundary values (tests/test_gpu_ensemble.py).
+#pragma once
+#include "pucfem_kernels.hpp"
+#include "pucfem_kernels_impl.hpp"
+
+namespace pucfem {
+namespace dev {
+
+constexpr int ENS_TM = 4;     // members per block of the dense products
+constexpr int ENS_VALS = 16;  // per-member value slots (k_stats' layout in 0..6; 8: scratch maximum, 9: sum(braw))
+
+// the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
+// (nv partial arrays of gridDim.x blocks per member)
+__device__ __forceinline__ RedOut ens_red(const RedOut& ro, int32_t m, double*& part) {
+  RedOut R = ro;
+  R.out = ro.out + (int64_t)ENS_VALS * m;
+  R.out1 = ro.out1 ? ro.out1 + (int64_t)ENS_VALS * m : nullptr;
+  R.cnt = ro.cnt + m;
+  R.stride = (int)gridDim.x;
+  part += (int64_t)m * 3 * gridDim.x;
+  return R;
+}
+
+// k_dense_mv2_bc for a tile of members: u* = A_visc^-1 u with the velocity BCs of the result.  u, us: M x 2n;
+// dval: M x dstride (the member's Dirichlet values in the context's entry order).  Dynamic LDS: 2 n ENS_TM doubles
+// (component-major per member: consecutive lanes read consecutive doubles).  A ragged last tile computes its
+// missing members as copies of the last member and does not store them.
+template <int TM>
+__global__ __launch_bounds__(BS) void k_ens_mv2_bc(int64_t n, int32_t M, const double* __restrict__ Ainv,
+                                                   const double* __restrict__ u, double* __restrict__ us,
+                                                   const int32_t* __restrict__ bsrc, const int32_t* __restrict__ bdir,
+                                                   const double* __restrict__ dval, int64_t dstride) {
+  extern __shared__ __align__(16) double ens_xl[];
+  const int32_t m0 = (int32_t)blockIdx.y * TM;
+#pragma unroll
+  for (int t = 0; t < TM; ++t) {
+    const int32_t mt = m0 + t < M ? m0 + t : M - 1;
+    const dbl2* x = reinterpret_cast<const dbl2*>(u) + (int64_t)mt * n;
+    for (int64_t j = threadIdx.x; j < n; j += BS) {
+      const dbl2 q = x[j];
+      ens_xl[(2 * t) * n + j] = q.x;
+      ens_xl[(2 * t + 1) * n + j] = q.y;
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
+    const int32_t d = bdir[row];
+    if (d >= 0) {
+      if (lane < TM && m0 + lane < M) {
+        const double* dv = dval + (int64_t)(m0 + lane) * dstride;
+        reinterpret_cast<dbl2*>(us)[(int64_t)(m0 + lane) * n + row] = dbl2{dv[2 * d], dv[2 * d + 1]};
+      }
+      continue;
+    }
+    const double* a = Ainv + (int64_t)bsrc[row] * n;
+    double s0[TM], s1[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) s0[t] = s1[t] = 0.0;
+    for (int64_t j = lane; j < n; j += 64) {
+      const double v = a[j];
+#pragma unroll
+      for (int t = 0; t < TM; ++t) {
+        s0[t] += v * ens_xl[(2 * t) * n + j];
+        s1[t] += v * ens_xl[(2 * t + 1) * n + j];
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TM; ++t) {
+      s0[t] = wave_sum(s0[t]);
+      s1[t] = wave_sum(s1[t]);
+    }
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+      if (lane == 0 && m0 + t < M) reinterpret_cast<dbl2*>(us)[(int64_t)(m0 + t) * n + row] = dbl2{s0[t], s1[t]};
+  }
+}
+
+// k_dense_pres for a tile of members: the restated right-hand side from the member's braw and its reduced sum
+// (vals slot 9), the pseudo-inverse product, p with every slave taking its master's value.  braw, p: M x n.
+// Dynamic LDS: n ENS_TM doubles.
+template <int TM>
+__global__ __launch_bounds__(BS) void k_ens_pres(int64_t n, int32_t M, const double* __restrict__ Pinv,
+                                                 const double* __restrict__ braw, const int32_t* __restrict__ slave_of,
+                                                 const int32_t* __restrict__ master_of, const double* __restrict__ vals,
+                                                 double inv_nfree, double* __restrict__ p) {
+  extern __shared__ __align__(16) double ens_bl[];
+  const int32_t m0 = (int32_t)blockIdx.y * TM;
+#pragma unroll
+  for (int t = 0; t < TM; ++t) {
+    const int32_t mt = m0 + t < M ? m0 + t : M - 1;
+    const double* br = braw + (int64_t)mt * n;
+    const double mean = vals[(int64_t)ENS_VALS * mt + 9] * inv_nfree;
+    for (int64_t j = threadIdx.x; j < n; j += BS) {
+      double b;
+      if (master_of[j] >= 0) {
+        b = 0.0;
+      } else {
+        b = br[j];
+        if (slave_of[j] >= 0) b += br[slave_of[j]];
+        b = b - mean;
+      }
+      ens_bl[t * n + j] = b;
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4) {
+    if (master_of[row] >= 0) continue;  // (a slave row's p is its master's; nothing else reads its product)
+    const double* a = Pinv + row * n;
+    double acc[TM];
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[t] = 0.0;
+    for (int64_t j = lane; j < n; j += 64) {
+      const double v = a[j];
+#pragma unroll
+      for (int t = 0; t < TM; ++t) acc[t] += v * ens_bl[t * n + j];
+    }
+#pragma unroll
+    for (int t = 0; t < TM; ++t) acc[t] = wave_sum(acc[t]);
+    const int32_t sl = slave_of[row];
+#pragma unroll
+    for (int t = 0; t < TM; ++t)
+      if (lane == 0 && m0 + t < M) {
+        double* pm = p + (int64_t)(m0 + t) * n;
+        pm[row] = 1.0 * acc[t];
+        if (sl >= 0) pm[sl] = 1.0 * acc[t];
+      }
+  }
+}
+
+// k_div (SELL rows, interleaved velocity) per member: max |div| and, with braw, the pressure right-hand side and
+// its sum.  u: M x 2n, braw: M x n (or null), part: M x 3 gridDim.x.  gridDim.x: the single path's div grid.
+template <bool C16>
+__global__ __launch_bounds__(BS) void k_ens_div(SellDev A, const double* __restrict__ gx, const double* __restrict__ gy,
+                                                const double* __restrict__ u, const double* __restrict__ as1,
+                                                const double* __restrict__ mp, double negidt, double* __restrict__ braw,
+                                                double* part, RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const int64_t n = A.n_own;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  double* bm = braw ? braw + (int64_t)m * n : nullptr;
+  const RedOut R = ens_red(ro, m, part);
+  double mx = 0.0, sb = 0.0;
+  int64_t s0, s1;
+  block_slices_n(A.nslices, gridDim.x, blockIdx.x, s0, s1);
+  const int lane = threadIdx.x & 63, wv = wave_id();
+  for (int64_t s = s0 + wv; s < s1; s += 4) {
+    const int64_t off = A.off[s];
+    const int w = A.w[s];
+    const int64_t row = sell_row(A, s, lane);
+    const int32_t base = (int32_t)(s * 64);
+    double acc = 0.0;
+    for (int k = 0; k < w; ++k) {
+      const int64_t e = off + (int64_t)k * 64 + lane;
+      const dbl2 q = um[sell_col<C16, false>(A, e, base)];
+      acc += gx[e] * q.x + gy[e] * q.y;
+    }
+    if (row >= 0) {
+      const double d = acc / as1[row];
+      mx = fmax(mx, fabs(d));
+      if (bm) {
+        const double b = mp[row] * (negidt * d);
+        bm[row] = b;
+        sb += b;
+      }
+    }
+  }
+  const double t = block_max(mx, sh);
+  const double v = block_sum(sb, sh);
+  if (threadIdx.x == 0) {
+    red_part(R, part, 0, t);
+    red_part(R, part, 1, v);
+  }
+  red_finish(R, part, sh);
+}
+
+// k_grad_proj_bc per member: the first projection with the velocity BCs.  p: M x n, us / u: M x 2n.
+template <bool C16>
+__global__ __launch_bounds__(BS) void k_ens_grad_proj_bc(SellDev A, const double* __restrict__ gx,
+                                                         const double* __restrict__ gy, const double* __restrict__ p,
+                                                         const double* __restrict__ as1, double dt, const double* us,
+                                                         double* u, const int32_t* __restrict__ bsrc,
+                                                         const int32_t* __restrict__ bdir,
+                                                         const int32_t* __restrict__ spos,
+                                                         const double* __restrict__ dval, int64_t dstride) {
+  const int32_t m = (int32_t)blockIdx.y;
+  const int64_t n = A.n_own;
+  const double* pm = p + (int64_t)m * n;
+  const dbl2* usm = reinterpret_cast<const dbl2*>(us) + (int64_t)m * n;
+  dbl2* um = reinterpret_cast<dbl2*>(u) + (int64_t)m * n;
+  const double* dv = dval + (int64_t)m * dstride;
+  for (int64_t t = (int64_t)blockIdx.x * BS + threadIdx.x; t < A.nslices * 64; t += (int64_t)gridDim.x * BS) {
+    const int64_t row = sell_row(A, t >> 6, (int)(t & 63));
+    if (row < 0) continue;
+    const int32_t dj = bdir[row];
+    if (dj >= 0) {
+      um[row] = dbl2{dv[2 * dj], dv[2 * dj + 1]};
+      continue;
+    }
+    const int32_t src = bsrc[row];
+    const int64_t pos = src == row ? t : (int64_t)spos[src];
+    const int64_t ss = pos >> 6;
+    const int lane = (int)(pos & 63);
+    const int64_t off = A.off[ss];
+    const int w = A.w[ss];
+    const int32_t base = (int32_t)(ss * 64);
+    const dbl2 o = usm[src];
+    const double d = as1[src];
+    double ax = 0.0, ay = 0.0;
+    for (int k = 0; k < w; ++k) {
+      const int64_t e = off + (int64_t)k * 64 + lane;
+      const double pj = pm[sell_col<C16, false>(A, e, base)];
+      ax += gx[e] * pj;
+      ay += gy[e] * pj;
+    }
+    um[row] = dbl2{o.x - dt * (ax / d), o.y - dt * (ay / d)};
+  }
+}
+
+// k_grad_proj mode 1 (SELL rows) per member: u[interior] -= DT grad p2.
+template <bool C16>
+__global__ __launch_bounds__(BS) void k_ens_grad_proj1(SellDev A, const double* __restrict__ gx,
+                                                       const double* __restrict__ gy, const double* __restrict__ p,
+                                                       const double* __restrict__ as1, double dt,
+                                                       const uint8_t* __restrict__ dirflag, double* u) {
+  const int32_t m = (int32_t)blockIdx.y;
+  const int64_t n = A.n_own;
+  const double* pm = p + (int64_t)m * n;
+  dbl2* um = reinterpret_cast<dbl2*>(u) + (int64_t)m * n;
+  int64_t s0, s1;
+  block_slices_n(A.nslices, gridDim.x, blockIdx.x, s0, s1);
+  const int lane = threadIdx.x & 63, wv = wave_id();
+  for (int64_t s = s0 + wv; s < s1; s += 4) {
+    const int64_t off = A.off[s];
+    const int w = A.w[s];
+    const int64_t row = sell_row(A, s, lane);
+    const int32_t base = (int32_t)(s * 64);
+    const int64_t rr = row >= 0 ? row : 0;
+    const dbl2 o = um[rr];
+    const double d = as1[rr];
+    const bool dirichlet = dirflag[rr] != 0;
+    double ax = 0.0, ay = 0.0;
+    for (int k = 0; k < w; ++k) {
+      const int64_t e = off + (int64_t)k * 64 + lane;
+      const double pj = pm[sell_col<C16, false>(A, e, base)];
+      ax += gx[e] * pj;
+      ay += gy[e] * pj;
+    }
+    if (row >= 0 && !dirichlet) um[row] = dbl2{o.x - dt * (ax / d), o.y - dt * (ay / d)};
+  }
+}
+
+// k_sl_rec_wave per member (row0 = 0: one rank): one wave per row, the single path's locator functions.
+// u: M x 2n, c / cout: M x n, part: M x 3 gridDim.x.
+__global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, int64_t n, const double* __restrict__ u,
+                                               double dt, const double* __restrict__ c, double* __restrict__ cout,
+                                               const double* __restrict__ wmix, double* part, RedOut ro) {
+  __shared__ double sw_[3][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const double* ux = u + (int64_t)m * 2 * n;
+  const double* uy = ux + 1;
+  const double* cm = c + (int64_t)m * n;
+  double* com = cout + (int64_t)m * n;
+  const RedOut R = ens_red(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double swc = 0.0, sw = 0.0, nnf = 0.0;
+  if (i < n) {
+    double xb, yb;
+    sl_point(Mh, i, ux[VS * i], uy[VS * i], dt, xb, yb);
+    SlTri r;
+    double bestd;
+    float rho2;
+    const bool cand = sl_best_wave(L, xb, yb, r, bestd, rho2);
+    const bool ok = cand && (sl_fast(L, r, xb, yb, bestd, rho2) || sl_rank_ok_wave(G, xb, yb, bestd, r.id));
+    double cn;
+    if (ok) {
+      cn = sl_value(r, xb, yb, cm);
+    } else {
+      cn = cm[i];
+      nnf = 1.0;
+    }
+    if (lane == 0) com[i] = cn;
+    const double w = wmix[i];
+    sw = w;
+    swc = w * cn;
+  }
+  if (lane == 0) {
+    sw_[0][wv] = swc;
+    sw_[1][wv] = sw;
+    sw_[2][wv] = nnf;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  red_finish(R, part, sh);
+}
+
+// k_mix2 per member: sum w (c - mu)^2 of the new dye cn (mu from vals 2 / 3), copied into c.  cn, c: M x n.
+__global__ __launch_bounds__(BS) void k_ens_mix2(int64_t n, const double* __restrict__ cn, const double* __restrict__ wmix,
+                                                 const double* vals, double* part, RedOut ro, double* __restrict__ c) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const double* cnm = cn + (int64_t)m * n;
+  double* cm = c + (int64_t)m * n;
+  const double* vm = vals + (int64_t)ENS_VALS * m;
+  const RedOut R = ens_red(ro, m, part);
+  const double swc = reduce_partials(vm + 2, 1, sh);
+  const double sw = reduce_partials(vm + 3, 1, sh);
+  const double mu = swc / sw;
+  double acc = 0.0;
+  int64_t r0, r1;
+  block_rows(n, r0, r1);
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += BS) {
+    const double ci = cnm[i];
+    cm[i] = ci;
+    const double d = ci - mu;
+    acc += wmix[i] * (d * d);
+  }
+  const double t = block_sum(acc, sh);
+  if (threadIdx.x == 0) red_part(R, part, 0, t);
+  red_finish(R, part, sh);
+}
+
+// k_tracer per member (one block each): the single path's locate / interpolate / move.  tx, ty, status: M x ntr.
+__global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
+                                                   int32_t ntr, double* tx, double* ty, double* status, double dt,
+                                                   double cx, double cy, double capture, double* vals) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const double* ux = u + (int64_t)m * 2 * n;
+  const double* uy = ux + 1;
+  double* txm = tx + (int64_t)m * ntr;
+  double* tym = ty + (int64_t)m * ntr;
+  double* stm = status + (int64_t)m * ntr;
+  double eaten = 0.0;
+  for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
+    const double px = txm[k], py = tym[k];
+    double vx = NAN, vy = NAN;
+    const int32_t found = tracer_locate(Mh, G, px, py);
+    if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+    eaten += tracer_move(txm, tym, stm, k, vx, vy, dt, cx, cy, capture);
+  }
+  const double t = block_sum(eaten, sh);
+  if (threadIdx.x == 0) vals[(int64_t)ENS_VALS * m + 6] = t;
+}
+
+// the step's record of every member (k_stats_ring per member): slot count[m] of the ring (steps x M x 8)
+__global__ void k_ens_record(int32_t M, const double* vals, double* ring, int* count) {
+  const int32_t m = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (m >= M) return;
+  const int k = count[m];
+  stats_body(vals + (int64_t)ENS_VALS * m, ring + 8 * ((int64_t)k * M + m), 7);
+  count[m] = k + 1;
+}
+
+}  // namespace dev
+}  // namespace pucfem

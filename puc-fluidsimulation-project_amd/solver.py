@@ -416,6 +416,178 @@ class StokesSimulation:
         self.ctx.close()
 
 
+_SHARED_BC_FIELDS = ("nu", "center", "capture_radius", "squirmer_radius")
+
+
+def _check_ensemble_bcs(bcs):
+    bcs = list(bcs)
+    if not bcs:
+        raise ValueError("an ensemble needs at least one SquirmerBC")
+    for f in _SHARED_BC_FIELDS:
+        vals = [tuple(getattr(b, f)) if f == "center" else getattr(b, f) for b in bcs]
+        if any(v != vals[0] for v in vals):
+            raise ValueError(f"ensemble members share the fluid and the swimmer's geometry: {f} differs ({vals})")
+    return bcs
+
+
+def ensemble_dirichlet_values(mesh: Mesh, bcs):
+    """Dirichlet nodes and per-member values (M, n_dir, 2) of an ensemble: row m is stokes_setup(mesh, bcs[m])'s
+    values (the wall values, then the squirmer surface values of makeDirBCU, StokesColor.py:405-427).  Host only."""
+    bcs = _check_ensemble_bcs(bcs)
+    nodes = None
+    vals = []
+    for bc in bcs:
+        _, n, v = stokes_setup(mesh, bc)
+        if nodes is None:
+            nodes = n
+        elif not np.array_equal(nodes, n):
+            raise ValueError("ensemble members must share the Dirichlet node list")
+        vals.append(v)
+    return nodes, np.ascontiguousarray(np.stack(vals, 0), dtype=np.float64)
+
+
+class StokesEnsemble:
+    """M squirmers on one mesh and fluid, stepped together on one GPU context (pucfem_ens_*): the reference's
+    experiment (README.md:43-45: the neutral, pusher and puller squirmer on mesh.1) or a B1 / B2 sweep in one
+    launch chain.  Members share nu, dt, the mesh and the swimmer's geometry and differ in their boundary values,
+    fields and tracers; each member's fields are bit-identical to a StokesSimulation with its SquirmerBC.
+    Small meshes only (the dense path: N <= 1500), scheme 'color' (semi-Lagrangian dye) or 'food'."""
+
+    def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
+                 tracers=None):
+        self.bcs = _check_ensemble_bcs(bcs)
+        if scheme not in ("color", "food"):
+            raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
+        nodes, vals = ensemble_dirichlet_values(mesh, self.bcs)
+        self.mesh = mesh
+        self.dt = dt
+        self.scheme = scheme
+        self.M = len(self.bcs)
+        bc0 = self.bcs[0]
+        self.ctx = Context(device)
+        try:
+            self.ctx.upload(mesh)
+            pairs, _, _ = stokes_setup(mesh, bc0)
+            self.ctx.set_pairs(0, pairs)
+            self.ctx.set_pairs(1, pairs)
+            self.ctx.set_dirichlet(nodes, vals[0])
+            self.ctx.build(scheme, dt, bc0.nu, tol or Tolerances(), bc0.capture_radius, bc0.center, 0)
+            self.n_tracers = 0
+            if scheme == "food":
+                from .tracers import tracer_init
+
+                pts = tracer_init(bc0.squirmer_radius, bc0.center) if tracers is None else tracers
+                pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+                self.ctx.set_field(_lib.F_TRACERS, pts)
+                self.n_tracers = len(pts)
+            self.ctx._c(self.ctx.L.pucfem_ens_create(self.ctx.h, self.M, _lib.dptr(vals)))
+        except Exception:
+            self.ctx.close()
+            raise
+        self.step_count = 0
+        self.history = []
+
+    # ---- fields (member = None: all members, leading axis M)
+    def _shape(self, f, ncomp=1):
+        if f == _lib.F_TRACERS:
+            return (self.n_tracers, 2)
+        if f == _lib.F_STATUS:
+            return (self.n_tracers,)
+        return (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,)
+
+    def get(self, f, ncomp=1, member=None):
+        shape = self._shape(f, ncomp)
+        out = np.zeros(shape if member is not None else (self.M,) + shape)
+        self.ctx._c(self.ctx.L.pucfem_ens_get_field(self.ctx.h, f, -1 if member is None else int(member),
+                                                    _lib.dptr(out), out.size))
+        return out
+
+    def set(self, f, a, member=None):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        self.ctx._c(self.ctx.L.pucfem_ens_set_field(self.ctx.h, f, -1 if member is None else int(member),
+                                                    _lib.dptr(a), a.size))
+
+    def field(self, f, ncomp=1):
+        return self.get(f, ncomp)
+
+    @property
+    def u(self):
+        return self.get(_lib.F_U, 2)
+
+    @u.setter
+    def u(self, v):
+        self.set(_lib.F_U, v)
+
+    @property
+    def c(self):
+        return self.get(_lib.F_C)
+
+    @c.setter
+    def c(self, v):
+        self.set(_lib.F_C, v)
+
+    @property
+    def tracers(self):
+        return self.get(_lib.F_TRACERS)
+
+    @tracers.setter
+    def tracers(self, v):
+        self.set(_lib.F_TRACERS, v)
+
+    @property
+    def tracer_status(self):
+        return self.get(_lib.F_STATUS).astype(np.int64)
+
+    @tracer_status.setter
+    def tracer_status(self, v):
+        self.set(_lib.F_STATUS, np.asarray(v, dtype=np.float64))
+
+    def step(self, n=1, stats=True):
+        """n steps of every member: a list over the steps of lists over the members of step records
+        (stats=False: no records are copied back, an empty list -- long sweeps that read only the final fields)."""
+        self.step_count += n
+        if not stats:
+            self.ctx._c(self.ctx.L.pucfem_ens_step(self.ctx.h, n, None))
+            return []
+        st = (_lib.StepStats * max(n * self.M, 1))()
+        self.ctx._c(self.ctx.L.pucfem_ens_step(self.ctx.h, n, st))
+        out = [[st[s * self.M + m] for m in range(self.M)] for s in range(n)]
+        self.history.extend(out)
+        return out
+
+    def info(self):
+        o = (ct.c_int64 * 4)()
+        self.ctx._c(self.ctx.L.pucfem_ens_info(self.ctx.h, o))
+        return dict(members=o[0], member_tile=o[1], state_bytes=o[2], steps=o[3])
+
+    def close(self):
+        self.ctx.close()
+
+
+def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None):
+    """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`."""
+    if scheme not in ("color", "food"):
+        raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
+    dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
+    ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol)
+    try:
+        st = ens.step(steps) if steps else []
+        u, p = ens.u, ens.get(_lib.F_P)
+        c = ens.c if scheme == "color" else None
+        tr, ts = (ens.tracers, ens.tracer_status) if scheme == "food" else (None, None)
+    finally:
+        ens.close()
+    res = []
+    for m in range(ens.M):
+        r = Result(scheme, steps, u=u[m], p=p[m], stats=[s[m] for s in st])
+        if scheme == "color":
+            r.c = c[m]
+        else:
+            r.tracers, r.tracer_status = tr[m], ts[m]
+        res.append(r)
+    return res
+
+
 def _literal_setup(mesh32: Mesh):
     """poisson.py:221-278 / heatEq.py:222-301 host setup on fp32 coordinates."""
     X = mesh32.coords
