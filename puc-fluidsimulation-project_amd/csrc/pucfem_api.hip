@@ -20,8 +20,6 @@
 #include <tuple>
 #include <utility>
 #include <vector>
-#include <future>
-#include <map>
 
 #include "pucfem.h"
 #include "pucfem_comm.hpp"
@@ -586,26 +584,8 @@ struct Ctx {
   double* gring = nullptr;
   int* gcount = nullptr;
   bool gcapture = false;  // (the step being captured)
-  // the captured step's record appended by k_mix2's reducing block (PUCFEM_RING_FOLD=0, measurement knob: k_stats_ring)
-  bool ring_fold = !(std::getenv("PUCFEM_RING_FOLD") && std::atoi(std::getenv("PUCFEM_RING_FOLD")) == 0);
+  // the captured step's record appended by k_mix2's reducing block (otherwise k_stats_ring)
   bool ring_in_mix = false;
-  // the captured step's fork (PUCFEM_GRAPH_FORK=1, measurement knob, off): a side stream and its events, made before
-  // the capture (prep_fork).  The same bits, but the graph's cross-stream edges cost more than the overlap gains:
-  // mesh_fine 10.0k steps/s forked against 12.5k in one chain (r14q)
-  hipStream_t st_fk = nullptr;
-  hipEvent_t ev_fk = nullptr, ev_fj = nullptr;
-  bool fork_pend = false;
-  void prep_fork() {
-    if (st_fk || !(std::getenv("PUCFEM_GRAPH_FORK") && std::atoi(std::getenv("PUCFEM_GRAPH_FORK")) != 0)) return;
-    HIPCHK(hipStreamCreateWithFlags(&st_fk, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&ev_fk, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ev_fj, hipEventDisableTiming));
-  }
-  void fork_join() {
-    if (!fork_pend) return;
-    HIPCHK(hipStreamWaitEvent(st, ev_fj, 0));
-    fork_pend = false;
-  }
 
   // ---- lattice operators (pucfem_lattice.hpp): multigrid hierarchies with faces of interior nodes
   bool lattice = false;
@@ -642,8 +622,6 @@ struct Ctx {
   // PUCFEM_MG_PAIR=0 runs every step as its own k_cheb (a measurement knob); a third x buffer and a second
   // d buffer of the finest level are allocated on first use
   bool mg_pair = !(std::getenv("PUCFEM_MG_PAIR") && std::atoi(std::getenv("PUCFEM_MG_PAIR")) == 0);
-  // PUCFEM_MG_PAIR_LEVELS (measurement knob): the step pairs on the finest k levels (default 1: the finest only)
-  int mg_pair_levels = std::getenv("PUCFEM_MG_PAIR_LEVELS") ? std::max(1, std::atoi(std::getenv("PUCFEM_MG_PAIR_LEVELS"))) : 1;
   int64_t mg_pairs = 0;
   float* mgp_x = nullptr;
   float* mgp_d = nullptr;
@@ -656,15 +634,9 @@ struct Ctx {
   bool use_mg = false;
   std::vector<MgLevel> mg;
   double* dKp_raw = nullptr;        // unscaled finest pressure operator on sPp
-  double* dAinv = nullptr;          // dense pseudo-inverse of the coarse-solve level's operator (replicated)
-  float* dAinv32 = nullptr;         // its fp32 copy (the fp32 V-cycle, when that level is not the coarsest)
-  // The V-cycle's dense coarse solve runs on level mg_dense_l: 0 (the coarsest, mesh_fine's 1,067 nodes), or with
-  // PUCFEM_MG_DENSE_LEVEL=1 (measurement knob) on level 1: the ~3.6k-node level's 8 latency-bound launches per V-cycle
-  // and the coarsest's dense solve replaced by one fp32 dense product.  At L7: 238 -> 214 launches per step, the
-  // window +0.3 %, steady +0.6 % (within the spread), but the per-step parity margin at L7 5.7x / 7.5x -> 3.6x / 5.2x
-  // (the iterates take another path to the tolerance) and setup +1 s (r12f / r12g): off.
-  int mg_dense_l = 0;
-  std::future<std::vector<double>> dense_fut;  // level mg_dense_l > 0: its inverse, computed beside the rest of setup
+  // dense pseudo-inverse of the coarsest level's operator (replicated).  The dense solve one level up instead gained
+  // nothing within the spread and halved the L7 parity margin (r12f / r12g).
+  double* dAinv = nullptr;
   bool mg_single = false;                        // fp32 V-cycle
   double* z = nullptr;              // preconditioned residual (finest; the fp64 V-cycle's)
   // the fp32 V-cycle's z: its last smoothing step computes in fp32, so z is fp32-exact -- stored as such,
@@ -675,18 +647,16 @@ struct Ctx {
   // (which = 3, 4: the viscous solve's x and y components, proj_k_visc directions each)
   int proj_k = 0, proj_k_visc = 0;
   ProjT* projX[5] = {};
-  i64 ldx = 0;  // column-major basis (PUCFEM_PROJ_TILED=0): the vectors' stride, nloc rounded up to even
-  // the basis of slot w: its ld argument (tiled: the capacity) and the offset of its vector i
-  i64 pld(int w) const { return PUCFEM_PROJ_TILED ? (w <= 2 ? proj_k : proj_k_visc) : ldx; }
-  i64 pcol(int w, int i) const { return PUCFEM_PROJ_TILED ? 64 * (i64)i : (i64)i * ldx; }
+  // the basis of slot w: its ld argument (the capacity) and the offset of its vector i
+  i64 pld(int w) const { return w <= 2 ? proj_k : proj_k_visc; }
+  i64 pcol(int, int i) const { return 64 * (i64)i; }
   double* proj_x0[5] = {};
   int proj_m[5] = {0, 0, 0, 0, 0};
   // Deferred update (project_guess): after a solve only v = y - x0 and A v are formed; the next
   // guess of the same solve orthogonalises v against X, appends it and projects the new right-hand
   // side in one multi-dot and one combination pass over X.  h_coef (pinned) receives each guess's
   // coefficients, read at the next guess to track the coordinates of the recent solutions in the
-  // basis (re-seeding a full basis, proj_reseed).  PUCFEM_PROJ_KEEP (measurement knob, 2..16,
-  // default 16): seeds kept.
+  // basis (re-seeding a full basis, proj_reseed, which keeps proj_keep seeds).
   static constexpr int NCOEF = 2 * PROJ_MAX + 4;
   double* h_coef = nullptr;
   ProjT* projXalt[5] = {};
@@ -695,9 +665,7 @@ struct Ctx {
     std::vector<double> gamma;              // coordinates of the last guess x0
     int coef_m = -1;                        // h_coef holds a guess over coef_m directions (-1: none)
   } proj_hist[5];
-  int proj_keep = std::getenv("PUCFEM_PROJ_KEEP")
-                      ? std::max(2, std::min(PROJ_KEEP_MAX, std::atoi(std::getenv("PUCFEM_PROJ_KEEP"))))
-                      : 16;
+  static constexpr int proj_keep = PROJ_KEEP_MAX;
   double *proj_part = nullptr, *proj_d = nullptr, *proj_coef = nullptr;
   double* dqm = nullptr;  // re-seed coefficients (QMat) on the device
   bool proj_pend[5] = {false, false, false, false, false};  // v / A v wait for the next guess
@@ -766,9 +734,6 @@ struct Ctx {
       if (graph) (void)hipGraphDestroy(graph);
       if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
       if (graph_k) (void)hipGraphDestroy(graph_k);
-      if (st_fk) (void)hipStreamDestroy(st_fk);
-      if (ev_fk) (void)hipEventDestroy(ev_fk);
-      if (ev_fj) (void)hipEventDestroy(ev_fj);
       for (void* a : allocs) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
       if (h_coef) (void)hipHostFree(h_coef);
@@ -887,62 +852,30 @@ struct Ctx {
 
   static int nb_for(i64 nslices) { return (int)std::max<i64>(1, std::min<i64>(EWB, (nslices + 3) / 4)); }
   // grid of the V-cycle kernels that produce no partials (more waves in flight than MAXB blocks)
-  int mg_nb_max = 16384;
-  int nb_mg(i64 nslices) const { return (int)std::max<i64>(1, std::min<i64>(mg_nb_max, (nslices + 3) / 4)); }
+  static int nb_mg(i64 nslices) { return (int)std::max<i64>(1, std::min<i64>(16384, (nslices + 3) / 4)); }
   int nb_rows(i64 n) const { return nb_for((n + 63) / 64); }
   // semi-Lagrangian grid: latency-bound gathers want more waves in flight than MAXB blocks give
-  // PUCFEM_SL_BLOCKS (measurement knob): a cap on k_sl's grid below SLB (fewer resident waves beside the main
-  // stream's kernels; the rows per block grow, the per-wave queue follows them)
-  int sl_cap = std::getenv("PUCFEM_SL_BLOCKS") ? std::max(8, std::min(SLB, std::atoi(std::getenv("PUCFEM_SL_BLOCKS"))))
-                                               : SLB;
-  // PUCFEM_SL_LDS (measurement knob): dynamic LDS bytes requested by the k_sl launches (unused by the kernel): caps
-  // the k_sl blocks resident per CU (160 KB / bytes), leaving wave slots and registers to the main stream
-  size_t sl_lds = std::getenv("PUCFEM_SL_LDS") ? (size_t)std::max(0, std::min(65536, std::atoi(std::getenv("PUCFEM_SL_LDS"))))
-                                               : 0;
   // PUCFEM_SL_WAVE (measurement knob): the lattice locator's second pass -- 2 (default) the numbered list
   // (k_sl_qscan + k_sl_wq + k_sl_qsum), 1 k_sl_wave (each wave its own queue), 0 k_sl_slow (one lane per point)
   int sl_wave_mode = std::getenv("PUCFEM_SL_WAVE") ? std::atoi(std::getenv("PUCFEM_SL_WAVE")) : 2;
   bool sl_wave = sl_wave_mode != 0;
   int nb_sl(i64 n) const {
     if (sl_rec_wave(n)) return (int)((n + BS / 64 - 1) / (BS / 64));  // k_sl_rec_wave: a wave per row
-    return (int)std::max<i64>(1, std::min<i64>(sl_cap, (n + 4 * 64 - 1) / (4 * 64)));
+    return (int)std::max<i64>(1, std::min<i64>(SLB, (n + 4 * 64 - 1) / (4 * 64)));
   }
   // the record locator on a small mesh (mesh.1, mesh_fine): one wave per row in one launch instead of k_sl queueing
   // every row for k_sl_slow's one lane per point (PUCFEM_SL_WAVE=0 keeps the two passes)
   bool sl_rec_wave(i64 n) const { return !lat_sl && sl_wave && n <= SLB * (BS / 64); }
   static int grid_ew(i64 n) { return (int)std::max<i64>(1, std::min<i64>(2048, (n + BS - 1) / BS)); }
-  // A grid-stride kernel whose grid holds more blocks than the chip keeps resident runs its work in two rounds of
-  // equal blocks, the second on part of the chip (k_mdot2 at 96 VGPRs: 5 blocks per CU resident, 1,280 of its 2,048);
-  // fit_grid gives the resident count (hipOccupancy..., cached per kernel) for such a grid.  With PUCFEM_FIT_GRID=1
-  // (measurement knob, off) k_mdot2 keeps its 2,048 blocks' rows and partials as virtual blocks run by a grid of
-  // nb / ceil(nb / resident) blocks: the same bits, and no faster (461 vs 465 us, r14g: 1,024 blocks of two units at
-  // 4 blocks per CU).  Capping the grid itself made k_mdot2 442 -> 397 us, but its partials then group other rows, the
-  // projection's guesses differ in their last bits and with them where each production solve stops below rtol: the
-  // L7 per-step margins went 5.7x / 7.5x -> 2.8x / 2.6x (r14d / r14e), so the plain grid stays.
-  bool fit_grid_on = std::getenv("PUCFEM_FIT_GRID") && std::atoi(std::getenv("PUCFEM_FIT_GRID")) != 0;
-  std::map<const void*, int> resident_blocks;
-  int n_cu = 0;
-  int fit_grid(const void* kern, int nb) {
-    if (!fit_grid_on) return nb;
-    auto it = resident_blocks.find(kern);
-    if (it == resident_blocks.end()) {
-      if (n_cu == 0) {
-        int d = 0;
-        HIPCHK(hipGetDevice(&d));
-        HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, d));
-      }
-      int per = 0;
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, BS, 0));
-      it = resident_blocks.emplace(kern, std::max(1, per) * std::max(1, n_cu)).first;
-    }
-    return std::max(1, std::min(nb, it->second));
-  }
+  // k_mdot2's 2,048 blocks do not all fit the chip (at the 96 VGPRs of r14 1,280 were resident, the rest a second
+  // round).  Virtual blocks on a resident grid gave the same bits and no speed (461 vs 465 us, r14g); capping the grid itself was faster (442 -> 397 us) but
+  // regroups the partials, and the L7 per-step margins went 5.7x / 7.5x -> 2.8x / 2.6x (r14d / r14e): the plain grid
+  // stays.
 
   // ------------------------------------------------------------------ timing helpers
   // Launch on the library stream.  When timing (cls >= 0), the start / stop events are taken by the
   // kernel's dispatch itself (hipExtLaunchKernelGGL): the sample is the kernel's own duration, as
   // rocprofv3 reports it, without the command-processor gap a separately recorded event adds.
-  size_t kl_lds = 0;  // dynamic LDS of the launch (0 but around the k_sl launches with PUCFEM_SL_LDS)
   template <typename... KArgs, typename... Args>
   void klaunch(int cls, double bytes, void (*kernel)(KArgs...), dim3 g, dim3 b, Args... args) {
     algo_bytes += bytes;
@@ -953,25 +886,20 @@ struct Ctx {
     if (timer.on && cls >= 0 && ((timer.mask >> cls) & 1u)) {
       hipEvent_t a = timer.get(), e = timer.get();
       ++g_nlaunch;
-      hipExtLaunchKernelGGL(kernel, g, b, kl_lds, st, a, e, 0, args...);
+      hipExtLaunchKernelGGL(kernel, g, b, 0, st, a, e, 0, args...);
       timer.pend.push_back({cls, a, e, bytes});
       if (timer.pend.size() > 4096) timer.flush();  // bounded number of live events
     } else {
-      hipLaunchKernelGGL(kernel, g, b, kl_lds, st, args...);
+      hipLaunchKernelGGL(kernel, g, b, 0, st, args...);
     }
   }
   // The solvers' host reads (convergence tests, |r_0|) wait by polling the event instead of a blocking
   // synchronize: a blocking wait that outlasts the runtime's short active spin sleeps on an interrupt, and
   // its wake-up left the GPU idle ~0.1 ms after every pressure solve (r10x trace: 124 us before each
-  // k_grad_proj).  PUCFEM_SPIN_WAIT=0 keeps the blocking calls (measurement knob).
-  bool spin_wait = !(std::getenv("PUCFEM_SPIN_WAIT") && std::atoi(std::getenv("PUCFEM_SPIN_WAIT")) == 0);
-  int spin_us = std::getenv("PUCFEM_SPIN_US") ? std::max(0, std::atoi(std::getenv("PUCFEM_SPIN_US"))) : 500;
+  // k_grad_proj).
+  static constexpr int spin_us = 500;
   hipEvent_t ev_wait = nullptr;
   void wait_event(hipEvent_t e) {
-    if (!spin_wait) {
-      HIPCHK(hipEventSynchronize(e));
-      return;
-    }
     // a bounded spin (the solvers' reads wait tens of microseconds): a longer wait blocks, so no host core
     // stays pinned beside other ranks' and the setup's threads
     const auto t0 = std::chrono::steady_clock::now();
@@ -989,10 +917,6 @@ struct Ctx {
     }
   }
   void sync_st() {  // hipStreamSynchronize(st) for the solvers' reads
-    if (!spin_wait) {
-      HIPCHK(hipStreamSynchronize(st));
-      return;
-    }
     if (!ev_wait) HIPCHK(hipEventCreateWithFlags(&ev_wait, hipEventDisableTiming));
     HIPCHK(hipEventRecord(ev_wait, st));
     wait_event(ev_wait);
@@ -1002,11 +926,6 @@ struct Ctx {
   void sl_launch(int nb, i64 row0, i64 n, const double* vx, const double* vy, double dt, const double* cf, double* cn,
                  const double* w, int32_t* nf, RedOut ro = RedOut{}) {
     const MeshDev M{mx, my, mtri, mesh.T};
-    struct LdsScope {  // (reset on unwind)
-      size_t& v;
-      LdsScope(size_t& x, size_t n) : v(x) { v = n; }
-      ~LdsScope() { v = 0; }
-    } lds_scope(kl_lds, sl_lds);
     if (lat_sl) {
       // per row: coordinates 16, u 16, c 8 (the departure triangle's vertices lie near the row: their
       // coordinate and c lines are the rows' own), home face 4, lattice cell entries 8 and fast-accept
@@ -1014,7 +933,6 @@ struct Ctx {
       const double sl_bytes = (16.0 + 16.0 + 8.0 + 4.0 + 8.0 + 8.0 + (w ? 8.0 : 0.0) + 8.0) * (double)n;
       klaunch(4, sl_bytes, k_sl<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, (int64_t)row0, (int64_t)n, vx,
               vy, dt, cf, cn, w, nf, part_sl, sl_queue, sl_qcnt);
-      kl_lds = 0;  // (the knob's LDS is k_sl's alone: k_sl_slow has static LDS of its own)
       // the queued rows: one wave per point (k_sl_wave, on k_sl's grid), or -- with the fused reductions (a
       // measurement knob) or PUCFEM_SL_WAVE=0 -- k_sl_slow on k_sl's grid, one lane per point
       if (sl_wave_mode == 2 && !ro.out) {
@@ -1034,13 +952,11 @@ struct Ctx {
         klaunch(8, 0.0, k_sl_slow<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, cgrid, (int64_t)row0, (int64_t)n, vx, vy,
                 dt, cf, cn, w, nf, part_sl, (const int32_t*)sl_queue, (const int32_t*)sl_qcnt, ro);
     } else if (sl_rec_wave(n)) {
-      kl_lds = 0;
       klaunch(4, 8.0 * 6 * (double)n, k_sl_rec_wave, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0, (int64_t)n, vx,
               vy, dt, cf, cn, w, nf, part_sl, ro);
     } else {
       klaunch(4, 8.0 * 6 * (double)n, k_sl<LocDev>, dim3(nb), dim3(BS), M, lgrid, (int64_t)row0, (int64_t)n, vx, vy,
               dt, cf, cn, w, nf, part_sl, sl_queue, sl_qcnt);
-      kl_lds = 0;
       klaunch(8, 0.0, k_sl_slow<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0, (int64_t)n, vx, vy, dt,
               cf, cn, w, nf, part_sl, (const int32_t*)sl_queue, (const int32_t*)sl_qcnt, ro);
     }
@@ -1342,8 +1258,6 @@ struct Ctx {
     }
     comm->group_end(st);
   }
-  // PUCFEM_VISC_SPEC=0 (measurement knob): no speculative finish ahead of the |r_0| round trip (see vcheb)
-  bool visc_spec = !(std::getenv("PUCFEM_VISC_SPEC") && std::atoi(std::getenv("PUCFEM_VISC_SPEC")) == 0);
   int vcheb(const DevSell& A, const HFace& hf, const double* val, dbl2* y, const dbl2* b, double tol, int maxit,
             int which, dbl2** out, const ViscFin* vfin = nullptr, bool* fin_done = nullptr) {
     constexpr int NR = 2;
@@ -1453,12 +1367,10 @@ struct Ctx {
                 dim3(nbs), dim3(BS), Ag.view(), fs, val, v1, c1a, c2a, first ? 1 : 0, (const int*)ctl,
                 first ? part_a : (double*)nullptr, first ? part_b : (double*)nullptr, RedOut{});
         KCHK();
-        if (first && dye_gate == 3) dye_tail_release();
         klaunch(12, bytes_f - (first ? 4.0 * NR * (double)hf.rows : 0.0), k_vcheb_pair, dim3(hf.items), dim3(BS), fc, p,
                 c1a, c2a, c1b, c2b, (const int*)ctl, pc, (int32_t)nbs, first ? 1 : 0,
                 first ? part_a : (double*)nullptr, first ? part_b : (double*)nullptr);
         KCHK();
-        if (first && dye_gate == 4) dye_tail_release();
         klaunch(-1, bytes_sk + fin_sk, k_vcheb<decltype(c16)::value>, dim3(nbs), dim3(BS), A.view(), fs, val, v2,
                 c1b, c2b, 0, (const int*)ctl, pc, (double*)nullptr, RedOut{});
         KCHK();
@@ -1539,7 +1451,7 @@ struct Ctx {
     // viscous() would launch it) goes ahead of the round trip, so the GPU works while the host waits; it stands
     // when the count is again at most two and is rewritten by the solve's real last step (or by viscous() from
     // x_0 when x_0 passes) otherwise
-    const bool spec_fin = pair0 && vfin && visc_spec && done == 2 && last_it[which] <= 2 && fin_done;
+    const bool spec_fin = pair0 && vfin && done == 2 && last_it[which] <= 2 && fin_done;
     if (spec_fin) {
       const i64 n = A.own();
       algo_bytes += 64.0 * (double)n;  // s, x_2, u read; u*, the fp32 increment written
@@ -1697,7 +1609,7 @@ struct Ctx {
     if constexpr (std::is_same<T, float>::value && std::is_same<TB, float>::value)
       // (one rank: the finest level only; pairs on L6 / L5 too measured neutral to -0.7 %, r10m)
       pairs = mg_pair && hf.items > 0 && hf.d.n <= VP_HALO &&
-              (dist() ? dg : (int)(&mg.back() - &L) < mg_pair_levels);
+              (dist() ? dg : &L == &mg.back());
     if (pairs && !mgp_x) {  // (sized for the finest level: every pair level uses them in turn)
       mgp_x = dalloc<float>(mg.back().nloc);
       mgp_d = dalloc<float>(mg.back().nloc);
@@ -1838,18 +1750,13 @@ struct Ctx {
     const HFace& hf = finest ? fP : L.hA;
     T* xa = B.x;
     T* xb = B.x2;
-    if (l == mg_dense_l) {
+    if (l == 0) {
       if constexpr (std::is_same<T, TB>::value) {
         // coarse solve: dense pseudo-inverse (replicated on every rank of a multi-rank run)
         const i64 N0 = (i64)L.ord.new2old.size();
         const dim3 g((unsigned)std::min<i64>(4096, (N0 + 3) / 4));
-        if (std::is_same<T, float>::value && dAinv32) {
-          algo_bytes += 4.0 * (double)N0 * (double)N0 + 2.0 * sizeof(T) * (double)N0;
-          hipLaunchKernelGGL((k_dense_mv<T, float>), g, dim3(BS), 0, st, N0, (const float*)dAinv32, b, xa, ctl);
-        } else {
-          algo_bytes += 8.0 * (double)N0 * (double)N0 + 2.0 * sizeof(T) * (double)N0;
-          hipLaunchKernelGGL(k_dense_mv<T>, g, dim3(BS), 0, st, N0, (const double*)dAinv, b, xa, ctl);
-        }
+        algo_bytes += 8.0 * (double)N0 * (double)N0 + 2.0 * sizeof(T) * (double)N0;
+        hipLaunchKernelGGL(k_dense_mv<T>, g, dim3(BS), 0, st, N0, (const double*)dAinv, b, xa, ctl);
         KCHK();
         return xa;
       } else {
@@ -1963,9 +1870,6 @@ struct Ctx {
     std::fprintf(stderr, "[pcg] solve %ld (slot %d) it %d |r|/|b| %.3e <r,z> %.3e ctl %d/%d\n", n_pcg_traced, which, it,
                  std::sqrt(h[0] / h[1]), h[2], cc[0], cc[1]);
   }
-  // PUCFEM_PROJ_SPMV=1 (diagnostic knob): the projection update's A v by an SpMV of v = y - x0 instead of the
-  // CG's residuals r0 - r_final (no pending directions)
-  bool proj_spmv = std::getenv("PUCFEM_PROJ_SPMV") && std::atoi(std::getenv("PUCFEM_PROJ_SPMV")) != 0;
   // the PCG's initial <r, r> and <b, b> beside the control word (k_conv / k_reduce_conv write them at iteration
   // 0; pcg_mg's control reads bring them along): the projected guess's quality, h_note() after a solve
   double* ctl_note() const { return reinterpret_cast<double*>(ctl + 2); }
@@ -2004,7 +1908,7 @@ struct Ctx {
     guess_n[slot] = 0;
     ++n_restart;
   }
-  bool proj_shared = false;  // prm.proj_shared (PUCFEM_PROJ_SHARED=0/1 overrides it: a measurement knob)
+  bool proj_shared = false;  // prm.proj_shared
   int proj_slot(int which) const { return proj_shared && which == 2 ? 1 : which; }
   int pcg_mg(double* y, const double* b, double tol, int maxit, int which) {
     const FaceDev fc = fP.part();
@@ -2141,7 +2045,6 @@ struct Ctx {
           if (pcg_trace) trace_pcg(which, it + 1);
           continue;
         }
-        if (dye_gate == 1 && which == 1) dye_tail_release();
         ro_rz = ro(redbuf + 32, CNT_RZ, 1);
         precondition();
         ro_rz = RedOut{};
@@ -2228,14 +2131,10 @@ struct Ctx {
   }
   // halo of the interleaved velocity u / u* (component pointers)
   void halo_v(double* vx) { halo2(reinterpret_cast<dbl2*>(vx)); }
-  // PUCFEM_VISC_FUSE_FIN=0 (measurement knob): k_visc_fin as its own launch after the solve
-  bool visc_fuse_fin = !(std::getenv("PUCFEM_VISC_FUSE_FIN") && std::atoi(std::getenv("PUCFEM_VISC_FUSE_FIN")) == 0);
-  bool dense_bc = !(std::getenv("PUCFEM_DENSE_BC") && std::atoi(std::getenv("PUCFEM_DENSE_BC")) == 0);
   int viscous(int& iters) {  // StokesColor.py:540-547
     const i64 n = lp.n_own;
     if (dense) {  // u* = A_visc^-1 (u + DT * 0)
-      // (PUCFEM_DENSE_BC=0, measurement knob: the BCs in their own launch)
-      if (dbcsrc && dense_bc && dir_ncomp == 2) {  // (velocity BCs: both components copied / set)
+      if (dbcsrc && dir_ncomp == 2) {  // (velocity BCs: both components copied / set)
         hipLaunchKernelGGL(k_dense_mv2_bc, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, ux,
                            uy, usx, usy, (const int32_t*)dbcsrc, (const int32_t*)dbcdir, (const double*)ddval,
                            dir_ncomp);
@@ -2279,7 +2178,7 @@ struct Ctx {
     bool fin_done = false;
     if (cheb) {
       ViscFin vf{};
-      const bool fuse = ext && visc_fuse_fin;
+      const bool fuse = ext;
       if (fuse) vf = ViscFin{dsv, {ux, uy}, {usx, usy}, {dvinc[last], dvinc[last + 1]}};
       dbl2* yo = vx2[0];  // the converged iterate (one of the solve's buffers)
       iters = vcheb(dP, fVisc, dKv, vx2[0], vb2, prm.rtol_visc, prm.maxit_visc, 0, &yo, fuse ? &vf : nullptr,
@@ -2345,7 +2244,6 @@ struct Ctx {
   // PUCFEM_RHS_FUSE=0 (measurement knob): the pressure right-hand side always in its own pass (k_pres_rhs)
   bool rhs_fuse = !(std::getenv("PUCFEM_RHS_FUSE") && std::atoi(std::getenv("PUCFEM_RHS_FUSE")) == 0);
   int pressure(double* yst, double* pout, int which, bool sb_fused = false) {  // StokesColor.py:554-555 (restated)
-    if (dye_gate >= 2 && which == 1) dye_tail_release();  // (gates 3 / 4 when the viscous solve ran no pair)
     const int nb = div_grid();
     Red sb{redbuf + 24, 1, 1};
     if (!sb_fused) sb = reduce_global(part_d + MAXB, nb, 1, false, 3);
@@ -2372,7 +2270,7 @@ struct Ctx {
     if (!prm.warm_start) HIPCHK(hipMemsetAsync(yst, 0, sizeof(double) * nloc, st));
     const RhsIn rin{braw, dslave_of, sb.p, 1.0 / (double)n_free, bh};
     const bool projected = proj && project_guess(proj_slot(which), bh, yst, rhs_in_mdot ? &rin : nullptr);
-    const bool acc = projected && !proj_spmv;  // the CG accumulates v (k_pcomb cleared pv)
+    const bool acc = projected;  // the CG accumulates v (k_pcomb cleared pv)
     int it;
     if (dense) {
       hipLaunchKernelGGL(k_dense_mv<double>, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dPinv, bh, yst,
@@ -2390,9 +2288,7 @@ struct Ctx {
         const int slot = proj_slot(which);
         pend_acc[slot] = acc;
         pend_vzero[slot] = acc && it == 0;
-        if (proj_spmv) {
-          project_update(slot, yst);  // A v by an SpMV of the stored v
-        } else if (p_from_y && proj_m[slot] > 0) {  // the direction stays pending (the next solve forms it)
+        if (p_from_y && proj_m[slot] > 0) {  // the direction stays pending (the next solve forms it)
           pend_otf[slot] = true;
           pend_y[slot] = yst;
           proj_pend[slot] = true;
@@ -2410,7 +2306,7 @@ struct Ctx {
       halo(yst);
       return it;
     }
-    if (!(use_mg && proj) || proj_spmv) {
+    if (!(use_mg && proj)) {
       algo_bytes += (20.0 + (sc ? 8.0 : 0.0)) * (double)n;  // master_of, y (, s) read; p written
       hipLaunchKernelGGL(k_cg_fin, dim3(grid_ew(n)), dim3(BS), 0, st, n, 1, sc, yst, (const double*)nullptr, pout,
                          (double*)nullptr, dmaster_of);
@@ -2444,16 +2340,6 @@ struct Ctx {
     }
     const int nb = grid_ew(n);
     const RedOut rmd = ro(proj_d, CNT_MDOT, 2 * m + 4);
-    // virtual blocks: nb blocks' rows and partials on a grid the chip holds at once (not with the fused reduction)
-    int nbp = nb, nvb = 0;
-    if (!rmd.out) {
-      const int res = fit_grid((const void*)mdot2_kernel(m), nb);
-      if (res < nb) {
-        const int per = (nb + res - 1) / res;
-        nbp = (nb + per - 1) / per;
-        nvb = nb;
-      }
-    }
     // k_mdot2: X (fp32), b, A v, v read
     const bool otf = pend_otf[which];
     // a pending direction: A v from the residuals; v accumulated (pend_acc) or y - x0 (the first direction)
@@ -2467,9 +2353,9 @@ struct Ctx {
     klaunch(14,
             (4.0 * m + 24.0 + (otf ? 8.0 : 0.0) + (vdiff ? 8.0 : 0.0) - (vz0 ? 8.0 : 0.0) + (rin ? 12.0 : 0.0)) *
                 (double)n,
-            mdot2_kernel(m), dim3(nbp), dim3(BS), (int64_t)n,
+            mdot2_kernel(m), dim3(nb), dim3(BS), (int64_t)n,
             (const ProjT*)projX[which], (int64_t)pld(which), b, (const double*)pav[which], vp,
-            op.null_free, proj_part, rmd, pd, rin ? *rin : RhsIn{}, nvb);
+            op.null_free, proj_part, rmd, pd, rin ? *rin : RhsIn{});
     if (!rmd.out) launch_reduce(proj_part, nb, MAXB, 2 * m + 4, false, proj_d);
     KCHK();
     if (dist()) comm->allreduce(proj_d, 2 * m + 4, false, st);
@@ -2483,7 +2369,7 @@ struct Ctx {
     HIPCHK(hipMemcpyAsync(h_coef + which * NCOEF, proj_coef, sizeof(double) * NCOEF, hipMemcpyDeviceToHost, st));
     // k_pcomb: X, v read; the new direction, y and x0 written (not x0 when the coming solve accumulates its
     // correction: the first update starts the accumulator, so it needs no clearing either)
-    const bool acc_next = which <= 2 && !proj_spmv;
+    const bool acc_next = which <= 2;
     klaunch(15, (4.0 * kq + (acc_next ? 24.0 : 32.0) + (vdiff ? 8.0 : 0.0) - (vz0 ? 8.0 : 0.0)) * (double)n,
             pcomb_kernel(kq), dim3(nb), dim3(BS), (int64_t)n,
             (const ProjT*)projX[which], (int64_t)pld(which), (const double*)proj_coef, vp,
@@ -2650,7 +2536,7 @@ struct Ctx {
     KCHK();
   }
   // The gradient projection after a pressure solve, enqueued behind the solve's convergence reads and gated on its
-  // control word (PUCFEM_GP_GATE, default on): when the read finds the solve converged the GPU has been running the
+  // control word: when the read finds the solve converged the GPU has been running the
   // projection during the host's round trip (the r13g trace: ~50 us idle before each k_grad_proj), and when it finds
   // it not converged the launch did nothing and the next read enqueues it again.  Single rank, multigrid path with
   // p kept in y (nothing is launched between the solve's last read and the projection there).
@@ -2681,7 +2567,6 @@ struct Ctx {
     gp_gate = GpGate{};
     return d;
   }
-  bool gp_gate_env = !(std::getenv("PUCFEM_GP_GATE") && std::atoi(std::getenv("PUCFEM_GP_GATE")) == 0);
   // the PCG's control-word read (h_ctl), with the gated projection behind it
   // arm: enqueue the gated projection behind this read (pcg_mg: when the solve has reached the last solve's count, so
   // that a read unlikely to find it converged adds no launch that does nothing)
@@ -2715,8 +2600,6 @@ struct Ctx {
 
   // side stream of the overlapped dye advection (stokes_step)
   hipStream_t st_sl = nullptr;
-  int sl_prio = 0;  // (PUCFEM_STREAM_PRIO: the side stream's priority)
-  bool sl_prio_on = false;
   hipEvent_t ev_u = nullptr, ev_sl = nullptr;
   bool sl_overlap = true, sl_pending = false;
   double* part_mx = nullptr;  // k_mix2 partials (part_b belongs to the solvers of the main stream)
@@ -2728,7 +2611,6 @@ struct Ctx {
   };
   // order the main stream after the pending dye advection
   void sl_join() {
-    dye_tail_release();
     if (!sl_pending) return;
     HIPCHK(hipStreamWaitEvent(st, ev_sl, 0));
     sl_pending = false;
@@ -2743,13 +2625,6 @@ struct Ctx {
   // (round 4 measured the tail released after the next step's first viscous step and after its viscous
   // solve: neutral, r10f; it is released at the end of the step)
   hipEvent_t ev_gate = nullptr;
-  // PUCFEM_DYE_GATE (measurement knob): where the semi-Lagrangian part of the tail (advection, mixing sums, the
-  // record) is released -- 0 with the final-divergence record at the end of the step (default), 1 at the first
-  // V-cycle of the next step's first pressure solve (beside its latency-bound coarse levels), 2 at the start of that
-  // pressure solve, 3 / 4 after the first SELL launch / the face kernel of the next viscous solve's first pair
-  int dye_gate = std::getenv("PUCFEM_DYE_GATE") ? std::atoi(std::getenv("PUCFEM_DYE_GATE")) : 0;
-  bool slb_pend = false;     // the semi-Lagrangian part waits for its release (dye_gate > 0)
-  double* slb_rec = nullptr;
   struct SmallRed {  // (reset on unwind)
     bool& f;
     explicit SmallRed(bool& x) : f(x) { f = true; }
@@ -2761,29 +2636,16 @@ struct Ctx {
     {
       StreamSwap sw(st, st_sl);
       SmallRed small_red(red_small);
-      if (dye_gate == 0 && dye_sl_first) dye_tail_sl(rec, false);
       const RedOut rf = ro(vals + 1, CNT_DYE_DIV, 1, MAXB, 1u);
       div(ux, uy, nullptr, false, part_fd, rf);  // (the final div field is computed when read)
       if (!rf.out) reduce_into(part_fd, div_grid(), 1, true, 1);  // max |final div|
-      if (dye_gate == 0 && !dye_sl_first) dye_tail_sl(rec);
-      if (dye_gate == 0 && dye_sl_first) {
-        hipLaunchKernelGGL(k_stats, dim3(1), dim3(64), 0, st, vals, rec, 6);
-        KCHK();
-      }
+      dye_tail_sl(rec);
     }
-    if (dye_gate == 0) {
-      HIPCHK(hipEventRecord(ev_sl, st_sl));
-      sl_pending = true;
-    } else {
-      slb_pend = true;
-      slb_rec = rec;
-    }
+    HIPCHK(hipEventRecord(ev_sl, st_sl));
+    sl_pending = true;
   }
-  // PUCFEM_DYE_SL_FIRST=1 (measurement knob): the tail's semi-Lagrangian part before its final-divergence record
-  bool dye_sl_first = std::getenv("PUCFEM_DYE_SL_FIRST") && std::atoi(std::getenv("PUCFEM_DYE_SL_FIRST")) != 0;
-  // the semi-Lagrangian part of the tail (launched on st_sl: the caller swapped the streams); stats: the step
-  // record after it (else the caller writes it)
-  void dye_tail_sl(double* rec, bool stats = true) {
+  // the semi-Lagrangian part of the tail (launched on st_sl: the caller swapped the streams) and the step record
+  void dye_tail_sl(double* rec) {
     const int nb = nb_sl(lp.n_own);
     const RedOut rs = ro(vals + 2, CNT_DYE_SL, 3, SLB);
     sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
@@ -2797,23 +2659,8 @@ struct Ctx {
                        part_mx, rm);
     KCHK();
     if (!rm.out) reduce_into(part_mx, nbm, 1, false, 5);
-    if (!stats) return;
     hipLaunchKernelGGL(k_stats, dim3(1), dim3(64), 0, st, vals, rec, 6);
     KCHK();
-  }
-  // release a deferred semi-Lagrangian part (dye_gate > 0): behind the main stream's work so far
-  void dye_tail_release() {
-    if (!slb_pend) return;
-    slb_pend = false;
-    HIPCHK(hipEventRecord(ev_gate, st));
-    HIPCHK(hipStreamWaitEvent(st_sl, ev_gate, 0));
-    {
-      StreamSwap sw(st, st_sl);
-      SmallRed small_red(red_small);
-      dye_tail_sl(slb_rec);
-    }
-    HIPCHK(hipEventRecord(ev_sl, st_sl));
-    sl_pending = true;
   }
   // W > 1, StokesColor: the second half of a step's dye tail (dye_range_start queued the first at its end): the
   // wide halo, the semi-Lagrangian advection of the owned rows, the mixing sums and the rest of the step record.
@@ -2853,12 +2700,12 @@ struct Ctx {
     // step reads it, and its 8 B/row store is a quarter of the kernel's bytes
     const bool f1 = div_rhs(usx, usy, nullptr, vals);
     if (!f1) reduce_into(part_d, div_grid(), 1, true, 0);
-    const bool gpg = gp_gate_env && use_mg && proj_k > 0 && p_from_y && !dist() && !proj_spmv;
+    const bool gpg = use_mg && proj_k > 0 && p_from_y && !dist();
     // (a solve that throws leaves no gated projection armed for later calls: gated_pressure resets it on unwind)
     const int itp = gated_pressure(GpGate{gpg, false, yp, 0, 0.0}, yp, p, 1, f1);
     const bool gp1 = gp_gate_end();
     sl_join();  // the previous step's dye advection still reads u: it must finish before u is rewritten
-    if (dense && dspos && dense_bc && dir_ncomp == 2 && !gp1 && (p_from_y ? fP : fK).rows == 0) {
+    if (dense && dspos && dir_ncomp == 2 && !gp1 && (p_from_y ? fP : fK).rows == 0) {
       grad_proj_bc(p_from_y ? yp : p);  // (the BCs inside the projection: small meshes)
     } else {
       if (!gp1) grad_proj(p_from_y ? yp : p, 0);
@@ -2877,21 +2724,9 @@ struct Ctx {
     const bool ovl = sl_overlap && scheme == PUCFEM_STOKES_COLOR && !dye_impl && !graph_mode && !dist();
     if (!ovl) {
       const RedOut r = ro(vals + 1, CNT_DIV, 1, MAXB, 1u);
-      // captured small-mesh step (fused reductions): the final-divergence record on a forked branch of the graph, beside
-      // the semi-Lagrangian advection (both read u and write their own partials); joined before the step record
-      const bool fork = gcapture && r.out && !dye_impl && st_fk != nullptr && scheme == PUCFEM_STOKES_COLOR;
-      if (fork) {
-        HIPCHK(hipEventRecord(ev_fk, st));
-        HIPCHK(hipStreamWaitEvent(st_fk, ev_fk, 0));
-        {
-          StreamSwap sw(st, st_fk);
-          div(ux, uy, nullptr, false, nullptr, r);
-        }
-        HIPCHK(hipEventRecord(ev_fj, st_fk));
-        fork_pend = true;
-      } else {
-        div(ux, uy, dye_impl ? final_div : nullptr, false, nullptr, r);  // (the implicit dye reads it)
-      }
+      // (a captured small-mesh step with this record on a forked branch of the graph gave the same bits and ran
+      // 10.0k steps/s against 12.5k in one chain, r14q)
+      div(ux, uy, dye_impl ? final_div : nullptr, false, nullptr, r);  // (the implicit dye reads it)
       if (r.out) red_done(vals + 1, 1, true);
       else reduce_into(part_d, div_grid(), 1, true, 1);  // max |final div|
     }
@@ -2899,22 +2734,7 @@ struct Ctx {
       if (!st_sl) {
         // (stream priorities and CU masks for the side stream were measured and changed nothing or lost,
         // rounds 2-3: r4d, r6c)
-        // PUCFEM_SL_CUMASK=k (measurement knob, 1..7): the side stream on k of every 8 CUs (mask bits i with
-        // i % 8 < k), the rest left to the main stream's small launches
-        const int cuk = std::getenv("PUCFEM_SL_CUMASK") ? std::atoi(std::getenv("PUCFEM_SL_CUMASK")) : 0;
-        if (cuk > 0 && cuk < 8) {
-          int d = 0, ncu = 0;
-          HIPCHK(hipGetDevice(&d));
-          HIPCHK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, d));
-          std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-          for (int i = 0; i < ncu; ++i)
-            if (i % 8 < cuk) mask[(size_t)i / 32] |= 1u << (i % 32);
-          HIPCHK(hipExtStreamCreateWithCUMask(&st_sl, (uint32_t)mask.size(), mask.data()));
-        } else if (sl_prio_on) {
-          HIPCHK(hipStreamCreateWithPriority(&st_sl, hipStreamNonBlocking, sl_prio));
-        } else {
-          HIPCHK(hipStreamCreateWithFlags(&st_sl, hipStreamNonBlocking));
-        }
+        HIPCHK(hipStreamCreateWithFlags(&st_sl, hipStreamNonBlocking));
         HIPCHK(hipEventCreateWithFlags(&ev_u, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ev_sl, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ev_gate, hipEventDisableTiming));
@@ -2956,10 +2776,9 @@ struct Ctx {
       sl_ro = RedOut{};
       const int nbm = nb_rows(lp.n_own);
       algo_bytes += 16.0 * (double)lp.n_own;
-      fork_join();  // (k_mix2's reducing block writes the step record, which holds the final divergence)
       const RedOut rm = ro(vals + 5, CNT_MIX, 1);
       // (captured small-mesh step with the fused reduction: k_mix2's reducing block appends the step record)
-      ring_in_mix = gcapture && rm.out && !ovl && ring_fold;
+      ring_in_mix = gcapture && rm.out && !ovl;
       hipLaunchKernelGGL(k_mix2, dim3(nbm), dim3(BS), 0, st, lp.r0, lp.n_own, mix_copy ? (const double*)c_new : c_full,
                          dwmix, vals + 2, 1, 1, part_mx, rm, mix_copy ? c_full : (double*)nullptr, (const double*)vals,
                          ring_in_mix ? gring : (double*)nullptr, ring_in_mix ? gcount : (int*)nullptr, 7);
@@ -2969,7 +2788,6 @@ struct Ctx {
     } else {
       tracer_advance(prm.dt);
     }
-    fork_join();
     if (!ovl) {
       if (gcapture) {
         if (!ring_in_mix) hipLaunchKernelGGL(k_stats_ring, dim3(1), dim3(64), 0, st, vals, gring, gcount, 7);
@@ -3389,13 +3207,6 @@ void build_mg_host(Ctx& c, SetupClock& clk) {  // (after mg_refine)
     L.P = Csr();  // only the merged operator is needed on coarse levels
   }
   clk.mark("  mg: coarse level operators");
-  // the level of the dense coarse solve; level 1's inverse (~3.6k rows: ~1.5 s of host work) runs beside the rest of
-  // setup from here
-  c.mg_dense_l = 0;
-  if (const char* e = std::getenv("PUCFEM_MG_DENSE_LEVEL"))
-    c.mg_dense_l = std::max(0, std::min(std::min(1, Lv - 1), std::atoi(e)));
-  if (c.mg_dense_l > 0)
-    c.dense_fut = std::async(std::launch::async, [&c] { return dense_coarse_inverse(c.mg[c.mg_dense_l]); });
   MgLevel& F = c.mg[Lv];
   F.ord = c.ord;
   if (c.lattice) F.latl = std::move(c.lat_fine);
@@ -3405,8 +3216,7 @@ void build_mg_host(Ctx& c, SetupClock& clk) {  // (after mg_refine)
   // parallel inside) read only what the level operators above produced: they run concurrently
   // the finest level's power iteration runs on the device at the end of build() (every rank its strip:
   // halos before the products, the two norms all-reduced)
-  // PUCFEM_LMAX_HOST=1 (measurement knob): every level's power iteration on the host's fp64 operator
-  c.lmax_dev = !c.host_only && !(std::getenv("PUCFEM_LMAX_HOST") && std::atoi(std::getenv("PUCFEM_LMAX_HOST")));
+  c.lmax_dev = !c.host_only;
   {
     ThreadGroup g;  // joined on every exit path; a level's exception reaches the caller from join()
     for (int l = 1; l <= Lv; ++l)
@@ -4267,12 +4077,7 @@ void build(Ctx& c) {
     }
     clk.mark("  dev: lattice face tables");
     // coarse solve: dense pseudo-inverse of the merged operator, constants regularised on the free dofs
-    {
-      const std::vector<double> D =
-          c.dense_fut.valid() ? c.dense_fut.get() : dense_coarse_inverse(c.mg[c.mg_dense_l]);
-      c.dAinv = c.upload(D);
-      if (c.mg_dense_l > 0) c.dAinv32 = c.upload(std::vector<float>(D.begin(), D.end()));
-    }
+    c.dAinv = c.upload(dense_coarse_inverse(c.mg[0]));
   }
   if (c.dist() && c.use_mg) {  // deep-halo flags: every rank takes the same exchanges (a flag off anywhere is off)
     const size_t nl = c.mg.size();
@@ -4311,11 +4116,10 @@ void build(Ctx& c) {
   auto proj_size = [](int k) { return k <= 0 ? 0 : std::max(3, std::min(k, (int)PROJ_MAX)); };
   c.proj_k = c.use_mg && !c.dense ? proj_size(c.prm.proj_k) : 0;
   c.proj_shared = c.prm.proj_shared != 0;
-  if (const char* e = std::getenv("PUCFEM_PROJ_SHARED")) c.proj_shared = std::atoi(e) != 0;
   // pending pressure directions and the gradient on y (Ctx::p_from_y): lattice operators, the multigrid PCG
   // with the projection, the explicit dye; PUCFEM_P_FROM_Y=0 keeps the stored form (a measurement knob: the
   // same values either way).  Partitioned runs exchange y's halo instead of p's.
-  c.p_from_y = stokes && c.lattice && c.use_mg && c.proj_k > 0 && !c.dye_impl && c.dP.c16 == nullptr && !c.proj_spmv &&
+  c.p_from_y = stokes && c.lattice && c.use_mg && c.proj_k > 0 && !c.dye_impl && c.dP.c16 == nullptr &&
                !(std::getenv("PUCFEM_P_FROM_Y") && std::atoi(std::getenv("PUCFEM_P_FROM_Y")) == 0);
   if (c.p_from_y) {  // dP with every column mapped to its periodic master (the dof map), in local ids
     std::vector<i32> colm(c.sP.col.size());
@@ -4354,11 +4158,10 @@ void build(Ctx& c) {
   }
   const bool block_visc = !c.dist() && c.block_cg && no <= (i64)CGB_THREADS * CGB_MAXR;
   c.proj_k_visc = stokes && !c.dense && !block_visc ? proj_size(c.prm.proj_k_visc) : 0;
-  c.ldx = (c.nloc + 1) & ~(i64)1;
   for (int w = 1; w <= 4; ++w) {
     const int k = w <= 2 ? c.proj_k : c.proj_k_visc;
     if (k > 0) {
-      const i64 pn = PUCFEM_PROJ_TILED ? (c.nloc + 63) / 64 * 64 * k : (i64)k * c.ldx;
+      const i64 pn = (c.nloc + 63) / 64 * 64 * k;
       c.projX[w] = c.dalloc<ProjT>(pn);
       c.proj_x0[w] = c.dalloc<double>(c.nloc);
       c.projXalt[w] = c.dalloc<ProjT>(pn);  // re-seeding target
@@ -4722,20 +4525,9 @@ int pucfem_ctx_create(int32_t device, void** out) {
     auto c = std::make_unique<Ctx>();
     c->device = device;
     c->host_only = device < 0;
-    if (const char* e = std::getenv("PUCFEM_MG_BLOCKS")) c->mg_nb_max = std::max(1, std::atoi(e));  // tuning knob
     if (!c->host_only) {
       HIPCHK(hipSetDevice(device));
-      // PUCFEM_STREAM_PRIO=1 (measurement knob): the main stream at the highest priority, the dye side stream at the
-      // lowest (the dispatcher then hands freed slots to the main stream's blocks first)
-      if (std::getenv("PUCFEM_STREAM_PRIO") && std::atoi(std::getenv("PUCFEM_STREAM_PRIO")) != 0) {
-        int lo = 0, hi = 0;
-        HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(hipStreamCreateWithPriority(&c->st, hipStreamNonBlocking, hi));
-        c->sl_prio = lo;
-        c->sl_prio_on = true;
-      } else {
-        HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
-      }
+      HIPCHK(hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking));
       HIPCHK(hipHostMalloc((void**)&c->h_ctl, 8 * sizeof(int), hipHostMallocDefault));
       HIPCHK(hipHostMalloc((void**)&c->h_coef, 5 * Ctx::NCOEF * sizeof(double), hipHostMallocDefault));
       HIPCHK(hipHostMalloc((void**)&c->h_pinned, 64 * sizeof(double), hipHostMallocDefault));
@@ -5080,7 +4872,6 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
             c.gcapture = false;
           } catch (...) {
             c.gcapture = false;
-            c.fork_pend = false;
             hipGraph_t g;
             (void)hipStreamEndCapture(c.st, &g);
             c.graph_mode = c.gexec != nullptr;
@@ -5090,7 +4881,6 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
           HIPCHK(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
         };
         c.prep_grad_proj_bc();
-        c.prep_fork();
         if (!c.gexec) {
           c.gstats = c.dalloc<double>(8);
           c.gring = c.dalloc<double>(8 * (i64)Ctx::GRING);
@@ -5133,7 +4923,6 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
           c.dits = nullptr;
           if (c.sl_pending) (void)hipStreamSynchronize(c.st_sl);
           c.sl_pending = false;
-          c.slb_pend = false;
           c.tail_pend = false;
           throw;
         }

@@ -738,27 +738,15 @@ constexpr int PROJ_MAX = 32;
 // relative residual is 1e-6 .. 1e-5 against the solve's rtol 1e-8), and rounding the A-orthonormal
 // directions to fp32 perturbs their A-inner products by ~1e-7, below that; the dots and the
 // combinations are formed in fp64.  Halves the two passes over the basis (2 m vector reads per solve).
-#ifdef PUCFEM_PROJ_F64
-using ProjT = double;  // (A/B variant: the basis in fp64)
-#else
 using ProjT = float;
-#endif
 typedef double dbl2 __attribute__((ext_vector_type(2)));
 typedef float flt2 __attribute__((ext_vector_type(2)));
 
-// Basis layout.  PUCFEM_PROJ_TILED (default): tiles of 64 rows, inside a tile each of the basis' kcap vectors holds
-// 64 consecutive values -- element (i, r) at ((r / 64) kcap + i) 64 + r % 64, ld = kcap: a wave's 64 rows of all
-// vectors are one contiguous block (one DRAM stream instead of one per vector), a new vector's 64 values one
-// 256-B segment.  0: column-major, (i, r) at i ld + r, ld = the vector stride
-#ifndef PUCFEM_PROJ_TILED
-#define PUCFEM_PROJ_TILED 1
-#endif
+// Basis layout: tiles of 64 rows, inside a tile each of the basis' kcap vectors holds 64 consecutive values --
+// element (i, r) at ((r / 64) kcap + i) 64 + r % 64, ld = kcap: a wave's 64 rows of all vectors are one contiguous
+// block (one DRAM stream instead of one per vector), a new vector's 64 values one 256-B segment
 __host__ __device__ __forceinline__ int64_t pxi(int i, int64_t r, int64_t ld) {
-#if PUCFEM_PROJ_TILED
   return (((r >> 6) * ld + i) << 6) + (r & 63);
-#else
-  return (int64_t)i * ld + r;
-#endif
 }
 // basis re-seeding: out_i = sum_j q[i][j] X_j (i < kq <= PROJ_KEEP_MAX, j < m), one pass over X.
 // Q: the re-seed coefficients in device memory, row-major [PROJ_KEEP_MAX][PROJ_MAX] (block-uniform loads)
@@ -820,25 +808,19 @@ struct PendDir {
   const double* rf;  // its final residual (null: A v was stored in av)
   const double* v;   // its accumulated correction (null: y - x0, or the stored v)
 };
-// Virtual blocks (nvb > 0): the rows and partials are those of a grid of nvb blocks (virtual block vb: rows
-// vb BS + t + k nvb BS, its partials at index vb), run by a smaller grid whose blocks take virtual blocks vb =
-// blockIdx.x, + gridDim.x, ... one after another -- the same sums in the same order, so the same bits, on a grid the
-// chip holds at once (at 96 VGPRs 1,280 of the 2,048 blocks are resident: the rest ran as a second, partial round)
 template <int M>
 __global__ __launch_bounds__(BS) void k_mdot2(int64_t n, const ProjT* __restrict__ X, int64_t ld,
                                               const double* __restrict__ b, const double* __restrict__ av,
                                               const double* __restrict__ v, const int32_t* __restrict__ master_of,
-                                              double* part, RedOut ro, PendDir D, RhsIn R = RhsIn{}, int nvb = 0) {
+                                              double* part, RedOut ro, PendDir D, RhsIn R = RhsIn{}) {
   constexpr int NA = 2 * M + 4;
   __shared__ double sh[NA][4];
   const double mean = R.braw ? R.sum[0] * R.inv_nfree : 0.0;
-  const int V = nvb > 0 ? nvb : (int)gridDim.x;
-  const int64_t step = (int64_t)V * BS;
-  for (int vb = blockIdx.x; vb < V; vb += gridDim.x) {
+  const int64_t step = (int64_t)gridDim.x * BS;
   double acc[NA];
 #pragma unroll
   for (int i = 0; i < NA; ++i) acc[i] = 0.0;
-  for (int64_t r = (int64_t)vb * BS + threadIdx.x; r < n; r += step) {
+  for (int64_t r = (int64_t)blockIdx.x * BS + threadIdx.x; r < n; r += step) {
     double br;
     if (R.braw) {  // (k_pres_rhs's row)
       if (master_of[r] >= 0) {
@@ -875,13 +857,7 @@ __global__ __launch_bounds__(BS) void k_mdot2(int64_t n, const ProjT* __restrict
     if ((threadIdx.x & 63) == 0) sh[i][threadIdx.x >> 6] = t;
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < NA; i += BS) {
-    const double t = (sh[i][0] + sh[i][1]) + (sh[i][2] + sh[i][3]);
-    if (nvb > 0) part[(int64_t)i * MAXB + vb] = t;  // (virtual blocks: the plain partials, no fused reduction)
-    else red_part(ro, part, i, t);
-  }
-  __syncthreads();  // (sh is reused by the next virtual block)
-  }
+  for (int i = threadIdx.x; i < NA; i += BS) red_part(ro, part, i, (sh[i][0] + sh[i][1]) + (sh[i][2] + sh[i][3]));
   red_finish(ro, part, sh[0], true);  // (several waves stored partials)
 }
 
@@ -1340,14 +1316,10 @@ __device__ __forceinline__ void pin_reg(float& x) { asm("" : "+v"(x)); }
 __device__ __forceinline__ void pin_reg(dbl2& x) { asm("" : "+v"(x.x), "+v"(x.y)); }
 template <typename T>
 __device__ __forceinline__ T pair_nbr(const T* lds, int32_t lw, const T* glob, int64_t g, bool in) {
-#ifdef PUCFEM_PAIR_SELECT_LOAD  // (A/B: the merged form)
-  return in ? lds[lw] : glob[g];
-#else
   T x = lds[lw];
   pin_reg(x);
   if (!in) x = glob[g];
   return x;
-#endif
 }
 constexpr int VP_W = BS * FACE_RPT + 2 * VP_HALO;
 constexpr int VP_WK = (VP_W + BS - 1) / BS;
