@@ -222,6 +222,42 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats);
    [3] steps taken since pucfem_ens_create */
 int pucfem_ens_info(void* ctx, int64_t* out4);
 
+/* ---- sampling and rasterising: fields at arbitrary points and as images, on the device --- */
+/* The reference reads a field at a point by locating the point's triangle and interpolating from its vertices
+   (StokesFood.py:482-487, the tracers' velocity), and its results are frames: the dye under a quiver of the
+   velocity (scripts/good_visualization2.py:536-571, a tripcolor of the whole mesh).  These calls do both from
+   caller-given points on the device with the context's point locator, so a probe, a line cut or a frame costs
+   its points, not a copy of the whole fields.
+   Semantics, for a query point q = (x, y) taken as given (no periodic wrap, no clamp): among the triangles that
+   pass the reference's weight test (|det| >= 1e-14 and all three weights >= 0, StokesColor.py:325-333) the one
+   with the smallest (squared centroid distance, triangle id); the value is the reference's interpolation on it
+   (StokesColor.py:374-386).  A point on a shared edge or vertex so has one answer.  PointLocator's restriction
+   to the 10 nearest centroids (StokesColor.py:324) is NOT applied: a sampler wants containment.  Where no
+   triangle passes (outside [0,1]^2, inside the swimmer, a non-finite q) the value is NaN and the triangle -1.
+   Fields: PUCFEM_F_U and _USTAR (2 components: x then y), _P, _P2, _DIV_STAR, _DIV_U, _FINAL_DIV, _C (1 each);
+   at most 16 components per call.  Single-rank STOKES_COLOR / STOKES_FOOD contexts after pucfem_build_operators,
+   else PUCFEM_ESTATE (heat / Poisson contexts have no locator; a multi-rank context's fields are partitioned);
+   PUCFEM_ENODEV on a host-only context; PUCFEM_EINVAL for another field, nfields < 1, a non-positive size, a
+   window without x0 < x1 and y0 < y1, or more than 2^31 - 1 pixels.  The calls run on the context's stream after
+   everything pending on it (after pucfem_step returns they see the last step's fields) and change no state of
+   the context or its ensemble; their device buffers are allocated at first use and kept. */
+/* out: fp64, field-major (component k of point e at out[k * npoints + e], components in the order of `fields`);
+   tri_out (or NULL): the triangle in the caller's numbering, -1 where none passes */
+int pucfem_sample_points(void* ctx, int32_t nfields, const int32_t* fields, int64_t npoints,
+                         const double* xy /* npoints x 2 */, double* out /* sum(ncomp) x npoints */,
+                         int32_t* tri_out /* npoints or NULL */);
+/* A width x height image of the window [x0, x1] x [y0, y1]: pixel (i, j) is the value at its centre
+   (x0 + (i + 0.5) (x1 - x0) / width, y0 + (j + 0.5) (y1 - y0) / height), row j = 0 the lowest y;
+   out: fp32, [component][height][width] (the fp64 value rounded to nearest) */
+int pucfem_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t width, int32_t height,
+                  const double* window4 /* x0 y0 x1 y1, NULL = 0 0 1 1 */, float* out);
+/* The same image of every member of the context's ensemble (README.md:43-45: the swimmers side by side), each
+   pixel located once for all members; fields PUCFEM_F_U, _USTAR, _P, _P2, _C; member = -1: all members,
+   out [member][component][height][width], else that member's [component][height][width].  PUCFEM_ESTATE without
+   an ensemble. */
+int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t member /* -1 = all */,
+                      int32_t width, int32_t height, const double* window4, float* out);
+
 /* ---- unit operations (reference-named shims and parity tests) --------------------- */
 int pucfem_apply(void* ctx, int32_t op, const double* x, double* y);
 /* op VISC: b,x are (N,2) (both velocity components, StokesColor.py:544-545);
@@ -289,6 +325,13 @@ int pucfem_bench_dir(void* ctx, int32_t variant, int32_t nblocks, int32_t iters,
    kernel + 16*F: F untimed launches of a coarse level's smoother follow every timed launch
    (ms_batch then includes them; ms_each still times the kernel's own launches) */
 int pucfem_bench_kernel(void* ctx, int32_t kernel, int32_t iters, double* ms_batch, double* ms_each, double* bytes);
+/* timing and pixel bookkeeping of pucfem_raster's kernel (tools/raster_bench.py; arguments as pucfem_raster,
+   the image stays on the device): out4[0] = ms per launch of `iters` back-to-back launches between two events
+   (after one untimed launch), [1] = pixels no triangle holds, [2] = pixels the lattice locator answers with the
+   inner test of the first macro face listed for the pixel (one lattice cell tested; the rest take its general
+   search; 0 with the record locator), [3] = bytes of the image */
+int pucfem_raster_probe(void* ctx, int32_t nfields, const int32_t* fields, int32_t width, int32_t height,
+                        const double* window4, int32_t iters, double* out4);
 /* sizes of the internal operators: out[0]=N, [1]=T, [2]=nnz(P), [3]=nnz(Pp), [4]=n_own,
    [5]=n_ghost, [6]=padded SELL entries (P), [7]=padded SELL entries (Pp), [8]=n_pairs, [9]=n_dirichlet,
    [10]=storage flags (bit 0: P has int16 columns, bit 1: Pp has int16 columns, bit 2: the finest

@@ -14,8 +14,9 @@ from .mesh import (Mesh, boundary_sets, filter_wall_pairs, find_boundary_pairs, 
 from .ops import (advect_semilagrange, buildLumpedMassMatrix, buildStiffnessMatrix, calculate_divergence,  # noqa: F401
                   build_mass_and_convection_mass, calculate_gradiant, dye_implicit_step, makeDirBCU, makePerBCU,
                   mixing_index, set_globals, solve_pressure, solve_viscous)
-from .solver import (Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble, StokesSimulation,  # noqa: F401
-                     Tolerances, ensemble_dirichlet_values, poisson_solve, solve, solve_ensemble, squirmer_values)
+from .solver import (SAMPLE_FIELDS, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
+                     StokesSimulation, Tolerances, ensemble_dirichlet_values, pixel_centres, poisson_solve, solve,
+                     solve_ensemble, squirmer_values)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401
 from .tracers import tracer_init  # noqa: F401
 

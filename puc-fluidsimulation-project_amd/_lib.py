@@ -81,6 +81,10 @@ SIGNATURES = {
     "pucfem_ens_get_field": ([_P, ct.c_int32, ct.c_int32, _D, ct.c_int64], ct.c_int),
     "pucfem_ens_step": ([_P, ct.c_int32, ct.POINTER(StepStats)], ct.c_int),
     "pucfem_ens_info": ([_P, _I64], ct.c_int),
+    "pucfem_sample_points": ([_P, ct.c_int32, _I32, ct.c_int64, _D, _D, _I32], ct.c_int),
+    "pucfem_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
+    "pucfem_ens_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
+    "pucfem_raster_probe": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _D], ct.c_int),
     "pucfem_apply": ([_P, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_solve": ([_P, ct.c_int32, _D, _D, ct.c_double, ct.c_int32, _I32], ct.c_int),
     "pucfem_sl_advect": ([_P, _D, _D, ct.c_double, _D, _I32], ct.c_int),

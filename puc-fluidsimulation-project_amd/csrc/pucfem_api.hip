@@ -27,6 +27,7 @@
 #include "pucfem_kernels.hpp"
 #include "pucfem_kernels_impl.hpp"
 #include "pucfem_ensemble.hpp"
+#include "pucfem_sample.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -544,6 +545,28 @@ struct Ctx {
   int32_t* sl_qcnt = nullptr; // per wave of k_sl: queued entries (SLB * BS / 64)
   int32_t* sl_qoff = nullptr; // k_sl_qscan: the queues' first entry numbers (SLB * BS / 64 + 1)
   bool has_cgrid = false, has_tgrid = false;
+  // pucfem_sample_points / pucfem_raster / pucfem_ens_raster (pucfem_sample.hpp): device buffers allocated at a
+  // call's first need and kept (grown when a later call needs more).  Slot 0 the points, 1 the output, 2 the
+  // triangle ids, 3 the probe's counters, 4.. the fields that are formed when read (p / p2 kept in y, div u*,
+  // the final divergence): the samplers form them here and write no field of the context
+  static constexpr int SMP_SLOTS = 8;
+  void* smp_buf[SMP_SLOTS] = {};
+  size_t smp_cap[SMP_SLOTS] = {};
+  template <class T>
+  T* smp_scratch(int slot, size_t count) {
+    const size_t bytes = sizeof(T) * std::max<size_t>(1, count);
+    if (smp_cap[slot] < bytes) {
+      if (smp_buf[slot]) {
+        HIPCHK(hipStreamSynchronize(st));
+        (void)hipFree(smp_buf[slot]);
+        smp_buf[slot] = nullptr;
+        smp_cap[slot] = 0;
+      }
+      HIPCHK(hipMalloc(&smp_buf[slot], bytes));
+      smp_cap[slot] = bytes;
+    }
+    return static_cast<T*>(smp_buf[slot]);
+  }
   double *c_full = nullptr, *c_new = nullptr, *ufx = nullptr, *ufy = nullptr;
   int32_t* dnotfound = nullptr;
   int32_t ntr = 0;
@@ -735,6 +758,8 @@ struct Ctx {
       if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
       if (graph_k) (void)hipGraphDestroy(graph_k);
       for (void* a : allocs) (void)hipFree(a);
+      for (void* a : smp_buf)
+        if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
       if (h_coef) (void)hipHostFree(h_coef);
       if (h_pinned) (void)hipHostFree(h_pinned);
@@ -5332,6 +5357,219 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
         o.sl_notfound = (int32_t)std::llround(r[6]);
         o.it_visc = o.it_p = o.it_p2 = 0;
       }
+  });
+}
+
+// ---- sampling and rasterising (pucfem_sample.hpp)
+namespace {
+// a context the samplers can read: a device, built, a Stokes scheme (the others have no locator), one rank
+void sample_ready(Ctx& c) {
+  c.need_dev();
+  c.need_built();
+  auto state = [](bool ok, const char* msg) {
+    if (!ok) throw Error(PUCFEM_ESTATE, msg);
+  };
+  state(c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD,
+        "sampling needs a Stokes context (heat / Poisson contexts have no point locator)");
+  state(!c.dist(), "sampling is single-rank (the fields of a multi-rank context are partitioned)");
+  state(c.lat_sl ? c.llgrid.face != nullptr : c.lgrid.rec != nullptr, "the context has no point locator");
+}
+void sample_push(SampleFields& F, const double* p, int32_t stride, int64_t member) {
+  require(F.ncomp < SMP_MAXC, "too many field components in one call (16)");
+  F.ptr[F.ncomp] = p;
+  F.stride[F.ncomp] = stride;
+  F.member[F.ncomp] = member;
+  ++F.ncomp;
+}
+// the components of the requested context fields, in output order.  Fields that pucfem_get_field forms when read
+// are formed here too, on the context's stream, into the samplers' own buffers.
+SampleFields sample_fields(Ctx& c, int32_t nfields, const int32_t* fields) {
+  require(nfields >= 1 && fields != nullptr, "nfields < 1");
+  SampleFields F{};
+  const i64 n = c.lp.n_own;
+  for (int32_t k = 0; k < nfields; ++k) {
+    switch (fields[k]) {
+      case PUCFEM_F_U:
+        sample_push(F, c.ux, VS, 0);
+        sample_push(F, c.uy, VS, 0);
+        break;
+      case PUCFEM_F_USTAR:
+        sample_push(F, c.usx, VS, 0);
+        sample_push(F, c.usy, VS, 0);
+        break;
+      case PUCFEM_F_P:
+      case PUCFEM_F_P2: {
+        const bool first = fields[k] == PUCFEM_F_P;
+        const double* pf = first ? c.p : c.p2;
+        if (c.p_from_y) {  // (p kept in y, the slaves not copied: pucfem_get_field's pass, into a buffer of ours)
+          double* s = c.smp_scratch<double>(first ? 4 : 5, (size_t)c.nloc);
+          hipLaunchKernelGGL(k_cg_fin, dim3(Ctx::grid_ew(n)), dim3(BS), 0, c.st, n, 1, (const double*)nullptr,
+                             (const double*)(first ? c.yp : c.yp2), (const double*)nullptr, s, (double*)nullptr,
+                             (const int32_t*)c.dmaster_of);
+          KCHK();
+          pf = s;
+        }
+        sample_push(F, pf, 1, 0);
+        break;
+      }
+      case PUCFEM_F_DIV_STAR: {  // from u*, as pucfem_get_field computes it
+        double* s = c.smp_scratch<double>(6, (size_t)c.nloc);
+        c.div(c.usx, c.usy, s, false);
+        sample_push(F, s, 1, 0);
+        break;
+      }
+      case PUCFEM_F_DIV_U: sample_push(F, c.div_u, 1, 0); break;
+      case PUCFEM_F_FINAL_DIV:
+        if (c.dye_impl) {
+          sample_push(F, c.final_div, 1, 0);
+        } else {
+          double* s = c.smp_scratch<double>(7, (size_t)c.nloc);
+          c.div(c.ux, c.uy, s, false);
+          sample_push(F, s, 1, 0);
+        }
+        break;
+      case PUCFEM_F_C: sample_push(F, c.c_full, 1, 0); break;
+      default: throw Error(PUCFEM_EINVAL, "not a sampled field (U, USTAR, P, P2, DIV_STAR, DIV_U, FINAL_DIV, C)");
+    }
+  }
+  return F;
+}
+// a raster's window, tiles and grid
+struct RasterPlan {
+  RasterWin R;
+  int32_t tiles_x;
+  int64_t ntiles, plane;
+  int grid;
+};
+RasterPlan raster_plan(int32_t W, int32_t H, const double* w4) {
+  require(W >= 1 && H >= 1, "raster width and height must be positive");
+  require((int64_t)W * H <= (int64_t)0x7fffffff, "more than 2^31 - 1 pixels");
+  const double dflt[4] = {0.0, 0.0, 1.0, 1.0};
+  const double* w = w4 ? w4 : dflt;
+  require(std::isfinite(w[0]) && std::isfinite(w[1]) && std::isfinite(w[2]) && std::isfinite(w[3]) && w[2] > w[0] &&
+              w[3] > w[1],
+          "degenerate window (x0 < x1 and y0 < y1, finite)");
+  RasterPlan p{};
+  p.R = RasterWin{w[0], w[1], w[2], w[3], W, H};
+  p.tiles_x = (W + RT - 1) / RT;
+  p.ntiles = (int64_t)p.tiles_x * ((H + RT - 1) / RT);
+  p.plane = (int64_t)W * H;
+  p.grid = (int)std::min<int64_t>(p.ntiles, 262144);
+  return p;
+}
+void launch_raster(Ctx& c, const RasterPlan& p, const SampleFields& F, float* dout) {
+  if (c.lat_sl)
+    hipLaunchKernelGGL(k_raster<LatLocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.llgrid, p.R, p.tiles_x, p.ntiles, F, dout);
+  else
+    hipLaunchKernelGGL(k_raster<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles, F, dout);
+  KCHK();
+}
+}  // namespace
+
+int pucfem_sample_points(void* ctx, int32_t nfields, const int32_t* fields, int64_t npoints, const double* xy,
+                         double* out, int32_t* tri_out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    sample_ready(c);
+    require(npoints >= 1 && npoints <= (int64_t)0x7fffffff, "npoints must be in 1 .. 2^31 - 1");
+    require(xy != nullptr && out != nullptr, "null points or output");
+    const SampleFields F = sample_fields(c, nfields, fields);
+    const size_t np = (size_t)npoints;
+    double* dxy = c.smp_scratch<double>(0, 2 * np);
+    double* dout = c.smp_scratch<double>(1, (size_t)F.ncomp * np);
+    int32_t* dtri = tri_out ? c.smp_scratch<int32_t>(2, np) : nullptr;
+    c.h2d(dxy, xy, sizeof(double) * 2 * np);
+    const int grid = (int)std::min<int64_t>(65536, (npoints + BS - 1) / BS);
+    if (c.lat_sl)
+      hipLaunchKernelGGL(k_sample_points<LatLocDev>, dim3(grid), dim3(BS), 0, c.st, c.llgrid, npoints,
+                         (const double*)dxy, F, dout, dtri);
+    else
+      hipLaunchKernelGGL(k_sample_points<LocDev>, dim3(grid), dim3(BS), 0, c.st, c.lgrid, npoints, (const double*)dxy,
+                         F, dout, dtri);
+    KCHK();
+    c.d2h(out, dout, sizeof(double) * (size_t)F.ncomp * np);
+    if (tri_out) c.d2h(tri_out, dtri, sizeof(int32_t) * np);
+  });
+}
+
+int pucfem_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t width, int32_t height,
+                  const double* window4, float* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    sample_ready(c);
+    const RasterPlan p = raster_plan(width, height, window4);
+    require(out != nullptr, "null output");
+    const SampleFields F = sample_fields(c, nfields, fields);
+    const size_t count = (size_t)F.ncomp * (size_t)p.plane;
+    float* dout = c.smp_scratch<float>(1, count);
+    launch_raster(c, p, F, dout);
+    c.d2h(out, dout, sizeof(float) * count);
+  });
+}
+
+int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t member, int32_t width, int32_t height,
+                      const double* window4, float* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    sample_ready(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const RasterPlan p = raster_plan(width, height, window4);
+    require(out != nullptr, "null output");
+    require(nfields >= 1 && fields != nullptr, "nfields < 1");
+    SampleFields F{};
+    for (int32_t k = 0; k < nfields; ++k) {
+      require(fields[k] != PUCFEM_F_TRACERS && fields[k] != PUCFEM_F_STATUS, "tracer fields are not rasterised");
+      const EnsField f = ens_field(c, e, fields[k]);
+      for (int q = 0; q < f.comp; ++q) sample_push(F, f.a + q, f.comp, f.per);
+    }
+    const int32_t m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+    const size_t count = (size_t)nm * (size_t)F.ncomp * (size_t)p.plane;
+    float* dout = c.smp_scratch<float>(1, count);
+    hipLaunchKernelGGL(k_ens_raster<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles, F, m0,
+                       nm, dout);
+    KCHK();
+    c.d2h(out, dout, sizeof(float) * count);
+  });
+}
+
+int pucfem_raster_probe(void* ctx, int32_t nfields, const int32_t* fields, int32_t width, int32_t height,
+                        const double* window4, int32_t iters, double* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    sample_ready(c);
+    const RasterPlan p = raster_plan(width, height, window4);
+    require(iters >= 1 && out4 != nullptr, "iters < 1 or null output");
+    const SampleFields F = sample_fields(c, nfields, fields);
+    const size_t count = (size_t)F.ncomp * (size_t)p.plane;
+    float* dout = c.smp_scratch<float>(1, count);
+    unsigned long long* dcnt = c.smp_scratch<unsigned long long>(3, 2);
+    HIPCHK(hipMemsetAsync(dcnt, 0, 2 * sizeof(unsigned long long), c.st));
+    if (c.lat_sl)
+      hipLaunchKernelGGL(k_raster_count<LatLocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.llgrid, p.R, p.tiles_x, p.ntiles,
+                         dcnt);
+    else
+      hipLaunchKernelGGL(k_raster_count<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles,
+                         dcnt);
+    KCHK();
+    launch_raster(c, p, F, dout);  // (untimed: the first launch)
+    hipEvent_t ea, eb;
+    HIPCHK(hipEventCreate(&ea));
+    HIPCHK(hipEventCreate(&eb));
+    HIPCHK(hipEventRecord(ea, c.st));
+    for (int k = 0; k < iters; ++k) launch_raster(c, p, F, dout);
+    HIPCHK(hipEventRecord(eb, c.st));
+    HIPCHK(hipEventSynchronize(eb));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
+    (void)hipEventDestroy(ea);
+    (void)hipEventDestroy(eb);
+    unsigned long long h[2] = {0, 0};
+    c.d2h(h, dcnt, sizeof(h));
+    out4[0] = (double)ms / iters;
+    out4[1] = (double)h[0];
+    out4[2] = (double)h[1];
+    out4[3] = (double)(sizeof(float) * count);
   });
 }
 

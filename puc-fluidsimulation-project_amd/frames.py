@@ -8,6 +8,10 @@ node's velocity, titled "Fluid Simulation - Step k", and saves it with ffmpeg at
 ffmpeg when it is installed, else an animated GIF (Pillow) or a PNG sequence; ``save_npz`` /
 ``load_npz`` keep the raw frames and ``write_vtk`` writes one frame as a legacy VTK unstructured grid
 (ParaView / VisIt), which needs no plotting stack at all.
+
+``FrameRecorder(mesh, interval, raster=(W, H))`` records images rasterised on the device instead
+(``StokesSimulation.raster``): no field leaves the GPU, and ``render`` draws them with ``imshow`` -- the
+way to frames of a mesh whose triangles no plotting library draws (L7: 28M).
 """
 from __future__ import annotations
 
@@ -19,12 +23,19 @@ import numpy as np
 
 class FrameRecorder:
     """Record (step, dye, velocity) every `interval` steps of a simulation (fp32 copies by default,
-    half the host memory of the reference's fp64 lists)."""
+    half the host memory of the reference's fp64 lists).
 
-    def __init__(self, mesh, interval=50, dtype=np.float32):
+    raster=(W, H): record W x H images instead of the nodal fields -- ``sim.raster`` rasterises the dye and the
+    velocity of `window` = (x0, y0, x1, y1) (None: the unit square) on the device, so a frame costs its pixels
+    at any mesh size and the fields are never copied.  ``dye`` then holds float32 (H, W) images and ``vel``
+    (2, H, W) ones (row 0 the lowest y, NaN inside the swimmer)."""
+
+    def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None):
         self.mesh = mesh
         self.interval = int(interval)
         self.dtype = dtype
+        self.raster = None if raster is None else (int(raster[0]), int(raster[1]))
+        self.window = None if window is None else tuple(float(v) for v in window)
         self.steps: list[int] = []
         self.dye: list[np.ndarray] = []
         self.vel: list[np.ndarray] = []
@@ -33,6 +44,15 @@ class FrameRecorder:
         self.steps.append(int(step))
         self.dye.append(np.array(c, dtype=self.dtype, copy=True) if c is not None else None)
         self.vel.append(np.array(u, dtype=self.dtype, copy=True))
+
+    def record_raster(self, step, sim):
+        """One raster frame of `sim` (its dye only under scheme 'color')."""
+        W, H = self.raster
+        color = sim.scheme == "color"
+        img = sim.raster(W, H, fields=("c", "u") if color else ("u",), window=self.window)
+        self.steps.append(int(step))
+        self.dye.append(np.asarray(img["c"], dtype=np.float32) if color else None)
+        self.vel.append(np.asarray(img["u"], dtype=np.float32))
 
     def run(self, sim, steps):
         """Step `sim` (a StokesSimulation) `steps` times, recording the state after every step whose
@@ -46,7 +66,10 @@ class FrameRecorder:
             n = min(end, r + 1) - k0
             stats += sim.step(n)
             if sim.step_count - 1 == r:
-                self.record(r, sim.c if sim.scheme == "color" else None, sim.u)
+                if self.raster is not None:
+                    self.record_raster(r, sim)
+                else:
+                    self.record(r, sim.c if sim.scheme == "color" else None, sim.u)
         return stats
 
     def __len__(self):
@@ -54,8 +77,15 @@ class FrameRecorder:
 
 
 def save_npz(rec: FrameRecorder, path):
-    d = dict(steps=np.array(rec.steps), coords=rec.mesh.coords, triangles=rec.mesh.triangles,
-             vel=np.stack(rec.vel) if rec.vel else np.zeros((0, rec.mesh.N, 2)))
+    """The raw frames.  Raster frames: `vel` (frames, 2, H, W), `dye` (frames, H, W) and `window`
+    (x0, y0, x1, y1) instead of the mesh."""
+    if getattr(rec, "raster", None) is not None:
+        W, H = rec.raster
+        d = dict(steps=np.array(rec.steps), window=np.array(rec.window or (0.0, 0.0, 1.0, 1.0), dtype=np.float64),
+                 vel=np.stack(rec.vel) if rec.vel else np.zeros((0, 2, H, W), dtype=np.float32))
+    else:
+        d = dict(steps=np.array(rec.steps), coords=rec.mesh.coords, triangles=rec.mesh.triangles,
+                 vel=np.stack(rec.vel) if rec.vel else np.zeros((0, rec.mesh.N, 2)))
     if rec.dye and rec.dye[0] is not None:
         d["dye"] = np.stack(rec.dye)
     np.savez_compressed(path, **d)
@@ -135,7 +165,9 @@ def read_vtk_header(path):
 def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     """Animate the recorded frames as the reference does (tripcolor of the dye + quiver of the
     velocity, good_visualization2.py:536-571).  out ending in .mp4 uses ffmpeg (if installed), .gif
-    Pillow; a directory name writes frame_00000.png ...  Returns the written path(s)."""
+    Pillow; a directory name writes frame_00000.png ...  Returns the written path(s).
+    Raster frames are drawn with imshow (magma, [0, 1], origin lower, the window as extent) under a quiver
+    of every `skip`-th pixel's velocity."""
     import matplotlib
 
     matplotlib.use("Agg")
@@ -143,23 +175,49 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     import matplotlib.tri as mtri
     from matplotlib import animation
 
-    X, T = rec.mesh.coords, rec.mesh.triangles
-    skip = skip or max(1, len(X) // 1500)
-    tri = mtri.Triangulation(X[:, 0], X[:, 1], T)
     fig, ax = plt.subplots(figsize=(8, 8))
-    dye0 = rec.dye[0] if rec.dye and rec.dye[0] is not None else np.zeros(len(X))
-    tpc = ax.tripcolor(tri, dye0, shading="gouraud", cmap="magma", vmin=0, vmax=1.0)
+    if getattr(rec, "raster", None) is not None:
+        # raster frames: the dye image under a quiver of the velocity image on a coarse pixel stride; the
+        # swimmer's NaN pixels stay transparent (the axes' grey shows) and carry no arrows
+        W, H = rec.raster
+        x0, y0, x1, y1 = rec.window or (0.0, 0.0, 1.0, 1.0)
+        skip = skip or max(1, max(W, H) // 40)
+        ax.set_facecolor("0.5")
+        dye0 = rec.dye[0] if rec.dye and rec.dye[0] is not None else np.zeros((H, W), dtype=np.float32)
+        tpc = ax.imshow(dye0, cmap="magma", vmin=0, vmax=1.0, origin="lower", extent=(x0, x1, y0, y1),
+                        interpolation="nearest")
+        px = x0 + (np.arange(W)[skip // 2::skip] + 0.5) * (x1 - x0) / W
+        py = y0 + (np.arange(H)[skip // 2::skip] + 0.5) * (y1 - y0) / H
+
+        def arrows(i):
+            v = rec.vel[i][:, skip // 2::skip, skip // 2::skip]
+            return np.ma.masked_invalid(v[0]), np.ma.masked_invalid(v[1])
+
+        qv = ax.quiver(*np.meshgrid(px, py), *arrows(0), color="white", scale=20.0)
+        ax.set_xlim(x0, x1)
+        ax.set_ylim(y0, y1)
+    else:
+        X, T = rec.mesh.coords, rec.mesh.triangles
+        skip = skip or max(1, len(X) // 1500)
+        tri = mtri.Triangulation(X[:, 0], X[:, 1], T)
+        dye0 = rec.dye[0] if rec.dye and rec.dye[0] is not None else np.zeros(len(X))
+        tpc = ax.tripcolor(tri, dye0, shading="gouraud", cmap="magma", vmin=0, vmax=1.0)
+        qv = ax.quiver(X[::skip, 0], X[::skip, 1], rec.vel[0][::skip, 0], rec.vel[0][::skip, 1], color="white",
+                       scale=20.0)
+        ax.set_xlim(0, 1)
+        ax.set_ylim(0, 1)
+
+        def arrows(i):
+            return rec.vel[i][::skip, 0], rec.vel[i][::skip, 1]
+
     fig.colorbar(tpc, ax=ax, label="Dye concentration")
-    qv = ax.quiver(X[::skip, 0], X[::skip, 1], rec.vel[0][::skip, 0], rec.vel[0][::skip, 1], color="white", scale=20.0)
     ax.set_aspect("equal")
-    ax.set_xlim(0, 1)
-    ax.set_ylim(0, 1)
     title = ax.set_title(f"Fluid Simulation - Step {rec.steps[0]}")
 
     def update(i):
         if rec.dye[i] is not None:
             tpc.set_array(rec.dye[i])
-        qv.set_UVC(rec.vel[i][::skip, 0], rec.vel[i][::skip, 1])
+        qv.set_UVC(*arrows(i))
         title.set_text(f"Fluid Simulation - Step {rec.steps[i]}")
         return tpc, qv, title
 

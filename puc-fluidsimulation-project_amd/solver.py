@@ -16,6 +16,57 @@ from . import _lib
 from .mesh import Mesh, boundary_sets, filter_wall_pairs, find_boundary_pairs, INNER_BOUNDARY_MARKER
 
 SCHEMES = {"color": _lib.STOKES_COLOR, "food": _lib.STOKES_FOOD, "heat": _lib.HEAT, "poisson": _lib.POISSON}
+# fields of pucfem_sample_points / pucfem_raster by name: (enum, components)
+SAMPLE_FIELDS = {"u": (_lib.F_U, 2), "u_star": (_lib.F_USTAR, 2), "p": (_lib.F_P, 1), "p2": (_lib.F_P2, 1),
+                 "div_star": (_lib.F_DIV_STAR, 1), "div_u": (_lib.F_DIV_U, 1), "final_div": (_lib.F_FINAL_DIV, 1),
+                 "c": (_lib.F_C, 1)}
+_SAMPLE_NCOMP = {f: n for f, n in SAMPLE_FIELDS.values()}
+
+
+def _sample_spec(fields):
+    """(names, enum array, components) of a field list given by name ("u", "c", ...) or pucfem_field value."""
+    if isinstance(fields, (str, int, np.integer)):
+        fields = (fields,)
+    names, ids, ncomp = [], [], []
+    for f in fields:
+        if isinstance(f, str):
+            if f not in SAMPLE_FIELDS:
+                raise ValueError(f"unknown field {f!r}: one of {sorted(SAMPLE_FIELDS)}")
+            e, n = SAMPLE_FIELDS[f]
+        else:
+            e = int(f)
+            n = _SAMPLE_NCOMP.get(e, 1)  # (a field the library refuses: it reports the error)
+        names.append(f)
+        ids.append(e)
+        ncomp.append(n)
+    return names, np.array(ids, dtype=np.int32), ncomp
+
+
+def _window(window):
+    if window is None:
+        return None, None
+    w = np.ascontiguousarray(window, dtype=np.float64).reshape(4)
+    return w, _lib.dptr(w)
+
+
+def pixel_centres(width, height, window=None):
+    """The (height * width, 2) points a raster samples, row j = 0 (the lowest y) first: pixel (i, j) of the window
+    (x0, y0, x1, y1) (None: the unit square) at x0 + (i + 0.5) (x1 - x0) / width, y0 + (j + 0.5) (y1 - y0) / height,
+    in the library's operation order (pucfem_raster)."""
+    x0, y0, x1, y1 = (0.0, 0.0, 1.0, 1.0) if window is None else [float(v) for v in window]
+    x = x0 + (np.arange(width, dtype=np.float64) + 0.5) * (x1 - x0) / float(width)
+    y = y0 + (np.arange(height, dtype=np.float64) + 0.5) * (y1 - y0) / float(height)
+    X, Y = np.meshgrid(x, y)
+    return np.ascontiguousarray(np.stack([X.ravel(), Y.ravel()], 1))
+
+
+def _split_images(names, ncomp, img):
+    """{name: (..., H, W) or (..., 2, H, W)} from an image stack whose component axis is -3."""
+    out, k = {}, 0
+    for f, n in zip(names, ncomp):
+        out[f] = img[..., k, :, :] if n == 1 else img[..., k:k + n, :, :]
+        k += n
+    return out
 
 
 @dataclass
@@ -202,6 +253,44 @@ class Context:
         st = (_lib.StepStats * max(n, 1))()
         self._c(self.L.pucfem_step(self.h, n, st))
         return [st[i] for i in range(n)]
+
+    def sample(self, fields, points):
+        """Fields at arbitrary points on the device (pucfem_sample_points; StokesFood.py:482-487's locate and
+        interpolate): ({field: (n,) or (n, 2) float64}, triangle ids (n,) int32, -1 where no triangle holds the
+        point and the values are NaN).  fields: names ("u", "u_star", "p", "p2", "div_star", "div_u", "final_div",
+        "c") or pucfem_field values; points (n, 2), taken as given (no periodic wrap)."""
+        names, ids, ncomp = _sample_spec(fields)
+        P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        n = P.shape[0]
+        out = np.zeros((sum(ncomp), n))
+        tri = np.zeros(n, dtype=np.int32)
+        self._c(self.L.pucfem_sample_points(self.h, len(ids), _lib.iptr(ids), n, _lib.dptr(P), _lib.dptr(out),
+                                            _lib.iptr(tri)))
+        vals, k = {}, 0
+        for f, nc in zip(names, ncomp):
+            vals[f] = out[k].copy() if nc == 1 else np.ascontiguousarray(out[k:k + nc].T)
+            k += nc
+        return vals, tri
+
+    def raster(self, fields, width, height, window=None):
+        """Fields as width x height images of `window` = (x0, y0, x1, y1) (None: the unit square), rasterised on
+        the device (pucfem_raster; the frames of scripts/good_visualization2.py:536-571 without a copy of the
+        fields): {field: float32 (height, width) or (2, height, width)}, row 0 the lowest y, NaN where no triangle
+        holds the pixel centre (outside the mesh, inside the swimmer)."""
+        names, ids, ncomp = _sample_spec(fields)
+        w, wp = _window(window)
+        # (a non-positive size: an empty buffer, and the library reports the error)
+        img = np.zeros((sum(ncomp), max(int(height), 0), max(int(width), 0)), dtype=np.float32)
+        self._c(self.L.pucfem_raster(self.h, len(ids), _lib.iptr(ids), int(width), int(height), wp, _lib.fptr(img)))
+        return _split_images(names, ncomp, img)
+
+    def raster_probe(self, fields, width, height, window=None, iters=10):
+        """Kernel time and pixel bookkeeping of raster() (pucfem_raster_probe; tools/raster_bench.py)."""
+        _, ids, _ = _sample_spec(fields)
+        w, wp = _window(window)
+        o = (ct.c_double * 4)()
+        self._c(self.L.pucfem_raster_probe(self.h, len(ids), _lib.iptr(ids), int(width), int(height), wp, int(iters), o))
+        return dict(kernel_ms=o[0], not_found=int(o[1]), first_face=int(o[2]), image_bytes=int(o[3]))
 
     def apply(self, op, x, out_shape):
         x = np.ascontiguousarray(x, dtype=np.float64)
@@ -400,6 +489,14 @@ class StokesSimulation:
     def field(self, f, ncomp=1):
         return self.ctx.get_field(f, (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,))
 
+    def sample(self, points, fields=("u", "c")):
+        """The fields at arbitrary points (Context.sample): ({field: values}, triangle ids)."""
+        return self.ctx.sample(fields, points)
+
+    def raster(self, width, height, fields=("c", "u"), window=None):
+        """The fields as images (Context.raster): {name: float32 (height, width) or (2, height, width)}."""
+        return self.ctx.raster(fields, width, height, window)
+
     @property
     def tracers(self):
         n = self._ntr()
@@ -541,6 +638,19 @@ class StokesEnsemble:
     @tracer_status.setter
     def tracer_status(self, v):
         self.set(_lib.F_STATUS, np.asarray(v, dtype=np.float64))
+
+    def raster(self, width, height, fields=("c", "u"), window=None, member=None):
+        """Every member's fields as images (pucfem_ens_raster: the swimmers side by side, each pixel located once
+        for all members): {name: float32 (M, height, width) or (M, 2, height, width)}; member = m: that member's
+        images without the leading axis.  Fields "u", "u_star", "p", "p2", "c"."""
+        names, ids, ncomp = _sample_spec(fields)
+        w, wp = _window(window)
+        nm = self.M if member is None else 1
+        img = np.zeros((nm, sum(ncomp), max(int(height), 0), max(int(width), 0)), dtype=np.float32)
+        self.ctx._c(self.ctx.L.pucfem_ens_raster(self.ctx.h, len(ids), _lib.iptr(ids),
+                                                 -1 if member is None else int(member), int(width), int(height), wp,
+                                                 _lib.fptr(img)))
+        return _split_images(names, ncomp, img if member is None else img[0])
 
     def step(self, n=1, stats=True):
         """n steps of every member: a list over the steps of lists over the members of step records
