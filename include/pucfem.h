@@ -128,7 +128,11 @@ enum pucfem_field {
   PUCFEM_F_C = 7,         /* dye c  (N) */
   PUCFEM_F_SCALAR = 8,    /* heat u / Poisson f (N) */
   PUCFEM_F_TRACERS = 9,   /* tracer_points (n_tr,2); set_field defines n_tr */
-  PUCFEM_F_STATUS = 10    /* tracer_status (n_tr) as 0.0 / 1.0 */
+  PUCFEM_F_STATUS = 10,   /* tracer_status (n_tr) as 0.0 / 1.0 */
+  /* capture steps (n_tr) as doubles, read only: the 1-based tracer step (counted since the tracers were last set)
+     in which the tracer's status first became 1, -1 while it is uncaptured.  Setting TRACERS resets them (and the
+     step count) as it clears the status; setting STATUS leaves them alone. */
+  PUCFEM_F_CAPTURE_STEP = 11
 };
 
 /* operators for pucfem_apply / pucfem_solve / pucfem_host_get_csr */
@@ -211,8 +215,9 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats /* nsteps en
    (StokesColor.py:482-483), c = 1[x < 0.5] (:493-495), the context's current tracers with status 0. */
 int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values);
 int pucfem_ens_destroy(void* ctx);
-/* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS in the caller's numbering; member = -1: all members,
-   member-major (count = members x the field's values per member).  Setting TRACERS clears the status. */
+/* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS (and, read only, _CAPTURE_STEP) in the caller's
+   numbering; member = -1: all members, member-major (count = members x the field's values per member).  Setting
+   TRACERS clears the status, the capture steps and the step count of the members it sets. */
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count);
 int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, int64_t count);
 /* nsteps steps of every member (StokesColor.py:537-586 / StokesFood.py:441-505 per member); stats: NULL or
@@ -270,6 +275,12 @@ int pucfem_sl_advect(void* ctx, const double* c, const double* u, double dt, dou
                      int32_t* notfound);
 /* tracer step (StokesFood.py:482-499) on the tracers held in the context, with u given */
 int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps);
+/* the context's tracer set (member = -1) or that of member `member` of its ensemble: out[0] tracers, [1] tracers
+   with status 1 (eaten), [2] tracers whose position is not finite (they left the mesh: NaN stays NaN,
+   StokesFood.py:482-499) -- both counted by a reduction at this call --, [3] tracer steps since the set was set,
+   [4] blocks in x of the last tracer launch (1: the one-block kernel; larger sets step one tracer per thread on a
+   grid, with the same bits), [5] that launch's threads per block ([4], [5]: 0 before the first launch) */
+int pucfem_tracer_info(void* ctx, int32_t member, int64_t* out6);
 /* makePerBCU / makeDirBCU (StokesColor.py:405-431) on a host velocity u (N,2), in place, through the
    device's boundary kernels: which bit 0 = makePerBCU (slave <- master copies), bit 1 = makeDirBCU
    (walls and squirmer surface); both: the periodic copies first, as the step applies them.

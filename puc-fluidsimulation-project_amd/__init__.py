@@ -18,6 +18,6 @@ from .solver import (SAMPLE_FIELDS, Context, HeatSimulation, Result, SquirmerBC,
                      StokesSimulation, Tolerances, ensemble_dirichlet_values, pixel_centres, poisson_solve, solve,
                      solve_ensemble, squirmer_values)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401
-from .tracers import tracer_init  # noqa: F401
+from .tracers import capture_map, tracer_init  # noqa: F401
 
 __version__ = "0.1.0"

@@ -17,6 +17,7 @@ LIBNAME = "libpucfem.so"
 # enums (pucfem.h)
 STOKES_COLOR, STOKES_FOOD, HEAT, POISSON = 0, 1, 2, 3
 F_U, F_USTAR, F_P, F_P2, F_DIV_STAR, F_DIV_U, F_FINAL_DIV, F_C, F_SCALAR, F_TRACERS, F_STATUS = range(11)
+F_CAPTURE_STEP = 11
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 HOST_ONLY = -1
 ERRORS = {-1: "EINVAL", -2: "EHIP", -3: "ENOCONV", -4: "ESTATE", -5: "ENCCL", -6: "ENOMEM", -7: "ENODEV"}
@@ -95,6 +96,7 @@ SIGNATURES = {
     "pucfem_mg_lmax": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_proj_info": ([_P, _D], ct.c_int),
     "pucfem_tracer_step": ([_P, _D, ct.c_double, ct.c_int32], ct.c_int),
+    "pucfem_tracer_info": ([_P, ct.c_int32, _I64], ct.c_int),
     "pucfem_mixing_index": ([_P, _D, _D], ct.c_int),
     "pucfem_mixing_index_w": ([_P, _D, _D, _D], ct.c_int),
     "pucfem_comm_selftest": ([_P, _D], ct.c_int),

@@ -138,7 +138,12 @@ struct Ens {
   double *u = nullptr, *us = nullptr, *p = nullptr, *p2 = nullptr, *braw = nullptr, *c = nullptr, *cn = nullptr;
   double *dval = nullptr, *trx = nullptr, *try_ = nullptr, *trs = nullptr, *vals = nullptr;
   double *part_d = nullptr, *part_sl = nullptr, *part_mx = nullptr, *ring = nullptr;
-  unsigned* cnt = nullptr;  // ticket counters: 3 launch sites (divergence, advection, mixing) x M
+  unsigned* cnt = nullptr;  // ticket counters: 4 launch sites (divergence, advection, mixing, tracer cloud) x M
+  int32_t* trcap = nullptr;   // capture steps (M x ntr, -1: not captured)
+  int32_t* trstep = nullptr;  // per member: tracer steps since its tracers were set
+  double* part_tr = nullptr;  // k_ens_tracer_cloud's partials
+  int nb_tr = 1;              // blocks in x of the tracer launch (1: k_ens_tracer)
+  int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
   int ring_steps = 0;
   int gx_dense = 1, nb_div = 1, nb_sl = 1, nb_mix = 1;
@@ -571,6 +576,12 @@ struct Ctx {
   int32_t* dnotfound = nullptr;
   int32_t ntr = 0;
   double *trx = nullptr, *try_ = nullptr, *trs = nullptr, *d_eaten = nullptr;
+  int32_t* trcap = nullptr;   // capture steps (-1: not captured), written by tracer_move
+  int32_t* trstep = nullptr;  // tracer steps since the set was set: read and advanced on the device (a captured step's
+                              // arguments are fixed)
+  double* part_tr = nullptr;  // the cloud kernels' per-block eaten partials (TRACER_CLOUD_MAXB)
+  unsigned long long* trcensus = nullptr;  // pucfem_tracer_info's two counts
+  int tr_blocks = 0, tr_threads = 0;       // the last tracer launch
   // iteration count of the last solve per `which` slot (the next solve's first host check): 0 viscous,
   // 1 / 2 the two pressure solves of a step, 3 / 4 standalone viscous / pressure solves (pucfem_solve)
   int last_it[6] = {0, 0, 0, 0, 0, 0};
@@ -997,8 +1008,8 @@ struct Ctx {
   // steps/s against 107.2 with k_reduce (r8a/r8b, same box type): under streaming load each block's
   // write-through partial store and returned ticket (two memory round trips in the block's tail) cost
   // 10-25 us per producer launch, more than the 9-14 us k_reduce launch they remove.
-  enum { CNT_VCHEB, CNT_INIT, CNT_RZ, CNT_DIR, CNT_UPD, CNT_DIV, CNT_MDOT, CNT_MIX, CNT_SL, CNT_DYE_DIV = 16,
-         CNT_DYE_SL, CNT_DYE_MIX, CNT_N = 32 };
+  enum { CNT_VCHEB, CNT_INIT, CNT_RZ, CNT_DIR, CNT_UPD, CNT_DIV, CNT_MDOT, CNT_MIX, CNT_SL, CNT_TRACER,
+         CNT_DYE_DIV = 16, CNT_DYE_SL, CNT_DYE_MIX, CNT_N = 32 };
   unsigned* dcnt = nullptr;
   bool fused_red = std::getenv("PUCFEM_FUSED_RED") && std::atoi(std::getenv("PUCFEM_FUSED_RED")) != 0;
   RedOut ro(double* out, int cnt, int nv, int stride = MAXB, unsigned maxmask = 0u, double* out1 = nullptr) const {
@@ -2959,6 +2970,13 @@ struct Ctx {
     }
     if (!has_tgrid) throw Error(PUCFEM_ESTATE, "tracer grid not built (scheme is not STOKES_FOOD)");
     double *fx = ux, *fy = uy;
+    // TRACER_CLOUD_MIN tracers and more: one tracer per thread on a grid, the eaten count through the kernel's own
+    // ticket (always fused: the count is exact in any order, and a k_reduce launch would cost more than the kernel)
+    const int nbt = tracer_blocks(ntr);
+    const bool cloud = nbt > 1;
+    const RedOut rt{vals + 6, nullptr, dcnt + CNT_TRACER, 1, TRACER_CLOUD_MAXB, 0u};
+    tr_blocks = nbt;
+    tr_threads = BS;
     if (dist()) {
       // no replica of u: each rank interpolates the tracers in its own triangles from its owned and
       // ghost values (placed at their global ids), then one all-reduce of 3 x ntr values hands every
@@ -2978,14 +2996,43 @@ struct Ctx {
                          (int64_t)lp.r0, (int64_t)lp.r1, trv);
       KCHK();
       comm->allreduce(trv, 3 * (size_t)ntr, false, st);
-      hipLaunchKernelGGL(k_tracer_move, dim3(1), dim3(BS), 0, st, ntr, trx, try_, trs, (const double*)trv, dt,
-                         prm.center_x, prm.center_y, prm.capture_radius, vals + 6);
+      if (cloud)
+        hipLaunchKernelGGL(k_tracer_move_cloud, dim3(nbt), dim3(BS), 0, st, ntr, trx, try_, trs, trcap, trstep,
+                           (const double*)trv, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt);
+      else
+        hipLaunchKernelGGL(k_tracer_move, dim3(1), dim3(BS), 0, st, ntr, trx, try_, trs, trcap, trstep,
+                           (const double*)trv, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6);
       KCHK();
       return;
     }
-    hipLaunchKernelGGL(k_tracer, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr, trx,
-                       try_, trs, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6);
+    if (cloud)
+      hipLaunchKernelGGL(k_tracer_cloud, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
+                         trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt);
+    else
+      hipLaunchKernelGGL(k_tracer, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr, trx,
+                         try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6);
     KCHK();
+  }
+  // blocks in x of a tracer launch over n tracers: 1 = the one-block kernels, else the cloud kernels' capped grid
+  static int tracer_blocks(i64 n) {
+    return n < TRACER_CLOUD_MIN ? 1 : (int)std::min<i64>(TRACER_CLOUD_MAXB, (n + BS - 1) / BS);
+  }
+  // the small-mesh step graphs hold the tracer arrays and their count as kernel arguments: dropped when those
+  // change, recaptured by the next pucfem_step
+  void drop_step_graphs() {
+    if (gexec) {
+      (void)hipGraphExecDestroy(gexec);
+      (void)hipGraphDestroy(graph);
+      gexec = nullptr;
+      graph = nullptr;
+      graph_mode = false;
+    }
+    if (gexec_k) {
+      (void)hipGraphExecDestroy(gexec_k);
+      (void)hipGraphDestroy(graph_k);
+      gexec_k = nullptr;
+      graph_k = nullptr;
+    }
   }
 
   // ------------------------------------------------------------------ literal operators (heat / Poisson)
@@ -4703,19 +4750,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
       (void)hipStreamSynchronize(c.st);
       c.ens.reset();
     }
-    if (c.gexec) {
-      (void)hipGraphExecDestroy(c.gexec);
-      (void)hipGraphDestroy(c.graph);
-      c.gexec = nullptr;
-      c.graph = nullptr;
-      c.graph_mode = false;
-    }
-    if (c.gexec_k) {
-      (void)hipGraphExecDestroy(c.gexec_k);
-      (void)hipGraphDestroy(c.graph_k);
-      c.gexec_k = nullptr;
-      c.graph_k = nullptr;
-    }
+    c.drop_step_graphs();
     build(c);
   });
 }
@@ -4763,12 +4798,21 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
       case PUCFEM_F_TRACERS: {
         require(count % 2 == 0, "tracers must be (n, 2)");
         const i64 n = count / 2;
-        if (n != c.ntr) {
+        require(n <= INT32_MAX, "at most 2^31 - 1 tracers");
+        if (n != c.ntr || !c.trcap) {
           c.ntr = (int32_t)n;
           c.trx = c.dalloc<double>(n);
           c.try_ = c.dalloc<double>(n);
           c.trs = c.dalloc<double>(n);
+          c.trcap = c.dalloc<int32_t>(n);
           if (c.dist()) c.trv = c.dalloc<double>(3 * n);
+          HIPCHK(hipStreamSynchronize(c.st));
+          c.drop_step_graphs();  // (they hold the old arrays and count)
+        }
+        if (!c.trstep) {
+          c.trstep = c.dalloc<int32_t>(1);
+          c.part_tr = c.dalloc<double>(TRACER_CLOUD_MAXB);
+          c.trcensus = c.dalloc<unsigned long long>(2);
         }
         std::vector<double> x(n), y(n);
         for (i64 k = 0; k < n; ++k) {
@@ -4778,6 +4822,8 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
         HIPCHK(hipMemcpyAsync(c.trx, x.data(), sizeof(double) * n, hipMemcpyHostToDevice, c.st));
         HIPCHK(hipMemcpyAsync(c.try_, y.data(), sizeof(double) * n, hipMemcpyHostToDevice, c.st));
         HIPCHK(hipMemsetAsync(c.trs, 0, sizeof(double) * n, c.st));
+        HIPCHK(hipMemsetAsync(c.trcap, 0xFF, sizeof(int32_t) * std::max<i64>(1, n), c.st));  // -1: not captured
+        HIPCHK(hipMemsetAsync(c.trstep, 0, sizeof(int32_t), c.st));
         break;
       }
       case PUCFEM_F_STATUS:
@@ -4867,6 +4913,15 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
         HIPCHK(hipMemcpyAsync(buf, c.trs, sizeof(double) * count, hipMemcpyDeviceToHost, c.st));
         HIPCHK(hipStreamSynchronize(c.st));
         break;
+      case PUCFEM_F_CAPTURE_STEP: {
+        require(count == c.ntr, "capture steps are (n,)");
+        std::vector<int32_t> cs((size_t)c.ntr);
+        if (c.ntr > 0)
+          HIPCHK(hipMemcpyAsync(cs.data(), c.trcap, sizeof(int32_t) * cs.size(), hipMemcpyDeviceToHost, c.st));
+        HIPCHK(hipStreamSynchronize(c.st));
+        for (size_t k = 0; k < cs.size(); ++k) buf[k] = (double)cs[k];
+        break;
+      }
       default: throw Error(PUCFEM_EINVAL, "unknown field");
     }
   });
@@ -5094,10 +5149,19 @@ void ens_enqueue_step(Ctx& c) {
                        (const double*)c.dwmix, (const double*)e.vals, e.part_mx, rm, e.c);
     KCHK();
   } else if (e.ntr > 0) {
-    hipLaunchKernelGGL(k_ens_tracer, dim3(1, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.tgrid,
-                       (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, c.prm.dt, c.prm.center_x,
-                       c.prm.center_y, c.prm.capture_radius, e.vals);
+    if (e.nb_tr > 1) {
+      const RedOut rt{e.vals + 6, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
+      hipLaunchKernelGGL(k_ens_tracer_cloud, dim3(e.nb_tr, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T},
+                         c.tgrid, (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep,
+                         c.prm.dt, c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt);
+    } else {
+      hipLaunchKernelGGL(k_ens_tracer, dim3(1, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.tgrid,
+                         (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                         c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.vals);
+    }
     KCHK();
+    e.tr_blocks = e.nb_tr;
+    e.tr_threads = BS;
   }
   hipLaunchKernelGGL(k_ens_record, dim3((M + 255) / 256), dim3(256), 0, st, M, (const double*)e.vals, e.ring, e.count);
   KCHK();
@@ -5117,7 +5181,8 @@ EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
     case PUCFEM_F_C: return {e.c, e.n, 1};
     case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
     case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
-    default: throw Error(PUCFEM_EINVAL, "not an ensemble field (U, USTAR, P, P2, C, TRACERS, STATUS)");
+    case PUCFEM_F_CAPTURE_STEP: return {nullptr, (i64)e.ntr, 0};
+    default: throw Error(PUCFEM_EINVAL, "not an ensemble field (U, USTAR, P, P2, C, TRACERS, STATUS, CAPTURE_STEP)");
   }
 }
 }  // namespace
@@ -5183,7 +5248,13 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     e.part_d = e.alloc<double>(sM * 3 * e.nb_div, st);
     e.part_sl = e.alloc<double>(sM * 3 * e.nb_sl, st);
     e.part_mx = e.alloc<double>(sM * 3 * e.nb_mix, st);
-    e.cnt = e.alloc<unsigned>(3 * sM, st);
+    // the member's grid in x: the single path's, capped so that the launch's blocks stay near the cloud kernels' cap
+    e.nb_tr = std::max(1, std::min(Ctx::tracer_blocks(e.ntr), TRACER_CLOUD_MAXB / M));
+    e.part_tr = e.alloc<double>(sM * 3 * e.nb_tr, st);
+    e.trcap = e.alloc<int32_t>(sM * (size_t)e.ntr, st);
+    HIPCHK(hipMemsetAsync(e.trcap, 0xFF, sizeof(int32_t) * std::max<size_t>(1, sM * (size_t)e.ntr), st));
+    e.trstep = e.alloc<int32_t>(sM, st);
+    e.cnt = e.alloc<unsigned>(4 * sM, st);
     e.count = e.alloc<int>(sM, st);
     e.ring_steps = (int)std::max<i64>(c.gk, std::min<i64>(Ctx::GRING, 65536 / M));
     e.ring = e.alloc<double>((size_t)e.ring_steps * sM * 8, st);
@@ -5237,6 +5308,7 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     Ctx& c = *C(ctx);
     Ens& e = *ens_of(c);
     require(member >= -1 && member < e.M, "member index out of range");
+    require(field != PUCFEM_F_CAPTURE_STEP, "capture steps cannot be set");
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
@@ -5251,6 +5323,8 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
       HIPCHK(hipMemcpyAsync(e.trx + m0 * e.ntr, x.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
       HIPCHK(hipMemcpyAsync(e.try_ + m0 * e.ntr, y.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
       HIPCHK(hipMemsetAsync(e.trs + m0 * e.ntr, 0, sizeof(double) * nm * e.ntr, c.st));  // (as pucfem_set_field)
+      HIPCHK(hipMemsetAsync(e.trcap + m0 * e.ntr, 0xFF, sizeof(int32_t) * nm * e.ntr, c.st));
+      HIPCHK(hipMemsetAsync(e.trstep + m0, 0, sizeof(int32_t) * nm, c.st));
     } else {
       for (i64 m = 0; m < nm; ++m)
         for (i64 g = 0; g < e.n && f.comp > 0; ++g) {
@@ -5273,6 +5347,13 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
     if (f.per == 0) return;
+    if (field == PUCFEM_F_CAPTURE_STEP) {
+      std::vector<int32_t> cs((size_t)(nm * e.ntr));
+      HIPCHK(hipMemcpyAsync(cs.data(), e.trcap + m0 * e.ntr, sizeof(int32_t) * cs.size(), hipMemcpyDeviceToHost, c.st));
+      HIPCHK(hipStreamSynchronize(c.st));
+      for (size_t k = 0; k < cs.size(); ++k) buf[k] = (double)cs[k];
+      return;
+    }
     if (field == PUCFEM_F_TRACERS) {
       std::vector<double> x((size_t)(nm * e.ntr)), y(x.size());
       HIPCHK(hipMemcpyAsync(x.data(), e.trx + m0 * e.ntr, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
@@ -5894,6 +5975,49 @@ int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps) {
     HIPCHK(hipMemcpyAsync(c.ux, bxy.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c.st));
     for (int s = 0; s < nsteps; ++s) c.tracer_advance(dt);
     HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_tracer_info(void* ctx, int32_t member, int64_t* out6) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.need_dev();
+    c.need_built();
+    require(out6 != nullptr, "out is null");
+    require(member >= -1, "member index out of range");
+    i64 n = c.ntr;
+    const double *tx = c.trx, *ty = c.try_, *ts = c.trs;
+    const int32_t* stepctr = c.trstep;
+    int blocks = c.tr_blocks, threads = c.tr_threads;
+    if (member >= 0) {
+      Ens& e = *ens_of(c);
+      require(member < e.M, "member index out of range");
+      n = e.ntr;
+      tx = e.trx + (i64)member * n;
+      ty = e.try_ + (i64)member * n;
+      ts = e.trs + (i64)member * n;
+      stepctr = e.trstep + member;
+      blocks = e.tr_blocks;
+      threads = e.tr_threads;
+    }
+    unsigned long long cen[2] = {0, 0};
+    int32_t steps = 0;
+    if (n > 0) {
+      if (!c.trcensus) c.trcensus = c.dalloc<unsigned long long>(2);
+      HIPCHK(hipMemsetAsync(c.trcensus, 0, sizeof(cen), c.st));
+      hipLaunchKernelGGL(k_tracer_census, dim3((unsigned)std::min<i64>(TRACER_CLOUD_MAXB, (n + BS - 1) / BS)), dim3(BS),
+                         0, c.st, (int64_t)n, tx, ty, ts, c.trcensus);
+      KCHK();
+      HIPCHK(hipMemcpyAsync(cen, c.trcensus, sizeof(cen), hipMemcpyDeviceToHost, c.st));
+    }
+    if (stepctr) HIPCHK(hipMemcpyAsync(&steps, stepctr, sizeof(int32_t), hipMemcpyDeviceToHost, c.st));
+    HIPCHK(hipStreamSynchronize(c.st));
+    out6[0] = n;
+    out6[1] = (int64_t)cen[0];
+    out6[2] = (int64_t)cen[1];
+    out6[3] = steps;
+    out6[4] = blocks;
+    out6[5] = threads;
   });
 }
 

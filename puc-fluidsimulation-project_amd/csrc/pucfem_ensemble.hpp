@@ -347,8 +347,9 @@ __global__ __launch_bounds__(BS) void k_ens_mix2(int64_t n, const double* __rest
 
 // k_tracer per member (one block each): the single path's locate / interpolate / move.  tx, ty, status: M x ntr.
 __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
-                                                   int32_t ntr, double* tx, double* ty, double* status, double dt,
-                                                   double cx, double cy, double capture, double* vals) {
+                                                   int32_t ntr, double* tx, double* ty, double* status,
+                                                   int32_t* capstep, int32_t* stepctr, double dt, double cx, double cy,
+                                                   double capture, double* vals) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -356,16 +357,49 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
   double* txm = tx + (int64_t)m * ntr;
   double* tym = ty + (int64_t)m * ntr;
   double* stm = status + (int64_t)m * ntr;
+  int32_t* cpm = capstep + (int64_t)m * ntr;
+  const int32_t stepno = stepctr[m] + 1;  // (the member's own count: k_tracer's)
   double eaten = 0.0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
     const double px = txm[k], py = tym[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(Mh, G, px, py);
     if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(txm, tym, stm, k, vx, vy, dt, cx, cy, capture);
+    eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
-  if (threadIdx.x == 0) vals[(int64_t)ENS_VALS * m + 6] = t;
+  if (threadIdx.x == 0) {
+    vals[(int64_t)ENS_VALS * m + 6] = t;
+    stepctr[m] = stepno;
+  }
+}
+// k_tracer_cloud per member: grid (blocks, M), the member's partials, ticket and step count (ro.out: vals + 6)
+__global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
+                                                         int32_t ntr, double* tx, double* ty, double* status,
+                                                         int32_t* capstep, int32_t* stepctr, double dt, double cx,
+                                                         double cy, double capture, double* part, RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const double* ux = u + (int64_t)m * 2 * n;
+  const double* uy = ux + 1;
+  double* txm = tx + (int64_t)m * ntr;
+  double* tym = ty + (int64_t)m * ntr;
+  double* stm = status + (int64_t)m * ntr;
+  int32_t* cpm = capstep + (int64_t)m * ntr;
+  const RedOut R = ens_red(ro, m, part);
+  const int32_t stepno = stepctr[m] + 1;
+  double eaten = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
+    const int32_t k = (int32_t)i;
+    const double px = txm[k], py = tym[k];
+    double vx = NAN, vy = NAN;
+    const int32_t found = tracer_locate(Mh, G, px, py);
+    if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+    eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  const double t = block_sum(eaten, sh);
+  if (threadIdx.x == 0) red_part(R, part, 0, t);
+  if (red_finish(R, part, sh) && threadIdx.x == 0) stepctr[m] = stepno;
 }
 
 // the step's record of every member (k_stats_ring per member): slot count[m] of the ring (steps x M x 8)

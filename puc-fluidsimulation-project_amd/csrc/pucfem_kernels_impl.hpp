@@ -3314,9 +3314,11 @@ __device__ __forceinline__ void tracer_interp(const MeshDev& M, int32_t t, const
   vx = zv[0];
   vy = zv[1];
 }
-// forward Euler, x mod 1, sticky capture (StokesFood.py:488-499)
-__device__ __forceinline__ double tracer_move(double* tx, double* ty, double* status, int32_t k, double vx, double vy,
-                                              double dt, double cx, double cy, double capture) {
+// forward Euler, x mod 1, sticky capture (StokesFood.py:488-499).  capstep[k] = stepno (the 1-based tracer step being
+// taken) in the step whose move first brings status[k] to 1: one extra store, on that transition only
+__device__ __forceinline__ double tracer_move(double* tx, double* ty, double* status, int32_t* capstep, int32_t k,
+                                              double vx, double vy, double dt, double cx, double cy, double capture,
+                                              int32_t stepno) {
   const double px = tx[k], py = ty[k];
   double nx_ = px + vx * dt, ny_ = py + vy * dt;
   nx_ = py_mod(nx_, 1.0);
@@ -3324,24 +3326,66 @@ __device__ __forceinline__ double tracer_move(double* tx, double* ty, double* st
   ty[k] = ny_;
   const double ddx = nx_ - cx, ddy = ny_ - cy;
   const double dist = sqrt(ddx * ddx + ddy * ddy);
-  if (dist <= capture) status[k] = 1.0;
+  if (dist <= capture) {
+    if (status[k] != 1.0) capstep[k] = stepno;
+    status[k] = 1.0;
+  }
   return status[k];
 }
 
+// Tracer sets of at least this many tracers step on a grid (k_tracer_cloud, k_tracer_move_cloud,
+// k_ens_tracer_cloud), smaller ones in one block (k_tracer, k_tracer_move, k_ens_tracer).  A tuning constant only:
+// a tracer's arithmetic does not depend on its thread, block or grid, and the eaten count is a sum of 0.0 / 1.0
+// terms (exact in any order), so both forms give the same bits.  (tracers.CLOUD_MIN mirrors it for the tests.)
+#ifndef PUCFEM_TRACER_CLOUD_MIN
+#define PUCFEM_TRACER_CLOUD_MIN 512
+#endif
+constexpr int32_t TRACER_CLOUD_MIN = PUCFEM_TRACER_CLOUD_MIN;  // (a variant build sets it to measure the crossover)
+constexpr int TRACER_CLOUD_MAXB = 2048;  // the cloud kernels' grid cap in x (memory-bound: grid-stride beyond it)
+
+// stepctr: the set's tracer steps so far, in device memory (a captured step's arguments are fixed); the step being
+// taken is *stepctr + 1.  Every thread reads it before the block's barrier, thread 0 stores the new count after it.
 __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, const double* __restrict__ uy,
-                         int32_t ntr, double* tx, double* ty, double* status, double dt, double cx, double cy,
-                         double capture, double* eaten_out) {
+                         int32_t ntr, double* tx, double* ty, double* status, int32_t* capstep, int32_t* stepctr,
+                         double dt, double cx, double cy, double capture, double* eaten_out) {
   __shared__ double sh[4];
+  const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
     const double px = tx[k], py = ty[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(M, G, px, py);
     if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(tx, ty, status, k, vx, vy, dt, cx, cy, capture);
+    eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
-  if (threadIdx.x == 0) *eaten_out = t;
+  if (threadIdx.x == 0) {
+    *eaten_out = t;
+    *stepctr = stepno;
+  }
+}
+// k_tracer on a grid: one tracer per thread, grid-stride past the capped grid; the eaten count from per-block
+// partials (red_finish; ro.out is never null here).  The block that finishes the reduction stores the new step
+// count: every block read the old one before it drew its ticket.
+__global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const double* __restrict__ ux,
+                                                     const double* __restrict__ uy, int32_t ntr, double* tx,
+                                                     double* ty, double* status, int32_t* capstep, int32_t* stepctr,
+                                                     double dt, double cx, double cy, double capture, double* part,
+                                                     RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t stepno = *stepctr + 1;
+  double eaten = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
+    const int32_t k = (int32_t)i;
+    const double px = tx[k], py = ty[k];
+    double vx = NAN, vy = NAN;
+    const int32_t found = tracer_locate(M, G, px, py);
+    if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+    eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  const double t = block_sum(eaten, sh);
+  if (threadIdx.x == 0) red_part(ro, part, 0, t);
+  if (red_finish(ro, part, sh) && threadIdx.x == 0) *stepctr = stepno;
 }
 
 // multi-rank tracer step, part 1: every rank interpolates the tracers whose triangle it owns (its
@@ -3364,16 +3408,57 @@ __global__ void k_tracer_vel(MeshDev M, GridDev G, const double* __restrict__ fx
 }
 // part 2 (after the all-reduce, identical on every rank): the move with the owner's velocity (NaN
 // where no rank holds the tracer: outside the mesh)
-__global__ void k_tracer_move(int32_t ntr, double* tx, double* ty, double* status, const double* tv, double dt,
-                              double cx, double cy, double capture, double* eaten_out) {
+__global__ void k_tracer_move(int32_t ntr, double* tx, double* ty, double* status, int32_t* capstep, int32_t* stepctr,
+                              const double* tv, double dt, double cx, double cy, double capture, double* eaten_out) {
   __shared__ double sh[4];
+  const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
-    const bool found = tv[3 * k + 2] > 0.5;
-    eaten += tracer_move(tx, ty, status, k, found ? tv[3 * k] : NAN, found ? tv[3 * k + 1] : NAN, dt, cx, cy, capture);
+    const bool found = tv[3 * (int64_t)k + 2] > 0.5;
+    eaten += tracer_move(tx, ty, status, capstep, k, found ? tv[3 * (int64_t)k] : NAN,
+                         found ? tv[3 * (int64_t)k + 1] : NAN, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
-  if (threadIdx.x == 0) *eaten_out = t;
+  if (threadIdx.x == 0) {
+    *eaten_out = t;
+    *stepctr = stepno;
+  }
+}
+// k_tracer_move on a grid (k_tracer_cloud's shape, reduction and step count)
+__global__ __launch_bounds__(BS) void k_tracer_move_cloud(int32_t ntr, double* tx, double* ty, double* status,
+                                                          int32_t* capstep, int32_t* stepctr, const double* tv,
+                                                          double dt, double cx, double cy, double capture,
+                                                          double* part, RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t stepno = *stepctr + 1;
+  double eaten = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
+    const int32_t k = (int32_t)i;
+    const bool found = tv[3 * i + 2] > 0.5;
+    eaten += tracer_move(tx, ty, status, capstep, k, found ? tv[3 * i] : NAN, found ? tv[3 * i + 1] : NAN, dt, cx, cy,
+                         capture, stepno);
+  }
+  const double t = block_sum(eaten, sh);
+  if (threadIdx.x == 0) red_part(ro, part, 0, t);
+  if (red_finish(ro, part, sh) && threadIdx.x == 0) *stepctr = stepno;
+}
+// pucfem_tracer_info's census of a tracer set: out[0] += tracers with status 1, out[1] += tracers whose position is
+// not finite (integer atomics: the same counts in any order); out zeroed before the launch
+__global__ __launch_bounds__(BS) void k_tracer_census(int64_t ntr, const double* __restrict__ tx,
+                                                      const double* __restrict__ ty,
+                                                      const double* __restrict__ status, unsigned long long* out) {
+  __shared__ double sh[4];
+  double eaten = 0.0, lost = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * BS + threadIdx.x; k < ntr; k += (int64_t)gridDim.x * BS) {
+    eaten += status[k] == 1.0 ? 1.0 : 0.0;
+    lost += isfinite(tx[k]) && isfinite(ty[k]) ? 0.0 : 1.0;
+  }
+  const double e = block_sum(eaten, sh);
+  const double l = block_sum(lost, sh);
+  if (threadIdx.x == 0) {
+    if (e > 0.0) atomicAdd(out, (unsigned long long)e);
+    if (l > 0.0) atomicAdd(out + 1, (unsigned long long)l);
+  }
 }
 // ghost values of a local vector into their global positions of a full-size array
 // (vs: the element stride of v)

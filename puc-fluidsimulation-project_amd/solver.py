@@ -349,6 +349,14 @@ class Context:
         self._c(self.L.pucfem_proj_info(self.h, o))
         return dict(reseeds=int(o[0]), restarts=int(o[1]), guess_rel=(o[2], o[3]))
 
+    def tracer_info(self, member=None):
+        """The context's tracer set, or that of ensemble member `member` (pucfem_tracer_info): tracers, eaten and
+        lost (non-finite position) counts reduced on the device, tracer steps since the set was set, and the last
+        tracer launch's blocks (1: the one-block kernel) and threads per block."""
+        o = (ct.c_int64 * 6)()
+        self._c(self.L.pucfem_tracer_info(self.h, -1 if member is None else int(member), o))
+        return dict(tracers=o[0], eaten=o[1], nonfinite=o[2], steps=o[3], blocks=o[4], threads=o[5])
+
     def comm_info(self):
         """Multi-rank data flow of the last step (pucfem_comm_info)."""
         o = (ct.c_int64 * 4)()
@@ -502,9 +510,30 @@ class StokesSimulation:
         n = self._ntr()
         return self.ctx.get_field(_lib.F_TRACERS, (n, 2))
 
+    @tracers.setter
+    def tracers(self, v):
+        """A new tracer set, of any size: status 0, no capture steps, step count 0."""
+        if self.scheme != "food":
+            raise ValueError("tracers belong to scheme 'food'")
+        pts = np.asarray(v, dtype=np.float64).reshape(-1, 2)
+        self.ctx.set_field(_lib.F_TRACERS, pts)
+        self.n_tracers = len(pts)
+
     @property
     def tracer_status(self):
         return self.ctx.get_field(_lib.F_STATUS, (self._ntr(),)).astype(np.int64)
+
+    @tracer_status.setter
+    def tracer_status(self, v):
+        self.ctx.set_field(_lib.F_STATUS, np.asarray(v, dtype=np.float64))
+
+    @property
+    def capture_step(self):
+        """Per tracer, the 1-based tracer step (since the tracers were set) in which it was eaten; -1: never."""
+        return self.ctx.get_field(_lib.F_CAPTURE_STEP, (self._ntr(),)).astype(np.int64)
+
+    def tracer_info(self):
+        return self.ctx.tracer_info()
 
     def _ntr(self):
         return getattr(self, "n_tracers", 0)
@@ -588,7 +617,7 @@ class StokesEnsemble:
     def _shape(self, f, ncomp=1):
         if f == _lib.F_TRACERS:
             return (self.n_tracers, 2)
-        if f == _lib.F_STATUS:
+        if f in (_lib.F_STATUS, _lib.F_CAPTURE_STEP):
             return (self.n_tracers,)
         return (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,)
 
@@ -639,6 +668,14 @@ class StokesEnsemble:
     def tracer_status(self, v):
         self.set(_lib.F_STATUS, np.asarray(v, dtype=np.float64))
 
+    @property
+    def capture_step(self):
+        """(M, n): per member and tracer, the 1-based step in which it was eaten; -1: never."""
+        return self.get(_lib.F_CAPTURE_STEP).astype(np.int64)
+
+    def tracer_info(self, member=0):
+        return self.ctx.tracer_info(member)
+
     def raster(self, width, height, fields=("c", "u"), window=None, member=None):
         """Every member's fields as images (pucfem_ens_raster: the swimmers side by side, each pixel located once
         for all members): {name: float32 (M, height, width) or (M, 2, height, width)}; member = m: that member's
@@ -684,7 +721,7 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
         c = ens.c if scheme == "color" else None
-        tr, ts = (ens.tracers, ens.tracer_status) if scheme == "food" else (None, None)
+        tr, ts, cs = (ens.tracers, ens.tracer_status, ens.capture_step) if scheme == "food" else (None, None, None)
     finally:
         ens.close()
     res = []
@@ -693,7 +730,7 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
         if scheme == "color":
             r.c = c[m]
         else:
-            r.tracers, r.tracer_status = tr[m], ts[m]
+            r.tracers, r.tracer_status, r.capture_step = tr[m], ts[m], cs[m]
         res.append(r)
     return res
 
@@ -786,6 +823,7 @@ class Result:
     p: np.ndarray | None = None
     tracers: np.ndarray | None = None
     tracer_status: np.ndarray | None = None
+    capture_step: np.ndarray | None = None  # scheme 'food': per tracer, the 1-based step it was eaten in (-1: never)
     scalar: np.ndarray | None = None
     stats: list = field(default_factory=list)
 
@@ -811,7 +849,7 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
                     log(f"Step: {k}, Div(u*): {s.max_div_star:.2e}, Final Div(u): {s.max_final_div:.2e}, "
                         f"Color mixing progress={1.0 - s.mix_var / (var0 + 1e-16):.3f}")
         else:
-            res.tracers, res.tracer_status = sim.tracers, sim.tracer_status
+            res.tracers, res.tracer_status, res.capture_step = sim.tracers, sim.tracer_status, sim.capture_step
             if log:
                 for k, s in enumerate(st):
                     log(f"Step: {k}, Div(u*): {s.max_div_star:.2e}, Final Div(u): {s.max_final_div:.2e}, "
