@@ -132,7 +132,15 @@ enum pucfem_field {
   /* capture steps (n_tr) as doubles, read only: the 1-based tracer step (counted since the tracers were last set)
      in which the tracer's status first became 1, -1 while it is uncaptured.  Setting TRACERS resets them (and the
      step count) as it clears the status; setting STATUS leaves them alone. */
-  PUCFEM_F_CAPTURE_STEP = 11
+  PUCFEM_F_CAPTURE_STEP = 11,
+  /* vorticity w (N) of the current u, read only (setting it is PUCFEM_EINVAL): calculate_vorticity
+     (scripts/good_visualization2.py:310-345), w = (Gx u_y - Gy u_x) / (area_sum + 1e-12), formed on the device when
+     read, as DIV_STAR is formed from u*.  It is the divergence kernel applied to (u_y, -u_x) with the swap made in
+     registers, so its bits are those of PUCFEM_OP_DIV on that rotated field (which the reference's
+     calculate_vorticity equals bit for bit on the host).  Stokes contexts, else PUCFEM_ESTATE.  On a multi-rank
+     context pucfem_get_field serves the rank's owned rows, as for FINAL_DIV; it is not collective: every call that
+     writes u leaves its ghost values current. */
+  PUCFEM_F_VORTICITY = 12
 };
 
 /* operators for pucfem_apply / pucfem_solve / pucfem_host_get_csr */
@@ -147,7 +155,9 @@ enum pucfem_op {
   PUCFEM_OP_LIT = 7,    /* literal heat operator I + DT*A (heatEq.py:305) or Poisson A (poisson.py:253-278) */
   PUCFEM_OP_MCONS = 8,  /* consistent mass of the implicit dye variant (StokesColor.py:286-312; host CSR only) */
   PUCFEM_OP_MLUMP = 9,  /* lumped mass M (StokesColor.py:266-284) as a diagonal (host CSR only) */
-  PUCFEM_OP_ASUM = 10   /* area_sum of calculate_divergence (StokesColor.py:151-163) as a diagonal (host CSR only) */
+  PUCFEM_OP_ASUM = 10,  /* area_sum of calculate_divergence (StokesColor.py:151-163) as a diagonal (host CSR only) */
+  PUCFEM_OP_CURL = 11   /* calculate_vorticity (scripts/good_visualization2.py:310-345): x = u (N,2), y = w (N);
+                           pucfem_apply only, on PUCFEM_OP_DIV's path and with its refusals */
 };
 
 /* ---- library / context ---------------------------------------------------------- */
@@ -215,8 +225,9 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats /* nsteps en
    (StokesColor.py:482-483), c = 1[x < 0.5] (:493-495), the context's current tracers with status 0. */
 int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values);
 int pucfem_ens_destroy(void* ctx);
-/* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS (and, read only, _CAPTURE_STEP) in the caller's
-   numbering; member = -1: all members, member-major (count = members x the field's values per member).  Setting
+/* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS (and, read only, _CAPTURE_STEP and _VORTICITY, the
+   latter formed from the members' u when read into a buffer of the ensemble's own) in the caller's numbering;
+   member = -1: all members, member-major (count = members x the field's values per member).  Setting
    TRACERS clears the status, the capture steps and the step count of the members it sets. */
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count);
 int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, int64_t count);
@@ -239,7 +250,8 @@ int pucfem_ens_info(void* ctx, int64_t* out4);
    (StokesColor.py:374-386).  A point on a shared edge or vertex so has one answer.  PointLocator's restriction
    to the 10 nearest centroids (StokesColor.py:324) is NOT applied: a sampler wants containment.  Where no
    triangle passes (outside [0,1]^2, inside the swimmer, a non-finite q) the value is NaN and the triangle -1.
-   Fields: PUCFEM_F_U and _USTAR (2 components: x then y), _P, _P2, _DIV_STAR, _DIV_U, _FINAL_DIV, _C (1 each);
+   Fields: PUCFEM_F_U and _USTAR (2 components: x then y), _P, _P2, _DIV_STAR, _DIV_U, _FINAL_DIV, _C, _VORTICITY
+   (1 each);
    at most 16 components per call.  Single-rank STOKES_COLOR / STOKES_FOOD contexts after pucfem_build_operators,
    else PUCFEM_ESTATE (heat / Poisson contexts have no locator; a multi-rank context's fields are partitioned);
    PUCFEM_ENODEV on a host-only context; PUCFEM_EINVAL for another field, nfields < 1, a non-positive size, a
@@ -257,11 +269,24 @@ int pucfem_sample_points(void* ctx, int32_t nfields, const int32_t* fields, int6
 int pucfem_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t width, int32_t height,
                   const double* window4 /* x0 y0 x1 y1, NULL = 0 0 1 1 */, float* out);
 /* The same image of every member of the context's ensemble (README.md:43-45: the swimmers side by side), each
-   pixel located once for all members; fields PUCFEM_F_U, _USTAR, _P, _P2, _C; member = -1: all members,
+   pixel located once for all members; fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _VORTICITY (formed from the members'
+   u into an ensemble-owned buffer, allocated at first use and kept); member = -1: all members,
    out [member][component][height][width], else that member's [component][height][width].  PUCFEM_ESTATE without
    an ensemble. */
 int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t member /* -1 = all */,
                       int32_t width, int32_t height, const double* window4, float* out);
+
+/* Flow summaries of the current u, reduced on the device in the pass that forms the vorticity (one launch, 32 bytes
+   copied back): the scalars one plots against the swimmer's B2 -- how much it stirs and how much it moves.  With
+   w_i the vorticity (PUCFEM_F_VORTICITY) and wt_i = area_sum_i + 1e-12 its row's denominator (the lumped mass to
+   1e-12 absolute) over all N nodes:
+     out[0] = max |w|,  out[1] = 1/2 sum wt w^2 (enstrophy),  out[2] = 1/2 sum wt |u|^2 (kinetic energy),
+     out[3] = sqrt(max |u|^2) (peak speed).
+   member = -1: the context's own run; otherwise that member of its ensemble (PUCFEM_ESTATE without one).  The sums
+   are taken in a fixed order: two calls without a step in between return identical bits, and a member's values are
+   those of a single run with its boundary values.  Changes no state of the context or its ensemble.  Single-rank
+   Stokes contexts after pucfem_build_operators, else PUCFEM_ESTATE; PUCFEM_ENODEV on a host-only context. */
+int pucfem_flow_info(void* ctx, int32_t member, double* out4);
 
 /* ---- unit operations (reference-named shims and parity tests) --------------------- */
 int pucfem_apply(void* ctx, int32_t op, const double* x, double* y);

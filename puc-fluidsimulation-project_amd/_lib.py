@@ -18,7 +18,9 @@ LIBNAME = "libpucfem.so"
 STOKES_COLOR, STOKES_FOOD, HEAT, POISSON = 0, 1, 2, 3
 F_U, F_USTAR, F_P, F_P2, F_DIV_STAR, F_DIV_U, F_FINAL_DIV, F_C, F_SCALAR, F_TRACERS, F_STATUS = range(11)
 F_CAPTURE_STEP = 11
+F_VORTICITY = 12
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
+OP_CURL = 11
 HOST_ONLY = -1
 ERRORS = {-1: "EINVAL", -2: "EHIP", -3: "ENOCONV", -4: "ESTATE", -5: "ENCCL", -6: "ENOMEM", -7: "ENODEV"}
 
@@ -86,6 +88,7 @@ SIGNATURES = {
     "pucfem_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
     "pucfem_ens_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
     "pucfem_raster_probe": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _D], ct.c_int),
+    "pucfem_flow_info": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_apply": ([_P, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_solve": ([_P, ct.c_int32, _D, _D, ct.c_double, ct.c_int32, _I32], ct.c_int),
     "pucfem_sl_advect": ([_P, _D, _D, ct.c_double, _D, _I32], ct.c_int),

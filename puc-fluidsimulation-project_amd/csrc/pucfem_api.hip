@@ -142,6 +142,10 @@ struct Ens {
   int32_t* trcap = nullptr;   // capture steps (M x ntr, -1: not captured)
   int32_t* trstep = nullptr;  // per member: tracer steps since its tracers were set
   double* part_tr = nullptr;  // k_ens_tracer_cloud's partials
+  // vorticity and flow summaries (k_ens_curl), allocated at first use and kept: the members' vorticity (M x n), its
+  // partials (M x 4 nb_div), the reduced values (M x ENS_VALS, slots 0..3) and the launch's ticket counters (M)
+  double *vort = nullptr, *part_curl = nullptr, *flow = nullptr;
+  unsigned* cnt_curl = nullptr;
   int nb_tr = 1;              // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
@@ -553,8 +557,9 @@ struct Ctx {
   // pucfem_sample_points / pucfem_raster / pucfem_ens_raster (pucfem_sample.hpp): device buffers allocated at a
   // call's first need and kept (grown when a later call needs more).  Slot 0 the points, 1 the output, 2 the
   // triangle ids, 3 the probe's counters, 4.. the fields that are formed when read (p / p2 kept in y, div u*,
-  // the final divergence): the samplers form them here and write no field of the context
-  static constexpr int SMP_SLOTS = 8;
+  // the final divergence, 8 the vorticity): the samplers form them here and write no field of the context.
+  // Slot 9: the partials of the vorticity pass (4 x MAXB) and, behind them, pucfem_flow_info's four reduced values
+  static constexpr int SMP_SLOTS = 10;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -1009,7 +1014,7 @@ struct Ctx {
   // write-through partial store and returned ticket (two memory round trips in the block's tail) cost
   // 10-25 us per producer launch, more than the 9-14 us k_reduce launch they remove.
   enum { CNT_VCHEB, CNT_INIT, CNT_RZ, CNT_DIR, CNT_UPD, CNT_DIV, CNT_MDOT, CNT_MIX, CNT_SL, CNT_TRACER,
-         CNT_DYE_DIV = 16, CNT_DYE_SL, CNT_DYE_MIX, CNT_N = 32 };
+         CNT_DYE_DIV = 16, CNT_DYE_SL, CNT_DYE_MIX, CNT_FLOW, CNT_N = 32 };
   unsigned* dcnt = nullptr;
   bool fused_red = std::getenv("PUCFEM_FUSED_RED") && std::atoi(std::getenv("PUCFEM_FUSED_RED")) != 0;
   RedOut ro(double* out, int cnt, int nv, int stride = MAXB, unsigned maxmask = 0u, double* out1 = nullptr) const {
@@ -2273,6 +2278,20 @@ struct Ctx {
               k_div<decltype(c16)::value, true>, dim3(div_grid()), dim3(BS), dP.view(), fc, (const double*)dGx,
               (const double*)dGy, ax, ay, (const double*)das1, out, (const double*)dmp, -(1.0 / prm.dt),
               rhs ? braw : (double*)nullptr, part ? part : part_d, r);
+    });
+    KCHK();
+  }
+  // k_div<CURL> on the interleaved velocity a (pucfem.h: PUCFEM_F_VORTICITY, pucfem_flow_info): the vorticity into
+  // out (null: not stored) and the flow partials into flow_part(), with the |u|^2 pair when energy; r reduces them
+  // in the launch.  Formed when read, outside the step: no kernel class, no counters, no step buffer written.
+  double* flow_part() { return smp_scratch<double>(9, 4 * MAXB + 4); }
+  void curl(const double* a, double* out, bool energy, RedOut r = RedOut{}) {
+    const FaceDev fc = fK.part();
+    double* part = flow_part();
+    with_c16(dP, [&](auto c16) {
+      hipLaunchKernelGGL((k_div<decltype(c16)::value, true, true>), dim3(div_grid()), dim3(BS), 0, st, dP.view(), fc,
+                         (const double*)dGx, (const double*)dGy, a, (const double*)nullptr, (const double*)das1, out,
+                         energy ? a : (const double*)nullptr, 0.0, (double*)nullptr, part, r);
     });
     KCHK();
   }
@@ -4886,6 +4905,14 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
           c.div(c.ux, c.uy, c.final_div, false);
         get1(c.final_div);
         break;
+      case PUCFEM_F_VORTICITY: {  // from u when read; the owned rows (u's ghosts are current after every write of u)
+        if (c.scheme != PUCFEM_STOKES_COLOR && c.scheme != PUCFEM_STOKES_FOOD)
+          throw Error(PUCFEM_ESTATE, "vorticity needs a Stokes context");
+        double* s = c.smp_scratch<double>(8, (size_t)c.nloc);
+        c.curl(c.ux, s, false);
+        get1(s);
+        break;
+      }
       case PUCFEM_F_SCALAR: get1(c.scalar); break;
       case PUCFEM_F_C: {
         require(count == N, "c is (N,)");
@@ -5166,6 +5193,30 @@ void ens_enqueue_step(Ctx& c) {
   hipLaunchKernelGGL(k_ens_record, dim3((M + 255) / 256), dim3(256), 0, st, M, (const double*)e.vals, e.ring, e.count);
   KCHK();
 }
+// the ensemble's vorticity buffers, allocated at first use and kept
+void ens_flow_bufs(Ctx& c, Ens& e) {
+  if (e.vort) return;
+  const size_t sM = (size_t)e.M;
+  e.vort = e.alloc<double>(sM * e.n, c.st);
+  e.part_curl = e.alloc<double>(sM * 4 * e.nb_div, c.st);
+  e.flow = e.alloc<double>(sM * ENS_VALS, c.st);
+  e.cnt_curl = e.alloc<unsigned>(sM, c.st);
+}
+// k_ens_curl over members m0 .. m0 + nm - 1 of the current u: the vorticity into e.vort (store) and the flow values
+// into slots 0..3 of the members' e.flow (energy: with the |u|^2 pair).  Writes only those buffers.
+void ens_curl(Ctx& c, Ens& e, int32_t m0, int32_t nm, bool store, bool energy) {
+  ens_flow_bufs(c, e);
+  const DevSell& A = c.dP;
+  const size_t m = (size_t)m0;
+  const RedOut r{e.flow + m * ENS_VALS, nullptr, e.cnt_curl + m, 4, 0, 0b1001u};
+  with_c16(A, [&](auto c16) {
+    hipLaunchKernelGGL(k_ens_curl<decltype(c16)::value>, dim3(e.nb_div, nm), dim3(BS), 0, c.st, A.view(),
+                       (const double*)c.dGx, (const double*)c.dGy, (const double*)(e.u + m * 2 * e.n),
+                       (const double*)c.das1, store ? e.vort + m * e.n : (double*)nullptr, energy ? 1 : 0,
+                       e.part_curl + m * 4 * e.nb_div, r);
+  });
+  KCHK();
+}
 // field -> (device array, values per member, per-row components: 2 interleaved, 1 plain, 0 not row-indexed)
 struct EnsField {
   double* a;
@@ -5179,10 +5230,13 @@ EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
     case PUCFEM_F_P: return {e.p, e.n, 1};
     case PUCFEM_F_P2: return {e.p2, e.n, 1};
     case PUCFEM_F_C: return {e.c, e.n, 1};
+    case PUCFEM_F_VORTICITY: ens_flow_bufs(c, e); return {e.vort, e.n, 1};  // (read only; ens_curl fills it)
     case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
     case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
     case PUCFEM_F_CAPTURE_STEP: return {nullptr, (i64)e.ntr, 0};
-    default: throw Error(PUCFEM_EINVAL, "not an ensemble field (U, USTAR, P, P2, C, TRACERS, STATUS, CAPTURE_STEP)");
+    default:
+      throw Error(PUCFEM_EINVAL,
+                  "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, TRACERS, STATUS, CAPTURE_STEP)");
   }
 }
 }  // namespace
@@ -5309,6 +5363,7 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     Ens& e = *ens_of(c);
     require(member >= -1 && member < e.M, "member index out of range");
     require(field != PUCFEM_F_CAPTURE_STEP, "capture steps cannot be set");
+    require(field != PUCFEM_F_VORTICITY, "the vorticity cannot be set");
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
@@ -5365,6 +5420,7 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
       }
       return;
     }
+    if (field == PUCFEM_F_VORTICITY) ens_curl(c, e, (int32_t)m0, (int32_t)nm, true, false);
     std::vector<double> x((size_t)(nm * f.per));
     HIPCHK(hipMemcpyAsync(x.data(), f.a + m0 * f.per, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
     HIPCHK(hipStreamSynchronize(c.st));
@@ -5510,7 +5566,14 @@ SampleFields sample_fields(Ctx& c, int32_t nfields, const int32_t* fields) {
         }
         break;
       case PUCFEM_F_C: sample_push(F, c.c_full, 1, 0); break;
-      default: throw Error(PUCFEM_EINVAL, "not a sampled field (U, USTAR, P, P2, DIV_STAR, DIV_U, FINAL_DIV, C)");
+      case PUCFEM_F_VORTICITY: {  // from u, as pucfem_get_field computes it
+        double* s = c.smp_scratch<double>(8, (size_t)c.nloc);
+        c.curl(c.ux, s, false);
+        sample_push(F, s, 1, 0);
+        break;
+      }
+      default:
+        throw Error(PUCFEM_EINVAL, "not a sampled field (U, USTAR, P, P2, DIV_STAR, DIV_U, FINAL_DIV, C, VORTICITY)");
     }
   }
   return F;
@@ -5605,6 +5668,8 @@ int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t
       for (int q = 0; q < f.comp; ++q) sample_push(F, f.a + q, f.comp, f.per);
     }
     const int32_t m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+    if (std::find(fields, fields + nfields, (int32_t)PUCFEM_F_VORTICITY) != fields + nfields)
+      ens_curl(c, e, m0, nm, true, false);
     const size_t count = (size_t)nm * (size_t)F.ncomp * (size_t)p.plane;
     float* dout = c.smp_scratch<float>(1, count);
     hipLaunchKernelGGL(k_ens_raster<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles, F, m0,
@@ -5738,6 +5803,17 @@ int pucfem_apply(void* ctx, int32_t op, const double* x, double* y) {
         perm_out(y, 1, o0, nullptr);
         break;
       }
+      case PUCFEM_OP_CURL: {  // (the SoA form of the same kernel: no rotated copy of x)
+        perm_in(x, 2, t0, t1);
+        with_c16(c.dP, [&](auto c16) {
+          hipLaunchKernelGGL((k_div<decltype(c16)::value, false, true>), dim3(c.div_grid()), dim3(BS), 0, c.st,
+                             c.dP.view(), c.fK.part(), c.dGx, c.dGy, t0, t1, c.das1, o0, (const double*)nullptr, 0.0,
+                             (double*)nullptr, c.part_d, RedOut{});
+        });
+        KCHK();
+        perm_out(y, 1, o0, nullptr);
+        break;
+      }
       case PUCFEM_OP_GRAD: {
         perm_in(x, 1, t0, nullptr);
         with_c16(c.dP, [&](auto c16) {
@@ -5764,6 +5840,35 @@ int pucfem_apply(void* ctx, int32_t op, const double* x, double* y) {
       }
       default: throw Error(PUCFEM_EINVAL, "unknown op");
     }
+  });
+}
+
+int pucfem_flow_info(void* ctx, int32_t member, double* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.need_dev();
+    c.need_built();
+    if (c.scheme != PUCFEM_STOKES_COLOR && c.scheme != PUCFEM_STOKES_FOOD)
+      throw Error(PUCFEM_ESTATE, "flow summaries need a Stokes context");
+    if (c.dist()) throw Error(PUCFEM_ESTATE, "flow summaries are single-rank (a multi-rank context is partitioned)");
+    require(out4 != nullptr, "null output");
+    double h[4];
+    if (member < 0) {
+      require(member == -1, "member index out of range");
+      double* fp = c.flow_part();
+      const RedOut r{fp + 4 * MAXB, nullptr, c.dcnt + Ctx::CNT_FLOW, 4, MAXB, 0b1001u};
+      c.curl(c.ux, nullptr, true, r);
+      c.d2h(h, fp + 4 * MAXB, sizeof(h));
+    } else {
+      Ens& e = *ens_of(c);
+      require(member < e.M, "member index out of range");
+      ens_curl(c, e, member, 1, false, true);
+      c.d2h(h, e.flow + (size_t)member * ENS_VALS, sizeof(h));
+    }
+    out4[0] = h[0];
+    out4[1] = 0.5 * h[1];
+    out4[2] = 0.5 * h[2];
+    out4[3] = std::sqrt(h[3]);
   });
 }
 

@@ -24,14 +24,15 @@ constexpr int ENS_TM = 4;     // members per block of the dense products
 constexpr int ENS_VALS = 16;  // per-member value slots (k_stats' layout in 0..6; 8: scratch maximum, 9: sum(braw))
 
 // the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
-// (nv partial arrays of gridDim.x blocks per member)
+// (NP partial arrays of gridDim.x blocks per member)
+template <int NP = 3>
 __device__ __forceinline__ RedOut ens_red(const RedOut& ro, int32_t m, double*& part) {
   RedOut R = ro;
   R.out = ro.out + (int64_t)ENS_VALS * m;
   R.out1 = ro.out1 ? ro.out1 + (int64_t)ENS_VALS * m : nullptr;
   R.cnt = ro.cnt + m;
   R.stride = (int)gridDim.x;
-  part += (int64_t)m * 3 * gridDim.x;
+  part += (int64_t)m * NP * gridDim.x;
   return R;
 }
 
@@ -188,6 +189,62 @@ __global__ __launch_bounds__(BS) void k_ens_div(SellDev A, const double* __restr
     red_part(R, part, 1, v);
   }
   red_finish(R, part, sh);
+}
+
+// k_div<CURL> (SELL rows, interleaved velocity) per member: the vorticity of the member's u as the divergence of
+// (u_y, -u_x), in k_ens_div's operation order, and the four flow partials in the single path's order (max |w|,
+// sum wt w^2, sum wt |u|^2, max |u|^2 with wt = area_sum + 1e-12; the last two only with `energy`).
+// u: M x 2n, vort: M x n (or null), part: M x 4 gridDim.x.  gridDim.x: the single path's div grid.
+template <bool C16>
+__global__ __launch_bounds__(BS) void k_ens_curl(SellDev A, const double* __restrict__ gx, const double* __restrict__ gy,
+                                                 const double* __restrict__ u, const double* __restrict__ as1,
+                                                 double* __restrict__ vort, int energy, double* part, RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  const int64_t n = A.n_own;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  double* vm = vort ? vort + (int64_t)m * n : nullptr;
+  const RedOut R = ens_red<4>(ro, m, part);
+  double mx = 0.0, sb = 0.0, se = 0.0, mu = 0.0;
+  int64_t s0, s1;
+  block_slices_n(A.nslices, gridDim.x, blockIdx.x, s0, s1);
+  const int lane = threadIdx.x & 63, wv = wave_id();
+  for (int64_t s = s0 + wv; s < s1; s += 4) {
+    const int64_t off = A.off[s];
+    const int w = A.w[s];
+    const int64_t row = sell_row(A, s, lane);
+    const int32_t base = (int32_t)(s * 64);
+    double acc = 0.0;
+    for (int k = 0; k < w; ++k) {
+      const int64_t e = off + (int64_t)k * 64 + lane;
+      const dbl2 q = rot<true>(um[sell_col<C16, false>(A, e, base)]);
+      acc += gx[e] * q.x + gy[e] * q.y;
+    }
+    if (row >= 0) {
+      const double wt = as1[row];
+      const double d = acc / wt;
+      if (vm) vm[row] = d;
+      mx = fmax(mx, fabs(d));
+      sb += wt * (d * d);
+      if (energy) {
+        const dbl2 q = um[row];
+        const double q2 = q.x * q.x + q.y * q.y;
+        se += wt * q2;
+        mu = fmax(mu, q2);
+      }
+    }
+  }
+  const double t = block_max(mx, sh);
+  const double v = block_sum(sb, sh);
+  const double e = block_sum(se, sh);
+  const double x = block_max(mu, sh);
+  if (threadIdx.x == 0) {
+    red_part(R, part, 2, e);
+    red_part(R, part, 3, x);
+    red_part(R, part, 0, t);
+    red_part(R, part, 1, v);
+  }
+  red_finish<8>(R, part, sh);
 }
 
 // k_grad_proj_bc per member: the first projection with the velocity BCs.  p: M x n, us / u: M x 2n.

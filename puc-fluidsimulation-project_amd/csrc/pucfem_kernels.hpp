@@ -175,6 +175,10 @@ __device__ __forceinline__ double red_load(const double* p) {
 // (and, as every block must, with no early return before it).  sh: >= 4 doubles of LDS.
 // all_waves: partials were stored by several waves (each drains its stores before the barrier).
 // returns true in the block that reduced (the last one to finish), after its thread 0 stored the values
+// U > 1: the reducing block loads U partials per thread before it combines them, in the same order (i, i + BS, ...),
+// so the values are those of U = 1; the loads of a pass are then in flight together instead of one memory round
+// trip each (k_div<CURL>: 4 values over 15k blocks at L7)
+template <int U = 1>
 __device__ __forceinline__ bool red_finish(const RedOut& R, const double* part, double* sh, bool all_waves = false) {
   if (!R.out) return false;
   __shared__ int last;
@@ -197,9 +201,24 @@ __device__ __forceinline__ bool red_finish(const RedOut& R, const double* part, 
     const bool mx = (R.maxmask >> v) & 1u;
     const double* p = part + (int64_t)v * R.stride;
     double a = 0.0;
-    for (int i = threadIdx.x; i < nb; i += BS) {
-      const double x = red_load(p + i);
-      a = mx ? fmax(a, x) : a + x;
+    if constexpr (U > 1) {
+      int i = threadIdx.x;
+      for (; i + (U - 1) * BS < nb; i += U * BS) {
+        double x[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) x[k] = red_load(p + i + k * BS);
+#pragma unroll
+        for (int k = 0; k < U; ++k) a = mx ? fmax(a, x[k]) : a + x[k];
+      }
+      for (; i < nb; i += BS) {
+        const double x = red_load(p + i);
+        a = mx ? fmax(a, x) : a + x;
+      }
+    } else {
+      for (int i = threadIdx.x; i < nb; i += BS) {
+        const double x = red_load(p + i);
+        a = mx ? fmax(a, x) : a + x;
+      }
     }
     const double r = mx ? block_max(a, sh) : block_sum(a, sh);
     if (threadIdx.x == 0) {

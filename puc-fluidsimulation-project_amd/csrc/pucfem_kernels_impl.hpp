@@ -1628,13 +1628,26 @@ __global__ void k_visc_fin(int64_t n, const double* __restrict__ s, const dbl2* 
 }
 
 // ----------------------------------------------------------------------------- div / grad
+// the gathered velocity pair as k_div<CURL> reads it: (u_y, -u_x), the field whose divergence is the vorticity
+template <bool CURL>
+__device__ __forceinline__ dbl2 rot(dbl2 q) {
+  if constexpr (CURL) return dbl2{q.y, -q.x};
+  else return q;
+}
 // calculate_divergence (StokesColor.py:130-165) in operator form: div = (Gx ux + Gy uy) / (area_sum + 1e-12)
 // into div (null: only its max |div| partials -- the step's div(u*) and final div fields are computed when
 // read, pucfem_get_field).
 // Optionally the pressure RHS of the row-scaled system: braw = (M + 1e-12) * (-(1/DT) * div)
 // (StokesColor.py:554 with A_pressure = K / (M + 1e-12)).  Partials: [0] max|div|, [1] sum(braw).
 // AOS: ux points at interleaved (x, y) pairs (uy unused): one 16-B gather per neighbour
-template <bool C16, bool AOS = false>
+// CURL: the vorticity of calculate_vorticity (scripts/good_visualization2.py:310-345) instead, as the divergence of
+// the rotated field (u_y, -u_x): every gathered pair is swapped to {y, -x} right after its load and the arithmetic
+// after it is the divergence's, so w = (Gx uy - Gy ux) / (area_sum + 1e-12) has the bits of k_div on a rotated copy
+// of u, which is never formed.  div: w (null: not stored).  mp, AOS only: the interleaved velocity of the rows
+// themselves (ux again) for the energy partials, null: w alone (partials 2, 3 are 0); negidt, braw unused.
+// Partials, with the row's denominator wt = area_sum + 1e-12 as its weight: [0] max |w|, [1] sum wt w^2,
+// [2] sum wt |u|^2, [3] max |u|^2.
+template <bool C16, bool AOS = false, bool CURL = false>
 __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict__ gx,
                                             const double* __restrict__ gy, const double* __restrict__ ux,
                                             const double* __restrict__ uy, const double* __restrict__ as1,
@@ -1642,6 +1655,19 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
                                             double* __restrict__ braw, double* part, RedOut ro = RedOut{}) {
   __shared__ double sh[4];
   double mx = 0.0, sb = 0.0;
+  [[maybe_unused]] double se = 0.0, mu = 0.0;  // CURL: sum wt |u|^2, max |u|^2 (sb: sum wt w^2)
+  // CURL: the row's own partial terms from its value d and denominator wt
+  [[maybe_unused]] auto flow_row = [&](int64_t row, double d, double wt) {
+    sb += wt * (d * d);
+    if constexpr (AOS) {
+      if (mp) {
+        const dbl2 q = reinterpret_cast<const dbl2*>(mp)[row];
+        const double q2 = q.x * q.x + q.y * q.y;
+        se += wt * q2;
+        mu = fmax(mu, q2);
+      }
+    }
+  };
   const BlockRole role = block_role(fc.nb);
   if (role.face) {
     // interior rows: the lumped divergence of the face's stencil; area_sum = lumped mass there
@@ -1660,12 +1686,13 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
           if constexpr (AOS) {
-            const dbl2 q = reinterpret_cast<const dbl2*>(ux)[nb[k]];
+            const dbl2 q = rot<CURL>(reinterpret_cast<const dbl2*>(ux)[nb[k]]);
             vx[r][k] = q.x;
             vy[r][k] = q.y;
           } else {
-            vx[r][k] = ux[nb[k]];
-            vy[r][k] = uy[nb[k]];
+            const dbl2 q = rot<CURL>(dbl2{ux[nb[k]], uy[nb[k]]});
+            vx[r][k] = q.x;
+            vy[r][k] = q.y;
           }
         }
       }
@@ -1680,7 +1707,9 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
         const double d = (ax + by) / as;
         if (div) stnt(div + row, d);
         mx = fmax(mx, fabs(d));
-        if (braw) {
+        if constexpr (CURL) {
+          flow_row(row, d, as);
+        } else if (braw) {
           const double b = as * (negidt * d);
           stnt(braw + row, b);
           sb += b;
@@ -1712,7 +1741,10 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
 #pragma unroll
           for (int k = 0; k < WN; ++k) {
             if constexpr (AOS) {
-              const dbl2 q = reinterpret_cast<const dbl2*>(ux)[cj[k]];
+              const dbl2 q = rot<CURL>(reinterpret_cast<const dbl2*>(ux)[cj[k]]);
+              acc += ax[k] * q.x + ay[k] * q.y;
+            } else if constexpr (CURL) {
+              const dbl2 q = rot<CURL>(dbl2{ux[cj[k]], uy[cj[k]]});
               acc += ax[k] * q.x + ay[k] * q.y;
             } else {
               acc += ax[k] * ux[cj[k]] + ay[k] * uy[cj[k]];
@@ -1723,7 +1755,10 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
             const int64_t e = off + (int64_t)k * 64 + lane;
             const int32_t j = sell_col<C16>(A, e, base);
             if constexpr (AOS) {
-              const dbl2 q = reinterpret_cast<const dbl2*>(ux)[j];
+              const dbl2 q = rot<CURL>(reinterpret_cast<const dbl2*>(ux)[j]);
+              acc += ldnt(gx + e) * q.x + ldnt(gy + e) * q.y;
+            } else if constexpr (CURL) {
+              const dbl2 q = rot<CURL>(dbl2{ux[j], uy[j]});
               acc += ldnt(gx + e) * q.x + ldnt(gy + e) * q.y;
             } else {
               acc += ldnt(gx + e) * ux[j] + ldnt(gy + e) * uy[j];
@@ -1735,7 +1770,9 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
         const double d = acc / as1[row];
         if (div) stnt(div + row, d);
         mx = fmax(mx, fabs(d));
-        if (braw) {
+        if constexpr (CURL) {
+          flow_row(row, d, as1[row]);
+        } else if (braw) {
           const double b = mp[row] * (negidt * d);
           stnt(braw + row, b);
           sb += b;
@@ -1745,11 +1782,20 @@ __global__ LB_GATHER void k_div(SellDev A, FaceDev fc, const double* __restrict_
   }
   const double t = block_max(mx, sh);
   const double u = block_sum(sb, sh);
+  if constexpr (CURL) {
+    const double e = block_sum(se, sh);
+    const double m = block_max(mu, sh);
+    if (threadIdx.x == 0) {
+      red_part(ro, part, 2, e);
+      red_part(ro, part, 3, m);
+    }
+  }
   if (threadIdx.x == 0) {
     red_part(ro, part, 0, t);
     red_part(ro, part, 1, u);
   }
-  red_finish(ro, part, sh);
+  if constexpr (CURL) red_finish<8>(ro, part, sh);
+  else red_finish(ro, part, sh);
 }
 
 // pressure RHS of the merged, range-projected, scaled system (oracle PressureSolver.rhs):

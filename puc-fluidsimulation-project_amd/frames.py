@@ -28,9 +28,13 @@ class FrameRecorder:
     raster=(W, H): record W x H images instead of the nodal fields -- ``sim.raster`` rasterises the dye and the
     velocity of `window` = (x0, y0, x1, y1) (None: the unit square) on the device, so a frame costs its pixels
     at any mesh size and the fields are never copied.  ``dye`` then holds float32 (H, W) images and ``vel``
-    (2, H, W) ones (row 0 the lowest y, NaN inside the swimmer)."""
+    (2, H, W) ones (row 0 the lowest y, NaN inside the swimmer).
 
-    def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None):
+    vorticity=True: each frame also appends the vorticity to ``vort`` -- the reference's second panel
+    (scripts/good_visualization.py:578-584), formed on the device: the (H, W) raster of "vorticity" in raster
+    mode, else the nodal field ``sim.vorticity``."""
+
+    def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None, vorticity=False):
         self.mesh = mesh
         self.interval = int(interval)
         self.dtype = dtype
@@ -39,20 +43,27 @@ class FrameRecorder:
         self.steps: list[int] = []
         self.dye: list[np.ndarray] = []
         self.vel: list[np.ndarray] = []
+        self.vorticity = bool(vorticity)
+        self.vort: list[np.ndarray] = []
 
-    def record(self, step, c, u):
+    def record(self, step, c, u, vort=None):
         self.steps.append(int(step))
         self.dye.append(np.array(c, dtype=self.dtype, copy=True) if c is not None else None)
         self.vel.append(np.array(u, dtype=self.dtype, copy=True))
+        if vort is not None:
+            self.vort.append(np.array(vort, dtype=self.dtype, copy=True))
 
     def record_raster(self, step, sim):
         """One raster frame of `sim` (its dye only under scheme 'color')."""
         W, H = self.raster
         color = sim.scheme == "color"
-        img = sim.raster(W, H, fields=("c", "u") if color else ("u",), window=self.window)
+        fields = (("c", "u") if color else ("u",)) + (("vorticity",) if self.vorticity else ())
+        img = sim.raster(W, H, fields=fields, window=self.window)
         self.steps.append(int(step))
         self.dye.append(np.asarray(img["c"], dtype=np.float32) if color else None)
         self.vel.append(np.asarray(img["u"], dtype=np.float32))
+        if self.vorticity:
+            self.vort.append(np.asarray(img["vorticity"], dtype=np.float32))
 
     def run(self, sim, steps):
         """Step `sim` (a StokesSimulation) `steps` times, recording the state after every step whose
@@ -69,7 +80,8 @@ class FrameRecorder:
                 if self.raster is not None:
                     self.record_raster(r, sim)
                 else:
-                    self.record(r, sim.c if sim.scheme == "color" else None, sim.u)
+                    self.record(r, sim.c if sim.scheme == "color" else None, sim.u,
+                                sim.vorticity if self.vorticity else None)
         return stats
 
     def __len__(self):
@@ -78,7 +90,8 @@ class FrameRecorder:
 
 def save_npz(rec: FrameRecorder, path):
     """The raw frames.  Raster frames: `vel` (frames, 2, H, W), `dye` (frames, H, W) and `window`
-    (x0, y0, x1, y1) instead of the mesh."""
+    (x0, y0, x1, y1) instead of the mesh.  A recorder with vorticity frames adds `vort` (frames, H, W) or
+    (frames, N)."""
     if getattr(rec, "raster", None) is not None:
         W, H = rec.raster
         d = dict(steps=np.array(rec.steps), window=np.array(rec.window or (0.0, 0.0, 1.0, 1.0), dtype=np.float64),
@@ -88,6 +101,8 @@ def save_npz(rec: FrameRecorder, path):
                  vel=np.stack(rec.vel) if rec.vel else np.zeros((0, rec.mesh.N, 2)))
     if rec.dye and rec.dye[0] is not None:
         d["dye"] = np.stack(rec.dye)
+    if getattr(rec, "vort", None):
+        d["vort"] = np.stack(rec.vort)
     np.savez_compressed(path, **d)
 
 
@@ -167,7 +182,9 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     velocity, good_visualization2.py:536-571).  out ending in .mp4 uses ffmpeg (if installed), .gif
     Pillow; a directory name writes frame_00000.png ...  Returns the written path(s).
     Raster frames are drawn with imshow (magma, [0, 1], origin lower, the window as extent) under a quiver
-    of every `skip`-th pixel's velocity."""
+    of every `skip`-th pixel's velocity.  With vorticity frames (``rec.vort``) a second panel beside it shows them
+    as the reference does (good_visualization.py:578-584: coolwarm, limits symmetric about 0 at the largest
+    |vorticity| of the frames)."""
     import matplotlib
 
     matplotlib.use("Agg")
@@ -175,7 +192,12 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     import matplotlib.tri as mtri
     from matplotlib import animation
 
-    fig, ax = plt.subplots(figsize=(8, 8))
+    vort = getattr(rec, "vort", None) or None
+    if vort:
+        fig, (ax, ax2) = plt.subplots(1, 2, figsize=(16, 8))
+        vmax = max(float(np.nanmax(np.abs(v))) for v in vort) + 1e-9
+    else:
+        fig, ax = plt.subplots(figsize=(8, 8))
     if getattr(rec, "raster", None) is not None:
         # raster frames: the dye image under a quiver of the velocity image on a coarse pixel stride; the
         # swimmer's NaN pixels stay transparent (the axes' grey shows) and carry no arrows
@@ -196,6 +218,10 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
         qv = ax.quiver(*np.meshgrid(px, py), *arrows(0), color="white", scale=20.0)
         ax.set_xlim(x0, x1)
         ax.set_ylim(y0, y1)
+        if vort:
+            ax2.set_facecolor("0.5")
+            tpv = ax2.imshow(vort[0], cmap="coolwarm", vmin=-vmax, vmax=vmax, origin="lower", extent=(x0, x1, y0, y1),
+                             interpolation="nearest")
     else:
         X, T = rec.mesh.coords, rec.mesh.triangles
         skip = skip or max(1, len(X) // 1500)
@@ -206,6 +232,10 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
                        scale=20.0)
         ax.set_xlim(0, 1)
         ax.set_ylim(0, 1)
+        if vort:
+            tpv = ax2.tripcolor(tri, vort[0], shading="gouraud", cmap="coolwarm", vmin=-vmax, vmax=vmax)
+            ax2.set_xlim(0, 1)
+            ax2.set_ylim(0, 1)
 
         def arrows(i):
             return rec.vel[i][::skip, 0], rec.vel[i][::skip, 1]
@@ -213,11 +243,17 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     fig.colorbar(tpc, ax=ax, label="Dye concentration")
     ax.set_aspect("equal")
     title = ax.set_title(f"Fluid Simulation - Step {rec.steps[0]}")
+    if vort:
+        fig.colorbar(tpv, ax=ax2, label="Vorticity")
+        ax2.set_aspect("equal")
+        ax2.set_title("Vorticity (Flow Curl)")
 
     def update(i):
         if rec.dye[i] is not None:
             tpc.set_array(rec.dye[i])
         qv.set_UVC(*arrows(i))
+        if vort:
+            tpv.set_array(vort[i])
         title.set_text(f"Fluid Simulation - Step {rec.steps[i]}")
         return tpc, qv, title
 

@@ -132,6 +132,12 @@ def calculate_divergence(nodes, triangles, u_star):
     return ctx.apply(_lib.OP_DIV, np.asarray(u_star, dtype=np.float64).reshape(-1, 2), (len(nodes),))
 
 
+def calculate_vorticity(nodes, triangles, u):
+    """scripts/good_visualization2.py:310-345 on the GPU: (N,) lumped nodal vorticity d(u_y)/dx - d(u_x)/dy."""
+    ctx = context_for(nodes, triangles)
+    return ctx.apply(_lib.OP_CURL, np.asarray(u, dtype=np.float64).reshape(-1, 2), (len(nodes),))
+
+
 def calculate_gradiant(nodes, triangles, p_scalar):
     """StokesColor.py:224-263 on the GPU: (grad_px, grad_py)."""
     ctx = context_for(nodes, triangles)

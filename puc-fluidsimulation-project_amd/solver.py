@@ -19,7 +19,8 @@ SCHEMES = {"color": _lib.STOKES_COLOR, "food": _lib.STOKES_FOOD, "heat": _lib.HE
 # fields of pucfem_sample_points / pucfem_raster by name: (enum, components)
 SAMPLE_FIELDS = {"u": (_lib.F_U, 2), "u_star": (_lib.F_USTAR, 2), "p": (_lib.F_P, 1), "p2": (_lib.F_P2, 1),
                  "div_star": (_lib.F_DIV_STAR, 1), "div_u": (_lib.F_DIV_U, 1), "final_div": (_lib.F_FINAL_DIV, 1),
-                 "c": (_lib.F_C, 1)}
+                 "c": (_lib.F_C, 1), "vorticity": (_lib.F_VORTICITY, 1)}
+FLOW_KEYS = ("max_vorticity", "enstrophy", "kinetic_energy", "max_speed")
 _SAMPLE_NCOMP = {f: n for f, n in SAMPLE_FIELDS.values()}
 
 
@@ -258,7 +259,7 @@ class Context:
         """Fields at arbitrary points on the device (pucfem_sample_points; StokesFood.py:482-487's locate and
         interpolate): ({field: (n,) or (n, 2) float64}, triangle ids (n,) int32, -1 where no triangle holds the
         point and the values are NaN).  fields: names ("u", "u_star", "p", "p2", "div_star", "div_u", "final_div",
-        "c") or pucfem_field values; points (n, 2), taken as given (no periodic wrap)."""
+        "c", "vorticity") or pucfem_field values; points (n, 2), taken as given (no periodic wrap)."""
         names, ids, ncomp = _sample_spec(fields)
         P = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
         n = P.shape[0]
@@ -356,6 +357,14 @@ class Context:
         o = (ct.c_int64 * 6)()
         self._c(self.L.pucfem_tracer_info(self.h, -1 if member is None else int(member), o))
         return dict(tracers=o[0], eaten=o[1], nonfinite=o[2], steps=o[3], blocks=o[4], threads=o[5])
+
+    def flow_info(self, member=None):
+        """Flow summaries of the current u, reduced on the device (pucfem_flow_info; one launch, four doubles
+        copied): max |vorticity|, the enstrophy 1/2 sum w vorticity^2, the kinetic energy 1/2 sum w |u|^2 and the
+        peak speed, with w = area_sum + 1e-12 per node.  member: that member of the context's ensemble."""
+        o = (ct.c_double * 4)()
+        self._c(self.L.pucfem_flow_info(self.h, -1 if member is None else int(member), o))
+        return dict(zip(FLOW_KEYS, (float(v) for v in o)))
 
     def comm_info(self):
         """Multi-rank data flow of the last step (pucfem_comm_info)."""
@@ -496,6 +505,16 @@ class StokesSimulation:
 
     def field(self, f, ncomp=1):
         return self.ctx.get_field(f, (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,))
+
+    @property
+    def vorticity(self):
+        """(N,) calculate_vorticity (scripts/good_visualization2.py:310-345) of the current u, formed on the device
+        when read."""
+        return self.ctx.get_field(_lib.F_VORTICITY, (self.mesh.N,))
+
+    def flow_info(self):
+        """Context.flow_info of this run."""
+        return self.ctx.flow_info()
 
     def sample(self, points, fields=("u", "c")):
         """The fields at arbitrary points (Context.sample): ({field: values}, triangle ids)."""
@@ -653,6 +672,16 @@ class StokesEnsemble:
         self.set(_lib.F_C, v)
 
     @property
+    def vorticity(self):
+        """(M, N): every member's vorticity, formed on the device when read."""
+        return self.get(_lib.F_VORTICITY)
+
+    def flow_info(self):
+        """Context.flow_info of every member (one call each): {name: (M,) array}."""
+        rows = [self.ctx.flow_info(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in FLOW_KEYS}
+
+    @property
     def tracers(self):
         return self.get(_lib.F_TRACERS)
 
@@ -679,7 +708,7 @@ class StokesEnsemble:
     def raster(self, width, height, fields=("c", "u"), window=None, member=None):
         """Every member's fields as images (pucfem_ens_raster: the swimmers side by side, each pixel located once
         for all members): {name: float32 (M, height, width) or (M, 2, height, width)}; member = m: that member's
-        images without the leading axis.  Fields "u", "u_star", "p", "p2", "c"."""
+        images without the leading axis.  Fields "u", "u_star", "p", "p2", "c", "vorticity"."""
         names, ids, ncomp = _sample_spec(fields)
         w, wp = _window(window)
         nm = self.M if member is None else 1
