@@ -276,6 +276,58 @@ int pucfem_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t wid
 int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t member /* -1 = all */,
                       int32_t width, int32_t height, const double* window4, float* out);
 
+/* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
+/* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,
+   good_visualization.py:738).  These calls integrate the context's current u from caller-given seeds with the
+   samplers' locate and interpolation, the whole loop of a line in one kernel thread.
+   Locating a point p: T(p) is the triangle pucfem_sample_points finds (above); V(p) = (u_x, u_y) interpolated on
+   it; "none" when no triangle passes.  The direction D(v): with ax = |vx|, ay = |vy| the line is stagnant when
+   !(ax > vmin || ay > vmin); else d = v (time mode), or with PUCFEM_SLN_UNIT d = (vx / m, vy / m),
+   m = ax > ay ? ax : ay -- the max norm on purpose: the same curve re-parameterised with a step between |h| and
+   sqrt(2) |h|, from a correctly rounded division alone.  One line, from the seed q0 with the signed step h:
+     p = q0 (as given: no wrap, no clamp);  T(p) none: status SEED_OUTSIDE, npts 0, stop;  store p as point 0
+     for s = 1 .. nsteps:
+       d = D(V(p));                                             stagnant: status STAGNANT, stop
+       midpoint (default): q = (mod1(p.x + (0.5 * h) * d.x), p.y + (0.5 * h) * d.y)
+                           T(q) none: status LEFT, stop;  d = D(V(q));  stagnant: status STAGNANT, stop
+       pn = (mod1(p.x + h * d.x), p.y + h * d.y);               T(pn) none: status LEFT, stop (pn is not stored)
+       p = pn;  store p as point s
+     status COMPLETE when all nsteps were taken
+   with every product and sum as written (unfused fp64) and mod1 numpy's x % 1.0: only x wraps, the walls are at
+   y = 0 and y = 1, and every stored point lies in a triangle.  PUCFEM_SLN_EULER takes one stage per step (the
+   tracer step's integrator).  PUCFEM_SLN_BOTH: lines = 2 * nseeds, line e < nseeds runs with +h and line
+   nseeds + e with -h; otherwise lines = nseeds.
+   Outputs, step-major: points[(s * lines + e) * 2 + {0, 1}], s = 0 .. nsteps, NaN past the end of a line;
+   status[e]: 0 COMPLETE, 1 LEFT, 2 STAGNANT, 3 SEED_OUTSIDE;  npts[e]: the points stored;
+   values[(k * (nsteps + 1) + s) * lines + e]: component k of `fields` (those of pucfem_sample_points, at most 16
+   components) at stored point s -- what pucfem_sample_points returns there -- NaN past the end.
+   Readiness and refusals are the samplers'.  PUCFEM_EINVAL also for nseeds < 1, nsteps < 1, h zero or not finite,
+   vmin negative or not finite, unknown flag bits, values given without fields or the reverse, or more than 2^26
+   stored points ((nsteps + 1) * lines * members: 1 GiB of output).  The calls run on the context's stream after
+   everything pending on it and change no state of the context or its ensemble. */
+enum pucfem_streamline_flag { PUCFEM_SLN_UNIT = 1, PUCFEM_SLN_EULER = 2, PUCFEM_SLN_BOTH = 4 };
+enum pucfem_streamline_status {
+  PUCFEM_SLN_COMPLETE = 0,
+  PUCFEM_SLN_LEFT = 1,
+  PUCFEM_SLN_STAGNANT = 2,
+  PUCFEM_SLN_SEED_OUTSIDE = 3
+};
+int pucfem_streamlines(void* ctx, int64_t nseeds, const double* seeds /* nseeds x 2 */, double h, int32_t nsteps,
+                       int32_t flags, double vmin, int32_t nfields, const int32_t* fields /* may be 0 / NULL */,
+                       double* points, int32_t* status, int32_t* npts, double* values /* NULL iff nfields == 0 */);
+/* Measurement: the kernel of the call above without fields, launched once untimed and then `iters` times back to
+   back between two events, the outputs left on the device.  out2[0]: milliseconds per launch; out2[1]: the bytes
+   of its outputs. */
+int pucfem_streamlines_probe(void* ctx, int64_t nseeds, const double* seeds, double h, int32_t nsteps, int32_t flags,
+                             double vmin, int32_t iters, double* out2);
+/* The same lines in every member of the context's ensemble (the neutral swimmer, the pusher and the puller side by
+   side): each member locates for itself, since the velocities differ.  member = -1: all members, the outputs
+   member-major (points [member][step][line][2], status and npts [member][line]); else that member's alone.
+   PUCFEM_ESTATE without an ensemble. */
+int pucfem_ens_streamlines(void* ctx, int32_t member /* -1 = all, member-major */, int64_t nseeds,
+                           const double* seeds, double h, int32_t nsteps, int32_t flags, double vmin,
+                           double* points, int32_t* status, int32_t* npts);
+
 /* Flow summaries of the current u, reduced on the device in the pass that forms the vorticity (one launch, 32 bytes
    copied back): the scalars one plots against the swimmer's B2 -- how much it stirs and how much it moves.  With
    w_i the vorticity (PUCFEM_F_VORTICITY) and wt_i = area_sum_i + 1e-12 its row's denominator (the lumped mass to

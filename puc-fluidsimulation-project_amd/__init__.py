@@ -15,8 +15,8 @@ from .ops import (advect_semilagrange, buildLumpedMassMatrix, buildStiffnessMatr
                   build_mass_and_convection_mass, calculate_gradiant, calculate_vorticity, dye_implicit_step,
                   makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous)
 from .solver import (SAMPLE_FIELDS, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
-                     StokesSimulation, Tolerances, ensemble_dirichlet_values, pixel_centres, poisson_solve, solve,
-                     solve_ensemble, squirmer_values)
+                     StokesSimulation, Streamlines, Tolerances, ensemble_dirichlet_values, pixel_centres,
+                     poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401
 from .tracers import capture_map, tracer_init  # noqa: F401
 

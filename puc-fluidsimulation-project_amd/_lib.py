@@ -21,6 +21,8 @@ F_CAPTURE_STEP = 11
 F_VORTICITY = 12
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 OP_CURL = 11
+SLN_UNIT, SLN_EULER, SLN_BOTH = 1, 2, 4  # pucfem_streamline_flag
+SLN_COMPLETE, SLN_LEFT, SLN_STAGNANT, SLN_SEED_OUTSIDE = range(4)  # pucfem_streamline_status
 HOST_ONLY = -1
 ERRORS = {-1: "EINVAL", -2: "EHIP", -3: "ENOCONV", -4: "ESTATE", -5: "ENCCL", -6: "ENOMEM", -7: "ENODEV"}
 
@@ -88,6 +90,12 @@ SIGNATURES = {
     "pucfem_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
     "pucfem_ens_raster": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, ct.c_int32, _D, _F], ct.c_int),
     "pucfem_raster_probe": ([_P, ct.c_int32, _I32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _D], ct.c_int),
+    "pucfem_streamlines": ([_P, ct.c_int64, _D, ct.c_double, ct.c_int32, ct.c_int32, ct.c_double, ct.c_int32, _I32, _D,
+                            _I32, _I32, _D], ct.c_int),
+    "pucfem_streamlines_probe": ([_P, ct.c_int64, _D, ct.c_double, ct.c_int32, ct.c_int32, ct.c_double, ct.c_int32, _D],
+                                 ct.c_int),
+    "pucfem_ens_streamlines": ([_P, ct.c_int32, ct.c_int64, _D, ct.c_double, ct.c_int32, ct.c_int32, ct.c_double, _D,
+                                _I32, _I32], ct.c_int),
     "pucfem_flow_info": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_apply": ([_P, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_solve": ([_P, ct.c_int32, _D, _D, ct.c_double, ct.c_int32, _I32], ct.c_int),

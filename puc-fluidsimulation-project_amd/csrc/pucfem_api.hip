@@ -28,6 +28,7 @@
 #include "pucfem_kernels_impl.hpp"
 #include "pucfem_ensemble.hpp"
 #include "pucfem_sample.hpp"
+#include "pucfem_streamline.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -559,7 +560,9 @@ struct Ctx {
   // triangle ids, 3 the probe's counters, 4.. the fields that are formed when read (p / p2 kept in y, div u*,
   // the final divergence, 8 the vorticity): the samplers form them here and write no field of the context.
   // Slot 9: the partials of the vorticity pass (4 x MAXB) and, behind them, pucfem_flow_info's four reduced values
-  static constexpr int SMP_SLOTS = 10;
+  // Slots 10..13: pucfem_streamlines / pucfem_ens_streamlines (pucfem_streamline.hpp): the seeds, the points, the
+  // status and npts (one buffer), the values along the lines
+  static constexpr int SMP_SLOTS = 14;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -5716,6 +5719,128 @@ int pucfem_raster_probe(void* ctx, int32_t nfields, const int32_t* fields, int32
     out4[1] = (double)h[0];
     out4[2] = (double)h[1];
     out4[3] = (double)(sizeof(float) * count);
+  });
+}
+
+// ---- streamlines (pucfem_streamline.hpp)
+namespace {
+// the checked scalars of a streamline call; members: the lines are integrated for that many velocity fields
+SlnArgs sln_args(const Ctx& c, int64_t nseeds, const double* seeds, double h, int32_t nsteps, int32_t flags,
+                 double vmin, int64_t members) {
+  constexpr int64_t CAP = int64_t(1) << 26;  // stored points per call (1 GiB of output): a memory guard
+  require(nseeds >= 1, "nseeds < 1");
+  require(nsteps >= 1, "nsteps < 1");
+  require(std::isfinite(h) && h != 0.0, "the step h must be finite and non-zero");
+  require(std::isfinite(vmin) && vmin >= 0.0, "the speed floor vmin must be finite and >= 0");
+  require((flags & ~(SLN_UNIT | SLN_EULER | SLN_BOTH)) == 0, "unknown streamline flag bits");
+  require(nseeds <= CAP, "more than 2^26 stored points ((nsteps + 1) * lines * members)");
+  const int64_t lines = (flags & SLN_BOTH) ? 2 * nseeds : nseeds;
+  const int64_t per = ((int64_t)nsteps + 1) * lines;  // (< 2^59)
+  require(per <= CAP && per * members <= CAP, "more than 2^26 stored points ((nsteps + 1) * lines * members)");
+  require(seeds != nullptr, "null seeds");
+  // PUCFEM_SLN_HINT=0: every locate from scratch (the A/B of tools/streamline_bench.py; the output is the same)
+  const char* hv = std::getenv("PUCFEM_SLN_HINT");
+  // lanes per wave: doubled while the launch keeps enough waves (pucfem_streamline.hpp); PUCFEM_SLN_LANES=1..64
+  // fixes it (the same A/B)
+  const int64_t total = lines * members;
+  const int64_t waves = total > SLN_MANY ? SLN_WAVES_MANY : (c.lat_sl ? SLN_WAVES_LAT : SLN_WAVES_REC);
+  int32_t lanes = 1;
+  while (lanes < SLN_BS && (total + 2 * lanes - 1) / (2 * lanes) >= waves) lanes *= 2;
+  if (const char* lv = std::getenv("PUCFEM_SLN_LANES")) lanes = std::min(std::max(std::atoi(lv), 1), SLN_BS);
+  return SlnArgs{nseeds, lines, h, vmin, nsteps, flags, hv && std::atoi(hv) == 0 ? 0 : 1, lanes};
+}
+// the seeds' lines in the context's own velocity; st: status (lines), then npts (lines)
+void sln_launch(Ctx& c, const SlnArgs& A, const SampleFields& F, const double* dseeds, double* dpts, int32_t* dst,
+                double* dval) {
+  const int grid = (int)((A.lines + A.lanes - 1) / A.lanes);
+  if (c.lat_sl)
+    hipLaunchKernelGGL(k_streamlines<LatLocDev>, dim3(grid), dim3(SLN_BS), 0, c.st, c.llgrid, A, dseeds,
+                       (const double*)c.ux, (const double*)c.uy, F, dpts, dst, dst + A.lines, dval);
+  else
+    hipLaunchKernelGGL(k_streamlines<LocDev>, dim3(grid), dim3(SLN_BS), 0, c.st, c.lgrid, A, dseeds,
+                       (const double*)c.ux, (const double*)c.uy, F, dpts, dst, dst + A.lines, dval);
+  KCHK();
+}
+}  // namespace
+
+int pucfem_streamlines(void* ctx, int64_t nseeds, const double* seeds, double h, int32_t nsteps, int32_t flags,
+                       double vmin, int32_t nfields, const int32_t* fields, double* points, int32_t* status,
+                       int32_t* npts, double* values) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    sample_ready(c);
+    const SlnArgs A = sln_args(c, nseeds, seeds, h, nsteps, flags, vmin, 1);
+    require(nfields >= 0 && (nfields == 0 || fields != nullptr), "nfields < 0 or null fields");
+    require(points != nullptr && status != nullptr && npts != nullptr, "null output");
+    require((values == nullptr) == (nfields == 0), "values must be given exactly when fields are");
+    SampleFields F{};
+    if (nfields > 0) F = sample_fields(c, nfields, fields);
+    const size_t lines = (size_t)A.lines, per = lines * ((size_t)nsteps + 1);
+    double* dseeds = c.smp_scratch<double>(10, 2 * (size_t)nseeds);
+    double* dpts = c.smp_scratch<double>(11, 2 * per);
+    int32_t* dst = c.smp_scratch<int32_t>(12, 2 * lines);
+    double* dval = F.ncomp ? c.smp_scratch<double>(13, (size_t)F.ncomp * per) : nullptr;
+    c.h2d(dseeds, seeds, sizeof(double) * 2 * (size_t)nseeds);
+    sln_launch(c, A, F, dseeds, dpts, dst, dval);
+    c.d2h(points, dpts, sizeof(double) * 2 * per);
+    c.d2h(status, dst, sizeof(int32_t) * lines);
+    c.d2h(npts, dst + lines, sizeof(int32_t) * lines);
+    if (dval) c.d2h(values, dval, sizeof(double) * (size_t)F.ncomp * per);
+  });
+}
+
+int pucfem_streamlines_probe(void* ctx, int64_t nseeds, const double* seeds, double h, int32_t nsteps, int32_t flags,
+                             double vmin, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    sample_ready(c);
+    const SlnArgs A = sln_args(c, nseeds, seeds, h, nsteps, flags, vmin, 1);
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    const SampleFields F{};
+    const size_t lines = (size_t)A.lines, per = lines * ((size_t)nsteps + 1);
+    double* dseeds = c.smp_scratch<double>(10, 2 * (size_t)nseeds);
+    double* dpts = c.smp_scratch<double>(11, 2 * per);
+    int32_t* dst = c.smp_scratch<int32_t>(12, 2 * lines);
+    c.h2d(dseeds, seeds, sizeof(double) * 2 * (size_t)nseeds);
+    sln_launch(c, A, F, dseeds, dpts, dst, nullptr);  // (untimed: the first launch)
+    hipEvent_t ea, eb;
+    HIPCHK(hipEventCreate(&ea));
+    HIPCHK(hipEventCreate(&eb));
+    HIPCHK(hipEventRecord(ea, c.st));
+    for (int k = 0; k < iters; ++k) sln_launch(c, A, F, dseeds, dpts, dst, nullptr);
+    HIPCHK(hipEventRecord(eb, c.st));
+    HIPCHK(hipEventSynchronize(eb));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
+    (void)hipEventDestroy(ea);
+    (void)hipEventDestroy(eb);
+    out2[0] = (double)ms / iters;
+    out2[1] = (double)(sizeof(double) * 2 * per + sizeof(int32_t) * 2 * lines);
+  });
+}
+
+int pucfem_ens_streamlines(void* ctx, int32_t member, int64_t nseeds, const double* seeds, double h, int32_t nsteps,
+                           int32_t flags, double vmin, double* points, int32_t* status, int32_t* npts) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    sample_ready(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const int32_t m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+    const SlnArgs A = sln_args(c, nseeds, seeds, h, nsteps, flags, vmin, nm);
+    require(points != nullptr && status != nullptr && npts != nullptr, "null output");
+    const size_t lines = (size_t)A.lines * (size_t)nm, per = lines * ((size_t)nsteps + 1);
+    double* dseeds = c.smp_scratch<double>(10, 2 * (size_t)nseeds);
+    double* dpts = c.smp_scratch<double>(11, 2 * per);
+    int32_t* dst = c.smp_scratch<int32_t>(12, 2 * lines);
+    c.h2d(dseeds, seeds, sizeof(double) * 2 * (size_t)nseeds);
+    const int grid = (int)((A.lines + A.lanes - 1) / A.lanes);
+    hipLaunchKernelGGL(k_ens_streamlines, dim3(grid, nm), dim3(SLN_BS), 0, c.st, c.lgrid, A, (const double*)dseeds,
+                       (const double*)e.u, (int64_t)e.n, m0, dpts, dst, dst + lines);
+    KCHK();
+    c.d2h(points, dpts, sizeof(double) * 2 * per);
+    c.d2h(status, dst, sizeof(int32_t) * lines);
+    c.d2h(npts, dst + lines, sizeof(int32_t) * lines);
   });
 }
 

@@ -12,6 +12,9 @@ ffmpeg when it is installed, else an animated GIF (Pillow) or a PNG sequence; ``
 ``FrameRecorder(mesh, interval, raster=(W, H))`` records images rasterised on the device instead
 (``StokesSimulation.raster``): no field leaves the GPU, and ``render`` draws them with ``imshow`` -- the
 way to frames of a mesh whose triangles no plotting library draws (L7: 28M).
+
+``FrameRecorder(..., streamlines=dict(seeds=..., h=..., nsteps=...))`` also records the streamlines of every
+recorded frame (``StokesSimulation.streamlines``, integrated on the device); ``render`` draws them over the dye.
 """
 from __future__ import annotations
 
@@ -32,9 +35,14 @@ class FrameRecorder:
 
     vorticity=True: each frame also appends the vorticity to ``vort`` -- the reference's second panel
     (scripts/good_visualization.py:578-584), formed on the device: the (H, W) raster of "vorticity" in raster
-    mode, else the nodal field ``sim.vorticity``."""
+    mode, else the nodal field ``sim.vorticity``.
 
-    def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None, vorticity=False):
+    streamlines=dict(seeds=..., h=..., nsteps=..., **options of StokesSimulation.streamlines): each frame also
+    appends the lines' points (lines, nsteps + 1, 2) to ``lines`` and their point counts to ``lines_npts`` -- the
+    reference's streamplot (stokes_flow.py:536) of the frame's velocity.  Off by default."""
+
+    def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None, vorticity=False,
+                 streamlines=None):
         self.mesh = mesh
         self.interval = int(interval)
         self.dtype = dtype
@@ -45,6 +53,24 @@ class FrameRecorder:
         self.vel: list[np.ndarray] = []
         self.vorticity = bool(vorticity)
         self.vort: list[np.ndarray] = []
+        self.streamlines = None
+        if streamlines is not None:
+            opts = dict(streamlines)
+            missing = [k for k in ("seeds", "h", "nsteps") if k not in opts]
+            if missing:
+                raise ValueError(f"streamlines= needs seeds, h and nsteps (missing: {missing})")
+            if opts.get("fields"):
+                raise ValueError("the recorder keeps the lines' points, not fields along them")
+            opts["seeds"] = np.array(opts["seeds"], dtype=np.float64).reshape(-1, 2)
+            self.streamlines = opts
+        self.lines: list[np.ndarray] = []
+        self.lines_npts: list[np.ndarray] = []
+
+    def record_lines(self, sim):
+        """The streamlines of `sim`'s current velocity, for the frame just recorded."""
+        sl = sim.streamlines(**self.streamlines)
+        self.lines.append(np.array(sl.points, dtype=np.float64, copy=True))
+        self.lines_npts.append(np.array(sl.npts, dtype=np.int32, copy=True))
 
     def record(self, step, c, u, vort=None):
         self.steps.append(int(step))
@@ -82,6 +108,8 @@ class FrameRecorder:
                 else:
                     self.record(r, sim.c if sim.scheme == "color" else None, sim.u,
                                 sim.vorticity if self.vorticity else None)
+                if self.streamlines is not None:
+                    self.record_lines(sim)
         return stats
 
     def __len__(self):
@@ -91,7 +119,7 @@ class FrameRecorder:
 def save_npz(rec: FrameRecorder, path):
     """The raw frames.  Raster frames: `vel` (frames, 2, H, W), `dye` (frames, H, W) and `window`
     (x0, y0, x1, y1) instead of the mesh.  A recorder with vorticity frames adds `vort` (frames, H, W) or
-    (frames, N)."""
+    (frames, N); one with streamlines `lines` (frames, lines, nsteps + 1, 2) and `lines_npts` (frames, lines)."""
     if getattr(rec, "raster", None) is not None:
         W, H = rec.raster
         d = dict(steps=np.array(rec.steps), window=np.array(rec.window or (0.0, 0.0, 1.0, 1.0), dtype=np.float64),
@@ -103,6 +131,9 @@ def save_npz(rec: FrameRecorder, path):
         d["dye"] = np.stack(rec.dye)
     if getattr(rec, "vort", None):
         d["vort"] = np.stack(rec.vort)
+    if getattr(rec, "lines", None):
+        d["lines"] = np.stack(rec.lines)
+        d["lines_npts"] = np.stack(rec.lines_npts)
     np.savez_compressed(path, **d)
 
 
@@ -184,13 +215,17 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
     Raster frames are drawn with imshow (magma, [0, 1], origin lower, the window as extent) under a quiver
     of every `skip`-th pixel's velocity.  With vorticity frames (``rec.vort``) a second panel beside it shows them
     as the reference does (good_visualization.py:578-584: coolwarm, limits symmetric about 0 at the largest
-    |vorticity| of the frames)."""
+    |vorticity| of the frames).  Recorded streamlines (``rec.lines``) are drawn over the dye panel, cut at the
+    periodic wraps (streamline_segments)."""
     import matplotlib
 
     matplotlib.use("Agg")
     import matplotlib.pyplot as plt
     import matplotlib.tri as mtri
     from matplotlib import animation
+    from matplotlib.collections import LineCollection
+
+    from .solver import streamline_segments
 
     vort = getattr(rec, "vort", None) or None
     if vort:
@@ -240,6 +275,10 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
         def arrows(i):
             return rec.vel[i][::skip, 0], rec.vel[i][::skip, 1]
 
+    lines = getattr(rec, "lines", None) or None
+    if lines:
+        lc = LineCollection(streamline_segments(lines[0]), colors="cyan", linewidths=0.8, zorder=3)
+        ax.add_collection(lc)
     fig.colorbar(tpc, ax=ax, label="Dye concentration")
     ax.set_aspect("equal")
     title = ax.set_title(f"Fluid Simulation - Step {rec.steps[0]}")
@@ -254,6 +293,8 @@ def render(rec: FrameRecorder, out, fps=20, dpi=150, skip=None):
         qv.set_UVC(*arrows(i))
         if vort:
             tpv.set_array(vort[i])
+        if lines:
+            lc.set_segments(streamline_segments(lines[i]))
         title.set_text(f"Fluid Simulation - Step {rec.steps[i]}")
         return tpc, qv, title
 

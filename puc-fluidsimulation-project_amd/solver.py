@@ -61,6 +61,48 @@ def pixel_centres(width, height, window=None):
     return np.ascontiguousarray(np.stack([X.ravel(), Y.ravel()], 1))
 
 
+def _streamline_args(seeds, h, nsteps, unit, order, both, vmin):
+    """(seeds (n, 2), flags) of a streamline call; order 2: midpoint, 1: Euler."""
+    if order not in (1, 2):
+        raise ValueError("order is 2 (midpoint) or 1 (Euler)")
+    P = np.ascontiguousarray(seeds, dtype=np.float64).reshape(-1, 2)
+    flags = (_lib.SLN_UNIT if unit else 0) | (_lib.SLN_EULER if order == 1 else 0) | (_lib.SLN_BOTH if both else 0)
+    return P, flags
+
+
+@dataclass
+class Streamlines:
+    """Lines of Context.streamlines: `points` (lines, nsteps + 1, 2), NaN past a line's end; `status` (lines,) 0
+    complete, 1 left the fluid, 2 stagnant, 3 seed outside; `npts` (lines,) the points stored; `values` {field:
+    (lines, nsteps + 1) or (lines, nsteps + 1, 2)} at the stored points.  With both=True the first half of the lines
+    runs along the flow and the second half against it.  An ensemble's arrays carry a leading member axis."""
+    points: np.ndarray
+    status: np.ndarray
+    npts: np.ndarray
+    values: dict = field(default_factory=dict)
+
+    def segments(self):
+        """streamline_segments(self.points)"""
+        return streamline_segments(self.points)
+
+
+def streamline_segments(points):
+    """Cut lines (..., npoints, 2) for plotting: a list of (k, 2) arrays, k >= 2.  A line's trailing NaNs are
+    dropped and it is split where consecutive x differ by more than 0.5 -- a periodic wrap, which would otherwise be
+    drawn as a stroke across the whole picture."""
+    P = np.asarray(points, dtype=np.float64)
+    out = []
+    for line in P.reshape((-1,) + P.shape[-2:]):
+        ok = ~np.isnan(line).any(axis=1)
+        n = int(np.argmin(ok)) if not ok.all() else len(line)
+        line = line[:n]
+        if n < 2:
+            continue
+        cuts = np.where(np.abs(np.diff(line[:, 0])) > 0.5)[0] + 1
+        out += [seg for seg in np.split(line, cuts) if len(seg) >= 2]
+    return out
+
+
 def _split_images(names, ncomp, img):
     """{name: (..., H, W) or (..., 2, H, W)} from an image stack whose component axis is -3."""
     out, k = {}, 0
@@ -284,6 +326,38 @@ class Context:
         img = np.zeros((sum(ncomp), max(int(height), 0), max(int(width), 0)), dtype=np.float32)
         self._c(self.L.pucfem_raster(self.h, len(ids), _lib.iptr(ids), int(width), int(height), wp, _lib.fptr(img)))
         return _split_images(names, ncomp, img)
+
+    def streamlines(self, seeds, h, nsteps, unit=True, order=2, both=False, vmin=0.0, fields=()):
+        """The frozen velocity integrated from `seeds` (n, 2) on the device (pucfem_streamlines; the reference's
+        ax.streamplot): a Streamlines.  h: the signed step (negative: against the flow) -- an arc length in the max
+        norm with unit=True, a time otherwise; order 2 midpoint, 1 Euler; both=True: every seed forwards (lines
+        [0, n)) and backwards (lines [n, 2 n)); vmin: a line ends (status 2) where both |u_x| and |u_y| are <= vmin;
+        fields: names as for sample(), read at every stored point."""
+        P, flags = _streamline_args(seeds, h, nsteps, unit, order, both, vmin)
+        names, ids, ncomp = _sample_spec(fields)
+        n, lines, ns = P.shape[0], P.shape[0] * (2 if both else 1), max(int(nsteps), 0) + 1
+        # (arguments the library refuses: small buffers, and it reports the error)
+        big = n < 1 or ns * lines > (1 << 26)
+        pts = np.zeros((1, 1, 2) if big else (ns, lines, 2))
+        st = np.zeros(1 if big else lines, dtype=np.int32)
+        npts = np.zeros(1 if big else lines, dtype=np.int32)
+        val = np.zeros((sum(ncomp), 1, 1) if big else (sum(ncomp), ns, lines)) if ids.size else None
+        self._c(self.L.pucfem_streamlines(self.h, n, _lib.dptr(P), float(h), int(nsteps), flags, float(vmin), len(ids),
+                                          _lib.iptr(ids) if ids.size else None, _lib.dptr(pts), _lib.iptr(st),
+                                          _lib.iptr(npts), _lib.dptr(val) if val is not None else None))
+        vals, k = {}, 0
+        for f, nc in zip(names, ncomp):
+            vals[f] = val[k].T if nc == 1 else val[k:k + nc].transpose(2, 1, 0)
+            k += nc
+        return Streamlines(pts.transpose(1, 0, 2), st, npts, vals)
+
+    def streamlines_probe(self, seeds, h, nsteps, unit=True, order=2, both=False, vmin=0.0, iters=5):
+        """Kernel time of streamlines() without fields (pucfem_streamlines_probe; tools/streamline_bench.py)."""
+        P, flags = _streamline_args(seeds, h, nsteps, unit, order, both, vmin)
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_streamlines_probe(self.h, P.shape[0], _lib.dptr(P), float(h), int(nsteps), flags,
+                                                float(vmin), int(iters), o))
+        return dict(kernel_ms=o[0], output_bytes=int(o[1]))
 
     def raster_probe(self, fields, width, height, window=None, iters=10):
         """Kernel time and pixel bookkeeping of raster() (pucfem_raster_probe; tools/raster_bench.py)."""
@@ -524,6 +598,11 @@ class StokesSimulation:
         """The fields as images (Context.raster): {name: float32 (height, width) or (2, height, width)}."""
         return self.ctx.raster(fields, width, height, window)
 
+    def streamlines(self, seeds, h, nsteps, unit=True, order=2, both=False, vmin=0.0, fields=()):
+        """Streamlines of the current velocity (Context.streamlines): points (lines, nsteps + 1, 2), status, npts and
+        values[name] (lines, nsteps + 1) or (lines, nsteps + 1, 2)."""
+        return self.ctx.streamlines(seeds, h, nsteps, unit, order, both, vmin, fields)
+
     @property
     def tracers(self):
         n = self._ntr()
@@ -717,6 +796,23 @@ class StokesEnsemble:
                                                  -1 if member is None else int(member), int(width), int(height), wp,
                                                  _lib.fptr(img)))
         return _split_images(names, ncomp, img if member is None else img[0])
+
+    def streamlines(self, seeds, h, nsteps, unit=True, order=2, both=False, vmin=0.0, member=None):
+        """Every member's streamlines from the same seeds (pucfem_ens_streamlines; Context.streamlines' arguments): a
+        Streamlines with points (M, lines, nsteps + 1, 2), status and npts (M, lines); member = m: that member's
+        alone, without the leading axis.  Each member's lines are those of a single run with its boundary values."""
+        P, flags = _streamline_args(seeds, h, nsteps, unit, order, both, vmin)
+        n, lines, ns = P.shape[0], P.shape[0] * (2 if both else 1), max(int(nsteps), 0) + 1
+        nm = self.M if member is None else 1
+        big = n < 1 or ns * lines * nm > (1 << 26)
+        pts = np.zeros((1, 1, 1, 2) if big else (nm, ns, lines, 2))
+        st = np.zeros((1, 1) if big else (nm, lines), dtype=np.int32)
+        npts = np.zeros((1, 1) if big else (nm, lines), dtype=np.int32)
+        self.ctx._c(self.ctx.L.pucfem_ens_streamlines(self.ctx.h, -1 if member is None else int(member), n,
+                                                      _lib.dptr(P), float(h), int(nsteps), flags, float(vmin),
+                                                      _lib.dptr(pts), _lib.iptr(st), _lib.iptr(npts)))
+        pts = pts.transpose(0, 2, 1, 3)
+        return Streamlines(pts, st, npts) if member is None else Streamlines(pts[0], st[0], npts[0])
 
     def step(self, n=1, stats=True):
         """n steps of every member: a list over the steps of lists over the members of step records
