@@ -140,8 +140,15 @@ enum pucfem_field {
      calculate_vorticity equals bit for bit on the host).  Stokes contexts, else PUCFEM_ESTATE.  On a multi-rank
      context pucfem_get_field serves the rank's owned rows, as for FINAL_DIV; it is not collective: every call that
      writes u leaves its ghost values current. */
-  PUCFEM_F_VORTICITY = 12
+  PUCFEM_F_VORTICITY = 12,
+  /* all dye channels, K x N channel-major (channel k at buf[k * N + node], the caller's numbering): see "dye
+     channels" below.  pucfem_set_field with count = K * N defines K (0 .. PUCFEM_MAX_DYES); count = 0 removes the
+     channels (buf may then be NULL). */
+  PUCFEM_F_DYES = 13,
+  /* channel k is field PUCFEM_F_DYE0 + k (N values, k < K) */
+  PUCFEM_F_DYE0 = 64
 };
+#define PUCFEM_MAX_DYES 16
 
 /* operators for pucfem_apply / pucfem_solve / pucfem_host_get_csr */
 enum pucfem_op {
@@ -276,6 +283,35 @@ int pucfem_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t wid
 int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t member /* -1 = all */,
                       int32_t width, int32_t height, const double* window4, float* out);
 
+/* ---- dye channels: several dyes advected per step from one back-trace ------------- */
+/* The reference starts its dye three ways: the half plane (StokesColor.py:495), a thin stripe at x = 0.2
+   (scripts/good_visualization2.py:520-524) and a blob at (0.5, 0.75) (scripts/good_visualization.py:555-559); how
+   well a swimmer mixes depends on which one is asked about.  A context carries up to PUCFEM_MAX_DYES extra dye
+   fields beside c.  Every pucfem_step advects all of them with that step's final u and dt by the semi-Lagrangian
+   scheme of c (StokesColor.py:347-389), the departure point and its triangle found once per node for all channels.
+   Channel k holds, bit for bit, what c would hold in a run whose c was started from channel k's values; u, p, c and
+   the step statistics of the run are those of a run without channels.
+   Single-rank PUCFEM_STOKES_COLOR contexts with dye_scheme = 0 after pucfem_build_operators, else PUCFEM_ESTATE
+   (multi-rank, STOKES_FOOD, heat, Poisson, the implicit dye; before the build); PUCFEM_ENODEV on a host-only context;
+   PUCFEM_EINVAL for a count that is no multiple of N, more than PUCFEM_MAX_DYES channels, nch outside
+   1 .. PUCFEM_MAX_DYES, or a channel k >= K.  Setting PUCFEM_F_DYES resets the channel step count; setting one
+   channel (PUCFEM_F_DYE0 + k), PUCFEM_F_C or PUCFEM_F_U leaves the channels and their count alone.
+   pucfem_build_operators and pucfem_ctx_destroy drop the channels.  PUCFEM_F_DYE0 + k is also a one-component
+   field of pucfem_sample_points, pucfem_raster and the values of pucfem_streamlines; ensembles have no channels
+   (PUCFEM_EINVAL in the pucfem_ens_* calls).  A small-mesh context steps from a captured graph only while it has
+   no channels; with channels it runs the same launches uncaptured (the same bits). */
+/* out[0] K, [1] channel steps since the channels were set, [2] not-found rows of the last channel launch (the same
+   for every channel; 0 before the first), [3] device bytes held for the channels */
+int pucfem_dyes_info(void* ctx, int64_t* out4);
+/* (I, mu, var) of every channel over marker == 0, out[3 * k + {0, 1, 2}]: computed at the call by the reduction
+   of pucfem_mixing_index, so row k holds the bits of pucfem_mixing_index(ctx, channel k read back, ...).  Changes
+   no state. */
+int pucfem_dyes_mixing(void* ctx, double* out /* K x 3 */);
+/* Measurement: the channels' kernel with nch channels (scratch buffers, zero fields) on the context's current u and
+   dt, launched once untimed and then `iters` times back to back between two events.  out2[0]: milliseconds per
+   launch; out2[1]: algorithmic bytes per launch. */
+int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2);
+
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,
    good_visualization.py:738).  These calls integrate the context's current u from caller-given seeds with the
@@ -350,6 +386,12 @@ int pucfem_solve(void* ctx, int32_t op, const double* b, double* x, double rtol,
 /* advect_semilagrange (StokesColor.py:347-389): c_out = SL(c, u, dt); notfound may be NULL */
 int pucfem_sl_advect(void* ctx, const double* c, const double* u, double dt, double* c_out,
                      int32_t* notfound);
+/* pucfem_sl_advect for nch fields at once (1 .. PUCFEM_MAX_DYES; c and c_out nch x N, field-major), through the dye
+   channels' kernel on scratch buffers: one back-trace and one point location per node for all fields.  Field k of
+   c_out and notfound (N or NULL) hold the bits pucfem_sl_advect returns for field k.  The step's state and the
+   context's channels are not touched.  Readiness as for the dye channels (below). */
+int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* c /* nch x N */, const double* u, double dt,
+                           double* c_out /* nch x N */, int32_t* notfound /* N or NULL */);
 /* tracer step (StokesFood.py:482-499) on the tracers held in the context, with u given */
 int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps);
 /* the context's tracer set (member = -1) or that of member `member` of its ensemble: out[0] tracers, [1] tracers

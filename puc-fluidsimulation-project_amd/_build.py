@@ -10,7 +10,8 @@ ROOT = os.path.dirname(HERE)
 SRC = ["csrc/pucfem_api.hip", "csrc/pucfem_host.cpp"]
 DEPS = SRC + ["csrc/pucfem_host.hpp", "csrc/pucfem_kernels.hpp", "csrc/pucfem_kernels_impl.hpp",
               "csrc/pucfem_comm.hpp", "csrc/pucfem_lattice.hpp", "csrc/pucfem_ensemble.hpp",
-              "csrc/pucfem_sample.hpp", "csrc/pucfem_streamline.hpp"]
+              "csrc/pucfem_sample.hpp", "csrc/pucfem_streamline.hpp",
+              "csrc/pucfem_dye_channels.hpp"]
 
 
 def hipcc():

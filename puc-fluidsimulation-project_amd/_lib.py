@@ -19,6 +19,9 @@ STOKES_COLOR, STOKES_FOOD, HEAT, POISSON = 0, 1, 2, 3
 F_U, F_USTAR, F_P, F_P2, F_DIV_STAR, F_DIV_U, F_FINAL_DIV, F_C, F_SCALAR, F_TRACERS, F_STATUS = range(11)
 F_CAPTURE_STEP = 11
 F_VORTICITY = 12
+F_DYES = 13  # all dye channels (K, N); channel k is field F_DYE0 + k
+F_DYE0 = 64
+MAX_DYES = 16
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 OP_CURL = 11
 SLN_UNIT, SLN_EULER, SLN_BOTH = 1, 2, 4  # pucfem_streamline_flag
@@ -100,6 +103,10 @@ SIGNATURES = {
     "pucfem_apply": ([_P, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_solve": ([_P, ct.c_int32, _D, _D, ct.c_double, ct.c_int32, _I32], ct.c_int),
     "pucfem_sl_advect": ([_P, _D, _D, ct.c_double, _D, _I32], ct.c_int),
+    "pucfem_sl_advect_multi": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32], ct.c_int),
+    "pucfem_dyes_info": ([_P, _I64], ct.c_int),
+    "pucfem_dyes_mixing": ([_P, _D], ct.c_int),
+    "pucfem_dyes_probe": ([_P, ct.c_int32, ct.c_int32, _D], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_dye_step": ([_P, _D, _D, _D, _I32], ct.c_int),
     "pucfem_comm_info": ([_P, ct.POINTER(ct.c_int64)], ct.c_int),

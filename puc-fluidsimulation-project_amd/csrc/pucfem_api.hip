@@ -29,6 +29,7 @@
 #include "pucfem_ensemble.hpp"
 #include "pucfem_sample.hpp"
 #include "pucfem_streamline.hpp"
+#include "pucfem_dye_channels.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -562,7 +563,9 @@ struct Ctx {
   // Slot 9: the partials of the vorticity pass (4 x MAXB) and, behind them, pucfem_flow_info's four reduced values
   // Slots 10..13: pucfem_streamlines / pucfem_ens_streamlines (pucfem_streamline.hpp): the seeds, the points, the
   // status and npts (one buffer), the values along the lines
-  static constexpr int SMP_SLOTS = 14;
+  // Slots 14..16: pucfem_sl_advect_multi / pucfem_dyes_probe (pucfem_dye_channels.hpp): the fields in, the fields
+  // out, the blocks' not-found counts
+  static constexpr int SMP_SLOTS = 17;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -777,6 +780,7 @@ struct Ctx {
       if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
       if (graph_k) (void)hipGraphDestroy(graph_k);
       for (void* a : allocs) (void)hipFree(a);
+      drop_dyes();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1004,6 +1008,96 @@ struct Ctx {
       klaunch(8, 0.0, k_sl_slow<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0, (int64_t)n, vx, vy, dt,
               cf, cn, w, nf, part_sl, (const int32_t*)sl_queue, (const int32_t*)sl_qcnt, ro);
     }
+  }
+
+  // ------------------------------------------------------------------ dye channels (pucfem_dye_channels.hpp)
+  // K extra dye fields advected beside c (PUCFEM_F_DYES), channel-major in the internal numbering: two K x N sets,
+  // swapped after every launch (a launch cannot write a vector that other rows still gather from).  The buffers are
+  // freed when the channels are dropped (they are not in `allocs`).
+  int ndye = 0;
+  double *dye_cur = nullptr, *dye_nxt = nullptr;
+  int32_t* dye_nfpart = nullptr;  // per block of the last channel launch: its not-found rows
+  int dye_nb = 0;                 // that launch's blocks (0: none since the channels were set)
+  i64 dye_steps = 0;
+  static int nb_dye(i64 n) { return (int)std::max<i64>(1, std::min<i64>(SLB, (n + BS - 1) / BS)); }
+  // per row: coordinates 16, u 16 and the locator's share as sl_launch counts it (lattice: home face 4, cell
+  // entries 8, radii 8); per channel and row: the old value read 8 (the vertices' lines are the rows' own), the
+  // new one written 8
+  double dye_launch_bytes(int nch, i64 n) const { return ((lat_sl ? 52.0 : 32.0) + 16.0 * nch) * (double)n; }
+  // the single-rank explicit-dye Stokes context the channels live on
+  void dye_ready() const {
+    need_built();
+    auto state = [](bool ok, const char* msg) {
+      if (!ok) throw Error(PUCFEM_ESTATE, msg);
+    };
+    state(scheme == PUCFEM_STOKES_COLOR, "dye channels need a STOKES_COLOR context");
+    state(!dist() && world == 1,
+          "dye channels are single-rank (a multi-rank context would need the dye's wide halo per channel)");
+    state(!dye_impl, "dye channels follow the semi-Lagrangian dye (dye_scheme = 0)");
+    need_dev();
+    state(has_cgrid && (lat_sl ? llgrid.face != nullptr : lgrid.rec != nullptr), "the context has no point locator");
+  }
+  // k_sl_multi over rows [row0, row0 + n) on the current stream: nch channels of leading dimension N
+  void dye_launch(i64 row0, i64 n, const double* vx, const double* vy, double dt, int nch, const double* cin,
+                  double* cout, int32_t* nf, int32_t* nfpart) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    if (lat_sl)
+      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, cgrid, (int64_t)row0,
+              (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
+    else
+      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0,
+              (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
+    KCHK();
+  }
+  // the channels' part of a step, on the stream of the step's sl_launch, with the step's final u
+  void dyes_step() {
+    if (!ndye) return;
+    dye_launch(lp.r0, lp.n_own, ux, uy, prm.dt, ndye, dye_cur, dye_nxt, nullptr, dye_nfpart);
+    std::swap(dye_cur, dye_nxt);
+    dye_nb = nb_dye(lp.n_own);
+    ++dye_steps;
+  }
+  void drop_dyes() {
+    if (!dye_cur && !dye_nfpart) {
+      ndye = 0;
+      return;
+    }
+    if (st) (void)hipStreamSynchronize(st);
+    if (st_sl) (void)hipStreamSynchronize(st_sl);
+    for (void* q : {(void*)dye_cur, (void*)dye_nxt, (void*)dye_nfpart})
+      if (q) (void)hipFree(q);
+    dye_cur = dye_nxt = nullptr;
+    dye_nfpart = nullptr;
+    ndye = dye_nb = 0;
+    dye_steps = 0;
+  }
+  // K channels from buf (K x N, the caller's numbering); K = 0 removes them
+  void set_dyes(int K, const double* buf) {
+    const i64 N = mesh.N;
+    if (K != ndye) {
+      drop_dyes();
+      if (K > 0) {
+        const size_t bytes = sizeof(double) * (size_t)K * (size_t)N;
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&dye_cur), bytes));
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&dye_nxt), bytes));
+        HIPCHK(hipMalloc(reinterpret_cast<void**>(&dye_nfpart), sizeof(int32_t) * SLB));
+        HIPCHK(hipMemsetAsync(dye_nxt, 0, bytes, st));
+        HIPCHK(hipMemsetAsync(dye_nfpart, 0, sizeof(int32_t) * SLB, st));
+        ndye = K;
+      }
+    }
+    dye_steps = 0;
+    dye_nb = 0;
+    if (K == 0) return;
+    std::vector<double> x((size_t)K * (size_t)N);
+    for (int k = 0; k < K; ++k)
+      for (i64 g = 0; g < N; ++g) x[(size_t)k * N + g] = buf[(size_t)k * N + ord.new2old[g]];
+    h2d(dye_cur, x.data(), sizeof(double) * x.size());
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  size_t dye_dev_bytes() const {
+    return ndye ? 2 * sizeof(double) * (size_t)ndye * (size_t)mesh.N + sizeof(int32_t) * SLB : 0;
   }
 
 
@@ -2708,6 +2802,7 @@ struct Ctx {
     const RedOut rs = ro(vals + 2, CNT_DYE_SL, 3, SLB);
     sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
     KCHK();
+    dyes_step();  // (before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
     std::swap(c_full, c_new);
     if (!rs.out) reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
     const int nbm = nb_rows(lp.n_own);
@@ -2820,6 +2915,8 @@ struct Ctx {
       } else {
         sl_ro = ro(vals + 2, CNT_SL, 3, SLB);
         sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, sl_ro);
+        KCHK();
+        dyes_step();
       }
       KCHK();
       // fixed buffers inside a captured graph: k_mix2 copies the new values back instead of a swap
@@ -4773,6 +4870,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
       c.ens.reset();
     }
     c.drop_step_graphs();
+    if (!c.host_only) c.drop_dyes();
     build(c);
   });
 }
@@ -4781,9 +4879,28 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
 int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
+    const bool dyef = field == PUCFEM_F_DYES || (field >= PUCFEM_F_DYE0 && field < PUCFEM_F_DYE0 + DYE_MAX);
+    if (dyef) c.dye_ready();
     c.need_dev();
     c.need_built();
     const i64 N = c.mesh.N, no = c.lp.n_own;
+    if (dyef) {
+      if (field == PUCFEM_F_DYES) {
+        require(count >= 0 && count % N == 0, "dyes must be (K, N)");
+        require(count / N <= DYE_MAX, "at most PUCFEM_MAX_DYES (16) dye channels");
+        require(count == 0 || buf != nullptr, "null dyes");
+        c.set_dyes((int)(count / N), buf);
+      } else {
+        const int k = field - PUCFEM_F_DYE0;
+        require(k < c.ndye, "dye channel index >= the number of channels");
+        require(count == N && buf != nullptr, "a dye channel must be (N,)");
+        std::vector<double> x(N);
+        for (i64 g = 0; g < N; ++g) x[g] = buf[c.ord.new2old[g]];
+        c.h2d(c.dye_cur + (size_t)k * N, x.data(), sizeof(double) * N);
+        HIPCHK(hipStreamSynchronize(c.st));
+      }
+      return;
+    }
     auto own2 = [&](double* a, double*) {  // (the interleaved velocity: a = its pairs)
       require(count == 2 * N, "field must be (N, 2)");
       std::vector<double> xy(2 * no);
@@ -4861,9 +4978,24 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
 int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
+    const bool dyef = field == PUCFEM_F_DYES || (field >= PUCFEM_F_DYE0 && field < PUCFEM_F_DYE0 + DYE_MAX);
+    if (dyef) c.dye_ready();
     c.need_dev();
     c.need_built();
     const i64 N = c.mesh.N, no = c.lp.n_own;
+    if (dyef) {  // K x N, or channel k alone, into the caller's numbering
+      const int k0 = field == PUCFEM_F_DYES ? 0 : field - PUCFEM_F_DYE0;
+      const int nk = field == PUCFEM_F_DYES ? c.ndye : 1;
+      require(k0 < c.ndye || field == PUCFEM_F_DYES, "dye channel index >= the number of channels");
+      require(count == (i64)nk * N, field == PUCFEM_F_DYES ? "dyes are (K, N)" : "a dye channel is (N,)");
+      if (nk == 0) return;
+      require(buf != nullptr, "null output");
+      std::vector<double> x((size_t)nk * (size_t)N);
+      c.d2h(x.data(), c.dye_cur + (size_t)k0 * N, sizeof(double) * x.size());
+      for (int k = 0; k < nk; ++k)
+        for (i64 g = 0; g < N; ++g) buf[(size_t)k * N + c.ord.new2old[g]] = x[(size_t)k * N + g];
+      return;
+    }
     auto get2 = [&](const double* a, const double*) {  // (the interleaved velocity)
       require(count == 2 * N, "field is (N, 2)");
       std::vector<double> xy(2 * no);
@@ -4969,7 +5101,8 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       double* rec = c.dalloc<double>(8 * (i64)nsteps);
       int* dits = c.dalloc<int>(3 * (i64)nsteps);
       std::vector<int32_t> its(3 * (size_t)nsteps);
-      if (c.dense && !c.timer.on && !c.dye_impl) {
+      // (a context with dye channels steps uncaptured: the channels' buffers swap every step)
+      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -5576,7 +5709,14 @@ SampleFields sample_fields(Ctx& c, int32_t nfields, const int32_t* fields) {
         break;
       }
       default:
-        throw Error(PUCFEM_EINVAL, "not a sampled field (U, USTAR, P, P2, DIV_STAR, DIV_U, FINAL_DIV, C, VORTICITY)");
+        if (fields[k] >= PUCFEM_F_DYE0 && fields[k] < PUCFEM_F_DYE0 + DYE_MAX) {
+          const int ch = fields[k] - PUCFEM_F_DYE0;
+          require(ch < c.ndye, "dye channel index >= the number of channels");
+          sample_push(F, c.dye_cur + (size_t)ch * (size_t)c.mesh.N, 1, 0);
+          break;
+        }
+        throw Error(PUCFEM_EINVAL,
+                    "not a sampled field (U, USTAR, P, P2, DIV_STAR, DIV_U, FINAL_DIV, C, VORTICITY, DYE0 + k)");
     }
   }
   return F;
@@ -6253,12 +6393,18 @@ int pucfem_tracer_info(void* ctx, int32_t member, int64_t* out6) {
 
 // (I, mu, var) of c with the node weights w (device, internal order) over the N nodes of a single-rank
 // context: the two weighted sums, then the weighted variance about mu (k_mix2), then k_stats
+static void mixing_dev(Ctx& c, const double* cf, const double* w, double* out3);
 static void mixing_on(Ctx& c, const double* cin, const double* w, double* out3) {
   const i64 N = c.mesh.N;
   std::vector<double> a(N);
   for (i64 g = 0; g < N; ++g) a[g] = cin[c.ord.new2old[g]];
   double* cf = c.cg_pa[0];
   HIPCHK(hipMemcpyAsync(cf, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+  mixing_dev(c, cf, w, out3);
+}
+// the same of a field cf already on the device (internal order; pucfem_dyes_mixing: a channel where it lies)
+static void mixing_dev(Ctx& c, const double* cf, const double* w, double* out3) {
+  const i64 N = c.mesh.N;
   const int nb = c.nb_rows(N);
   // part_a[0..] = sum w c (the second dot, w w, is not used)
   hipLaunchKernelGGL(k_dot2, dim3(nb), dim3(BS), 0, c.st, N, w, (const double*)cf, w, w, c.part_a);
@@ -6307,6 +6453,100 @@ int pucfem_mixing_index_w(void* ctx, const double* cin, const double* w, double*
     double* dw = c.cg_q[0];
     HIPCHK(hipMemcpyAsync(dw, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
     mixing_on(c, cin, dw, out3);
+  });
+}
+
+// ---- dye channels (pucfem_dye_channels.hpp)
+int pucfem_dyes_info(void* ctx, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.dye_ready();
+    require(out4 != nullptr, "null output");
+    int64_t nf = 0;
+    if (c.ndye && c.dye_nb > 0) {  // the blocks' counts of the last launch, in block order
+      std::vector<int32_t> part((size_t)c.dye_nb);
+      c.d2h(part.data(), c.dye_nfpart, sizeof(int32_t) * part.size());
+      for (int32_t v : part) nf += v;
+    }
+    out4[0] = c.ndye;
+    out4[1] = c.dye_steps;
+    out4[2] = nf;
+    out4[3] = (int64_t)c.dye_dev_bytes();
+  });
+}
+
+int pucfem_dyes_mixing(void* ctx, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.dye_ready();
+    require(out != nullptr || c.ndye == 0, "null output");
+    for (int k = 0; k < c.ndye; ++k) mixing_dev(c, c.dye_cur + (size_t)k * (size_t)c.mesh.N, c.dwmix, out + 3 * k);
+  });
+}
+
+int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* cin, const double* u, double dt, double* cout,
+                           int32_t* notfound) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.dye_ready();
+    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    const size_t tot = (size_t)nch * (size_t)N;
+    std::vector<double> a(tot), bxy(2 * N);
+    for (i64 g = 0; g < N; ++g) {
+      const i64 o = c.ord.new2old[g];
+      for (int k = 0; k < nch; ++k) a[(size_t)k * N + g] = cin[(size_t)k * N + o];
+      bxy[2 * g] = u[2 * o];
+      bxy[2 * g + 1] = u[2 * o + 1];
+    }
+    // u as the step stores it (interleaved pairs) in scratch: the step's state stays untouched
+    if (!c.solve_tmp) c.solve_tmp = c.dalloc<double>(4 * c.nloc);
+    double *tx = c.solve_tmp, *ty = tx + 1;
+    double* din = c.smp_scratch<double>(14, tot);
+    double* dout = c.smp_scratch<double>(15, tot);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    c.h2d(din, a.data(), sizeof(double) * tot);
+    c.h2d(tx, bxy.data(), sizeof(double) * 2 * N);
+    c.dye_launch(0, N, tx, ty, dt, nch, din, dout, c.dnotfound, dpart);
+    std::vector<int32_t> nf(N);
+    c.d2h(a.data(), dout, sizeof(double) * tot);
+    c.d2h(nf.data(), c.dnotfound, sizeof(int32_t) * N);
+    for (i64 g = 0; g < N; ++g) {
+      const i64 o = c.ord.new2old[g];
+      for (int k = 0; k < nch; ++k) cout[(size_t)k * N + o] = a[(size_t)k * N + g];
+      if (notfound) notfound[o] = nf[g];
+    }
+  });
+}
+
+int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.dye_ready();
+    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    const i64 N = c.mesh.N;
+    const size_t tot = (size_t)nch * (size_t)N;
+    double* din = c.smp_scratch<double>(14, tot);
+    double* dout = c.smp_scratch<double>(15, tot);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
+    auto launch = [&] { c.dye_launch(0, N, c.ux, c.uy, c.prm.dt, nch, din, dout, nullptr, dpart); };
+    launch();  // (untimed: the first launch)
+    hipEvent_t ea, eb;
+    HIPCHK(hipEventCreate(&ea));
+    HIPCHK(hipEventCreate(&eb));
+    HIPCHK(hipEventRecord(ea, c.st));
+    for (int k = 0; k < iters; ++k) launch();
+    HIPCHK(hipEventRecord(eb, c.st));
+    HIPCHK(hipEventSynchronize(eb));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
+    (void)hipEventDestroy(ea);
+    (void)hipEventDestroy(eb);
+    out2[0] = (double)ms / iters;
+    out2[1] = c.dye_launch_bytes(nch, N);
   });
 }
 

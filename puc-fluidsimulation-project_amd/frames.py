@@ -39,10 +39,14 @@ class FrameRecorder:
 
     streamlines=dict(seeds=..., h=..., nsteps=..., **options of StokesSimulation.streamlines): each frame also
     appends the lines' points (lines, nsteps + 1, 2) to ``lines`` and their point counts to ``lines_npts`` -- the
-    reference's streamplot (stokes_flow.py:536) of the frame's velocity.  Off by default."""
+    reference's streamplot (stokes_flow.py:536) of the frame's velocity.  Off by default.
+
+    dyes=True: each frame also appends the simulation's dye channels (``StokesSimulation.dyes``) to ``dyes``, the way
+    the dye is recorded: a copy (K, N) of the channels, or in raster mode one image per channel (K, H, W), rasterised
+    as "dye0" .. in the frame's raster call.  dyes= may also name the channels to record ("dye0", 2, ...)."""
 
     def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None, vorticity=False,
-                 streamlines=None):
+                 streamlines=None, dyes=False):
         self.mesh = mesh
         self.interval = int(interval)
         self.dtype = dtype
@@ -65,6 +69,15 @@ class FrameRecorder:
             self.streamlines = opts
         self.lines: list[np.ndarray] = []
         self.lines_npts: list[np.ndarray] = []
+        # True: every channel of the simulation; else the recorded channels' indices
+        self.dye_channels = dyes if isinstance(dyes, bool) else _dye_indices(dyes)
+        self.dyes: list[np.ndarray] = []
+
+    def _channels(self, sim):
+        """The indices of the channels to record from `sim`."""
+        if self.dye_channels is True:
+            return list(range(sim.dyes_info()[0]))
+        return list(self.dye_channels or ())
 
     def record_lines(self, sim):
         """The streamlines of `sim`'s current velocity, for the frame just recorded."""
@@ -84,7 +97,11 @@ class FrameRecorder:
         W, H = self.raster
         color = sim.scheme == "color"
         fields = (("c", "u") if color else ("u",)) + (("vorticity",) if self.vorticity else ())
-        img = sim.raster(W, H, fields=fields, window=self.window)
+        chans = [f"dye{k}" for k in self._channels(sim)] if self.dye_channels else []
+        img = sim.raster(W, H, fields=fields + tuple(chans), window=self.window)
+        if self.dye_channels:
+            self.dyes.append(np.stack([np.asarray(img[f], dtype=np.float32) for f in chans]) if chans
+                             else np.zeros((0, H, W), dtype=np.float32))
         self.steps.append(int(step))
         self.dye.append(np.asarray(img["c"], dtype=np.float32) if color else None)
         self.vel.append(np.asarray(img["u"], dtype=np.float32))
@@ -108,6 +125,8 @@ class FrameRecorder:
                 else:
                     self.record(r, sim.c if sim.scheme == "color" else None, sim.u,
                                 sim.vorticity if self.vorticity else None)
+                    if self.dye_channels:
+                        self.dyes.append(np.array(sim.dyes[self._channels(sim)], dtype=self.dtype, copy=True))
                 if self.streamlines is not None:
                     self.record_lines(sim)
         return stats
@@ -116,10 +135,30 @@ class FrameRecorder:
         return len(self.steps)
 
 
+def _dye_indices(dyes):
+    """The channel indices named by a recorder's dyes= list ("dye3" or 3)."""
+    from .solver import dye_field
+    from . import _lib
+
+    out = []
+    for f in ([dyes] if isinstance(dyes, (str, int, np.integer)) else list(dyes)):
+        if isinstance(f, str):
+            e = dye_field(f)
+            if e is None:
+                raise ValueError(f"unknown dye channel {f!r}: 'dye0' .. 'dye{_lib.MAX_DYES - 1}'")
+            out.append(e - _lib.F_DYE0)
+        else:
+            if not 0 <= int(f) < _lib.MAX_DYES:
+                raise ValueError(f"dye channel index {f} outside 0 .. {_lib.MAX_DYES - 1}")
+            out.append(int(f))
+    return out
+
+
 def save_npz(rec: FrameRecorder, path):
     """The raw frames.  Raster frames: `vel` (frames, 2, H, W), `dye` (frames, H, W) and `window`
     (x0, y0, x1, y1) instead of the mesh.  A recorder with vorticity frames adds `vort` (frames, H, W) or
-    (frames, N); one with streamlines `lines` (frames, lines, nsteps + 1, 2) and `lines_npts` (frames, lines)."""
+    (frames, N); one with streamlines `lines` (frames, lines, nsteps + 1, 2) and `lines_npts` (frames, lines); one
+    with dye channels `dyes` (frames, K, N) or (frames, K, H, W)."""
     if getattr(rec, "raster", None) is not None:
         W, H = rec.raster
         d = dict(steps=np.array(rec.steps), window=np.array(rec.window or (0.0, 0.0, 1.0, 1.0), dtype=np.float64),
@@ -134,6 +173,8 @@ def save_npz(rec: FrameRecorder, path):
     if getattr(rec, "lines", None):
         d["lines"] = np.stack(rec.lines)
         d["lines_npts"] = np.stack(rec.lines_npts)
+    if getattr(rec, "dyes", None):
+        d["dyes"] = np.stack(rec.dyes)
     np.savez_compressed(path, **d)
 
 

@@ -163,6 +163,26 @@ def advect_semilagrange(c, u, DT, nodes=None, triangles=None):
     return nf.astype(bool)
 
 
+def advect_semilagrange_multi(C, u, DT, nodes=None, triangles=None):
+    """advect_semilagrange of the K fields C (K, N), K = 1 .. 16, at once (pucfem_sl_advect_multi): one back-trace
+    and one point location per node for all of them, every field's bits those of advect_semilagrange alone.
+    In place on C like the reference (C[:] = C_new); returns the not-found mask (N,), the same for every field."""
+    if nodes is None or triangles is None:
+        m = _mesh_or_global(None)
+        nodes, triangles = m.coords, m.triangles
+    ctx = context_for(nodes, triangles)
+    cin = np.ascontiguousarray(C, dtype=np.float64)
+    if cin.ndim != 2 or cin.shape[1] != len(nodes):
+        raise ValueError(f"advect_semilagrange_multi: C must have shape (K, {len(nodes)})")
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros_like(cin)
+    nf = np.zeros(cin.shape[1], dtype=np.int32)
+    _lib.check(ctx.L.pucfem_sl_advect_multi(ctx.h, cin.shape[0], _lib.dptr(cin), _lib.dptr(uu), float(DT),
+                                            _lib.dptr(out), _lib.iptr(nf)), ctx.h)
+    C[:] = out
+    return nf.astype(bool)
+
+
 def buildStiffnessMatrix(nodes, triangles, g_source=1.0):
     """StokesColor.py:98-128: (A, -B) with B = 0 (the reference never fills it)."""
     ctx = context_for(nodes, triangles)

@@ -24,16 +24,31 @@ FLOW_KEYS = ("max_vorticity", "enstrophy", "kinetic_energy", "max_speed")
 _SAMPLE_NCOMP = {f: n for f, n in SAMPLE_FIELDS.values()}
 
 
+def dye_field(name):
+    """The pucfem_field value of a dye channel's name "dye0" .. "dye15" (PUCFEM_F_DYE0 + k); None for a name that is
+    not of that form at all, ValueError for "dye" followed by anything but a channel index below 16."""
+    if not (isinstance(name, str) and name.startswith("dye")):
+        return None
+    k = name[3:]
+    if not (k.isascii() and k.isdigit() and str(int(k)) == k and int(k) < _lib.MAX_DYES):
+        raise ValueError(f"unknown field {name!r}: the dye channels are 'dye0' .. 'dye{_lib.MAX_DYES - 1}'")
+    return _lib.F_DYE0 + int(k)
+
+
 def _sample_spec(fields):
-    """(names, enum array, components) of a field list given by name ("u", "c", ...) or pucfem_field value."""
+    """(names, enum array, components) of a field list given by name ("u", "c", "dye3", ...) or pucfem_field
+    value."""
     if isinstance(fields, (str, int, np.integer)):
         fields = (fields,)
     names, ids, ncomp = [], [], []
     for f in fields:
         if isinstance(f, str):
-            if f not in SAMPLE_FIELDS:
-                raise ValueError(f"unknown field {f!r}: one of {sorted(SAMPLE_FIELDS)}")
-            e, n = SAMPLE_FIELDS[f]
+            if f not in SAMPLE_FIELDS and dye_field(f) is not None:
+                e, n = dye_field(f), 1
+            elif f not in SAMPLE_FIELDS:
+                raise ValueError(f"unknown field {f!r}: one of {sorted(SAMPLE_FIELDS)} or 'dye0' .. 'dye15'")
+            else:
+                e, n = SAMPLE_FIELDS[f]
         else:
             e = int(f)
             n = _SAMPLE_NCOMP.get(e, 1)  # (a field the library refuses: it reports the error)
@@ -432,6 +447,26 @@ class Context:
         self._c(self.L.pucfem_tracer_info(self.h, -1 if member is None else int(member), o))
         return dict(tracers=o[0], eaten=o[1], nonfinite=o[2], steps=o[3], blocks=o[4], threads=o[5])
 
+    def dyes_info(self):
+        """The context's dye channels (pucfem_dyes_info): their number, the channel steps since they were set, the
+        not-found rows of the last channel launch and the device bytes held for them."""
+        o = (ct.c_int64 * 4)()
+        self._c(self.L.pucfem_dyes_info(self.h, o))
+        return dict(channels=o[0], steps=o[1], notfound=o[2], bytes=o[3])
+
+    def dyes_mixing(self):
+        """(K, 3): (I, mu, var) of every dye channel over marker == 0 (pucfem_dyes_mixing)."""
+        K = self.dyes_info()["channels"]
+        out = np.zeros((K, 3))
+        self._c(self.L.pucfem_dyes_mixing(self.h, _lib.dptr(out) if K else None))
+        return out
+
+    def dyes_probe(self, nch, iters=10):
+        """Kernel time of one channel launch with nch channels (pucfem_dyes_probe; tools/dye_bench.py)."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_dyes_probe(self.h, int(nch), int(iters), o))
+        return dict(kernel_ms=o[0], algo_bytes=o[1])
+
     def flow_info(self, member=None):
         """Flow summaries of the current u, reduced on the device (pucfem_flow_info; one launch, four doubles
         copied): max |vorticity|, the enstrophy 1/2 sum w vorticity^2, the kinetic energy 1/2 sum w |u|^2 and the
@@ -579,6 +614,35 @@ class StokesSimulation:
 
     def field(self, f, ncomp=1):
         return self.ctx.get_field(f, (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,))
+
+    @property
+    def dyes(self):
+        """(K, N) the dye channels: extra dye fields advected beside c with every step's final u, the departure
+        point and its triangle found once per node for all of them.  Channel k holds the bits c would hold in a run
+        started from c = channel k.  Setting them (K = 0 .. 16 rows; dye_patterns gives the reference's three starts)
+        resets the channel step count; an empty array removes them."""
+        K = self.ctx.dyes_info()["channels"]
+        return self.ctx.get_field(_lib.F_DYES, (K, self.mesh.N))
+
+    @dyes.setter
+    def dyes(self, v):
+        a = np.ascontiguousarray(v, dtype=np.float64)
+        if a.size and (a.ndim != 2 or a.shape[1] != self.mesh.N):
+            raise ValueError(f"dyes must have shape (K, {self.mesh.N})")
+        if a.size == 0:
+            self.ctx._c(self.ctx.L.pucfem_set_field(self.ctx.h, _lib.F_DYES, None, 0))
+        else:
+            self.ctx.set_field(_lib.F_DYES, a)
+
+    def dye_mixing(self):
+        """(K, 3): mixing_index (StokesColor.py:391-403) (I, mu, var) of every dye channel over marker == 0, reduced
+        on the device when called."""
+        return self.ctx.dyes_mixing()
+
+    def dyes_info(self):
+        """Context.dyes_info of this run as (channels, steps, notfound, bytes)."""
+        d = self.ctx.dyes_info()
+        return d["channels"], d["steps"], d["notfound"], d["bytes"]
 
     @property
     def vorticity(self):
@@ -939,6 +1003,29 @@ class HeatSimulation:
         self.ctx.close()
 
 
+DYE_PATTERNS = ("half", "stripe", "blob")
+
+
+def dye_patterns(mesh: Mesh, names=DYE_PATTERNS):
+    """(len(names), N) the reference's three dye starts, each 0 / 1 per node, for StokesSimulation.dyes:
+      "half"   c = 1 where x < 0.5                                  (code/StokesColor.py:493-495)
+      "stripe" c = 1 where |x - 0.2| < 0.05 / 2                     (scripts/good_visualization2.py:520-524)
+      "blob"   c = 1 where |(x, y) - (0.5, 0.75)| < 0.1             (scripts/good_visualization.py:555-559)
+    with the reference's expressions.  On a coarse mesh the 0.05-wide stripe can catch no node (mesh.1: check)."""
+    X = np.asarray(mesh.coords, dtype=np.float64)
+    out = np.zeros((len(names), len(X)))
+    for k, name in enumerate(names):
+        if name == "half":
+            out[k, X[:, 0] < 0.5] = 1.0
+        elif name == "stripe":
+            out[k, np.where(np.abs(X[:, 0] - 0.2) < 0.05 / 2.0)[0]] = 1.0
+        elif name == "blob":
+            out[k, np.linalg.norm(X - np.array([0.5, 0.75]), axis=1) < 0.1] = 1.0
+        else:
+            raise ValueError(f"unknown dye pattern {name!r}: one of {DYE_PATTERNS}")
+    return out
+
+
 @dataclass
 class Result:
     scheme: str
@@ -951,21 +1038,29 @@ class Result:
     capture_step: np.ndarray | None = None  # scheme 'food': per tracer, the 1-based step it was eaten in (-1: never)
     scalar: np.ndarray | None = None
     stats: list = field(default_factory=list)
+    dyes: np.ndarray | None = None  # scheme 'color' with dyes=: the final dye channels (K, N)
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
-          tol: Tolerances | None = None, log=None):
+          tol: Tolerances | None = None, log=None, dyes=None):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
     backward Euler), 'poisson' = poisson.py (one steady solve).  `log`, if given, receives the
-    reference's per-step print line (StokesColor.py:586 / StokesFood.py:505)."""
+    reference's per-step print line (StokesColor.py:586 / StokesFood.py:505).  dyes (scheme 'color'): (K, N) dye
+    channels advected beside c (StokesSimulation.dyes); the result's `dyes` holds them after the last step."""
+    if dyes is not None and scheme != "color":
+        raise ValueError("dyes belong to scheme 'color'")
     if scheme in ("color", "food"):
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
         sim = StokesSimulation(mesh, bc, dt, scheme, device, tol)
+        if dyes is not None:
+            sim.dyes = dyes
         st = sim.step(steps) if steps else []
         res = Result(scheme, steps, u=sim.u, p=sim.field(_lib.F_P), stats=st)
+        if dyes is not None:
+            res.dyes = sim.dyes
         if scheme == "color":
             res.c = sim.c
             if log:
