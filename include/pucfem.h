@@ -508,6 +508,35 @@ int pucfem_visc_interval(void* ctx, double* out2);
    quotient (0: estimated on the host), the host 30-step power iteration's quotient on the level's fp64
    operator (computed by this call), the host Gershgorin bound]; lmax = min(Gershgorin, 1.1 x quotient). */
 int pucfem_mg_lmax(void* ctx, int32_t level, double* out4);
+/* One piece of the pressure multigrid's V-cycle (the preconditioner of the np.linalg.solve sites
+   StokesColor.py:555,569) on given vectors, launched by the very members the cycle calls.  Test infrastructure
+   (tests/test_gpu_mg_cycle.py compares every piece with an fp64 restatement); not on the step path.
+   Vectors are fp64 in caller numbering of their level (0 = coarsest .. levels); they are rounded to the cycle's
+   type (fp32 with mg_single, else fp64) on upload.  Only the cycle's scratch buffers are written: a run continues
+   bit for bit.  Pieces (level l; unused vectors may be null):
+     RESID     out = b - A_l x                                   l >= 1
+     SMOOTH0   out = the pre-smoothing (mg_degree steps from a zero guess) for right-hand side b      l >= 1
+     SMOOTHX   out = the post-smoothing (mg_post or mg_degree steps) from x for b; no z, no <r, z>    l >= 1
+     RESTRICT  out (level l - 1) = R x, x on level l                                                  l >= 1
+     PROLONG   out = x + P b, b on level l - 1, x on level l                                          l >= 1
+     COARSE    out = the dense coarse solve of b                                                      l == 0
+     CYCLE     out = the V-cycle from level l down for b                                              l >= 0
+     PRECOND   out = z = M^-1 b as the PCG calls it, rz[0] = the reduced <b, z>                      l == levels
+   A built single-rank device context with a multigrid hierarchy: PUCFEM_ESTATE before the build and on a host-only
+   context, PUCFEM_EINVAL without a hierarchy, on a multi-rank context, for a piece / level that does not exist or
+   a null vector the piece needs. */
+enum {
+  PUCFEM_MG_RESID = 0,
+  PUCFEM_MG_SMOOTH0 = 1,
+  PUCFEM_MG_SMOOTHX = 2,
+  PUCFEM_MG_RESTRICT = 3,
+  PUCFEM_MG_PROLONG = 4,
+  PUCFEM_MG_COARSE = 5,
+  PUCFEM_MG_CYCLE = 6,
+  PUCFEM_MG_PRECOND = 7
+};
+int pucfem_mg_probe(void* ctx, int32_t piece, int32_t level, const double* b, const double* x, double* out,
+                    double* rz);
 /* The pressure solves' projected initial guesses (successive right-hand sides, pucfem_params.proj_k; the solves
    replace np.linalg.solve at StokesColor.py:555,569): out4 = [bases re-seeded so far, bases restarted by the guess
    monitor (a projected guess > 50x worse than the best of its basis' last 8), the last projected guess's relative residual

@@ -1875,68 +1875,87 @@ struct Ctx {
     }
     return cur;
   }
-  // z = M^-1 r on level l (b = r_l); the finest level passes rdot = r for the <r, z> partials and
-  // writes z (fp64) directly from its last smoothing step
-  // (every level smooths with the finest level's degrees: fewer steps on the latency-bound coarse levels
-  // cost more pressure iterations than their launches save, round 3 r8e / r8f)
-  template <typename T, typename TB>
-  T* vcycle(int l, const TB* b, const double* rdot, double* part) {
-    MgLevel& L = mg[l];
-    MgBufs<T>& B = bufs<T>(L);
+  // The cycle's pieces, one launch site each: vcycle strings them together and pucfem_mg_probe runs them one at a
+  // time against a reference.
+  template <typename T>
+  struct MgAt {
+    MgLevel& L;
+    MgBufs<T>& B;
+    const DevSell& A;
+    const HFace& hf;
+    bool finest;
+  };
+  template <typename T>
+  MgAt<T> mg_at(int l) {
     const bool finest = l == (int)mg.size() - 1;
-    const DevSell& A = finest ? dPp : L.dA;
-    const HFace& hf = finest ? fP : L.hA;
-    T* xa = B.x;
-    T* xb = B.x2;
-    if (l == 0) {
-      if constexpr (std::is_same<T, TB>::value) {
-        // coarse solve: dense pseudo-inverse (replicated on every rank of a multi-rank run)
-        const i64 N0 = (i64)L.ord.new2old.size();
-        const dim3 g((unsigned)std::min<i64>(4096, (N0 + 3) / 4));
-        algo_bytes += 8.0 * (double)N0 * (double)N0 + 2.0 * sizeof(T) * (double)N0;
-        hipLaunchKernelGGL(k_dense_mv<T>, g, dim3(BS), 0, st, N0, (const double*)dAinv, b, xa, ctl);
-        KCHK();
-        return xa;
-      } else {
-        throw Error(PUCFEM_ESTATE, "multigrid hierarchy has a single level");
-      }
-    }
+    return MgAt<T>{mg[l], bufs<T>(mg[l]), finest ? dPp : mg[l].dA, finest ? fP : mg[l].hA, finest};
+  }
+  // coarse solve (level 0): dense pseudo-inverse (replicated on every rank of a multi-rank run)
+  template <typename T>
+  T* mg_coarse(const T* b) {
+    MgLevel& L = mg[0];
+    T* xa = bufs<T>(L).x;
+    const i64 N0 = (i64)L.ord.new2old.size();
+    const dim3 g((unsigned)std::min<i64>(4096, (N0 + 3) / 4));
+    algo_bytes += 8.0 * (double)N0 * (double)N0 + 2.0 * sizeof(T) * (double)N0;
+    hipLaunchKernelGGL(k_dense_mv<T>, g, dim3(BS), 0, st, N0, (const double*)dAinv, b, xa, ctl);
+    KCHK();
+    return xa;
+  }
+  // pre-smoothing from a zero guess
+  template <typename T, typename TB>
+  T* mg_pre(int l, const TB* b) {
+    const MgAt<T> m = mg_at<T>(l);
     const int pre = prm.mg_degree;
     if constexpr (std::is_same<T, TB>::value) {
       // coarse levels: the fused first smoothing step reads b at ghost columns
-      if (pre >= 2) mg_halo(L, const_cast<T*>(b));
+      if (pre >= 2) mg_halo(m.L, const_cast<T*>(b));
     }
-    T* x = mg_smooth<T, TB>(L, A, hf, B, b, nullptr, xa, xb, false, nullptr, nullptr, pre);
-    mg_halo(L, x);
+    return mg_smooth<T, TB>(m.L, m.A, m.hf, m.B, b, nullptr, m.B.x, m.B.x2, false, nullptr, nullptr, pre);
+  }
+  // res = b - A x (into the level's res buffer)
+  template <typename T, typename TB>
+  void mg_resid(int l, const TB* b, const T* x) {
+    const MgAt<T> m = mg_at<T>(l);
+    MgLevel& L = m.L;
+    const MgBufs<T>& B = m.B;
+    const DevSell& A = m.A;
     // residual: matrix entries, x gathered once, b read, res written; deep halos: also on the ghost rows one layer
     // out, which the restriction gathers (no exchange of the residual)
     const bool rg = dist() && L.res_deep && (deep_mask & 2);
     const DevSell& Ar = rg ? A.with_ghosts() : A;
     const double bytes_res = (B.val_bytes() + A.idx_bytes()) * (double)A.nnz + A.row_bytes() * (double)A.nrows +
                              (double)A.own() * (2.0 * sizeof(T) + sizeof(TB));
-    const FaceDev fr = hf.full();
+    const FaceDev fr = m.hf.full();
     B.with_vals([&](auto* val) {
       using VT = std::remove_const_t<std::remove_pointer_t<decltype(val)>>;
       with_c16(A, [&](auto c16) {
-        if (finest)
+        if (m.finest)
           klaunch(5, bytes_res, k_resid<T, TB, VT, decltype(c16)::value, 1>, dim3(grid_full(fr, Ar)), dim3(BS),
-                  Ar.view(), fr, val, b, (const T*)x, B.res, (const int*)ctl);
+                  Ar.view(), fr, val, b, x, B.res, (const int*)ctl);
         else
           klaunch(-1, bytes_res, k_resid<T, TB, VT, decltype(c16)::value, 0>, dim3(grid_full(fr, Ar)), dim3(BS),
-                  Ar.view(), fr, val, b, (const T*)x, B.res, (const int*)ctl);
+                  Ar.view(), fr, val, b, x, B.res, (const int*)ctl);
       });
     });
     KCHK();
     if (!rg) mg_halo(L, B.res);
+  }
+  // level l's res -> level l - 1's b
+  template <typename T>
+  void mg_restrict(int l) {
+    const MgAt<T> m = mg_at<T>(l);
+    MgLevel& L = m.L;
+    const MgBufs<T>& B = m.B;
     MgLevel& C = mg[l - 1];
     MgBufs<T>& CB = bufs<T>(C);
     const bool gather = C.rep && !L.rep && dist();  // into the finest replicated level
     T* cb = gather ? CB.b + L.r_r0 : CB.b;
     // restriction: entries (value + column), fine residual read once, coarse rhs written
-    const FaceDev frs = L.hR.full(), fpr = L.hPr.full();
-    klaunch(finest ? 6 : -1,
+    const FaceDev frs = L.hR.full();
+    klaunch(m.finest ? 6 : -1,
             (double)(sizeof(T) + 4) * (double)L.dR.nnz + L.dR.row_bytes() * (double)L.dR.nrows +
-                (double)sizeof(T) * (double)(A.own() + L.dR.nrows + L.hR.rows),
+                (double)sizeof(T) * (double)(m.A.own() + L.dR.nrows + L.hR.rows),
             k_transfer<T>, dim3(grid_full(frs, L.dR)), dim3(BS), L.dR.view(), frs, (const T*)B.Rval, (const T*)B.res,
             cb, 0, (const int*)ctl);
     KCHK();
@@ -1945,26 +1964,62 @@ struct Ctx {
       for (int r = 0; r < world; ++r) comm->bcast(CB.b + C.rs[r], C.rs[r + 1] - C.rs[r], r, st);
       comm->group_end(st);
     }
-    T* xc = vcycle<T, T>(l - 1, CB.b, nullptr, nullptr);
+  }
+  // x += P xc; returns pr_deep (the prolongation also ran on this level's ghost rows)
+  template <typename T>
+  bool mg_prolong(int l, T* xc, T* x) {
+    const MgAt<T> m = mg_at<T>(l);
+    MgLevel& L = m.L;
+    MgLevel& C = mg[l - 1];
     if (!(dist() && L.xc_deep && (deep_mask & 4))) mg_halo(C, xc);  // (xc_deep: level l - 1's last step wrote its ghosts one layer out)
     // prolongation: entries, coarse x read once, fine x read + written; pr_deep: also on this level's ghost rows (x
     // there is current since the exchange before the residual), so the post-smoothing starts without an exchange
     const bool pg = dist() && L.pr_deep && (deep_mask & 8) && ((deep_mask & 4) || C.rep);
     const DevSell& Apr = pg ? L.dPr.with_ghosts() : L.dPr;
-    klaunch(finest ? 7 : -1,
+    const FaceDev fpr = L.hPr.full();
+    klaunch(m.finest ? 7 : -1,
             (double)(sizeof(T) + 4) * (double)L.dPr.nnz + L.dPr.row_bytes() * (double)L.dPr.nrows +
-                (double)sizeof(T) * (double)(2 * A.own() + L.dR.nrows + L.hR.rows),
-            k_transfer<T>, dim3(grid_full(fpr, Apr)), dim3(BS), Apr.view(), fpr, (const T*)B.Prval, (const T*)xc,
+                (double)sizeof(T) * (double)(2 * m.A.own() + L.dR.nrows + L.hR.rows),
+            k_transfer<T>, dim3(grid_full(fpr, Apr)), dim3(BS), Apr.view(), fpr, (const T*)m.B.Prval, (const T*)xc,
             x, 1, (const int*)ctl);
     KCHK();
-    T* other = (x == xa) ? xb : xa;
+    return pg;
+  }
+  // post-smoothing from x; toz: the last step writes z (the cycle's finest level), and nullptr is returned
+  template <typename T, typename TB>
+  T* mg_post(int l, const TB* b, T* x, bool toz, const double* rdot, double* part, bool pg = false) {
+    const MgAt<T> m = mg_at<T>(l);
+    MgLevel& L = m.L;
+    // the smoother rotates through the level's two x buffers, the first being x's own.  After a pre-smoothing that
+    // ended in a general pair (mg_degree 5, 9, ...) x is the pairs' extra buffer: taking it for one of the two made
+    // the next pair write x_{a+1} over the x_a it reads (tests/test_gpu_mg_cycle.py, V(5,4))
+    T* first = (x == m.B.x2) ? m.B.x2 : m.B.x;
+    T* other = (first == m.B.x) ? m.B.x2 : m.B.x;
     const int post = prm.mg_post > 0 ? prm.mg_post : prm.mg_degree;
     // the last step on the ghost rows one layer out where its consumer gathers them: the prolongation into level
     // l + 1 (xc_deep), and z for the PCG's A z on the finest level -- there the ghost rows must repeat the owners'
     // arithmetic bit for bit (the outer fp64 PCG needs w = A z of ONE vector z: its recurrences s = A p and
     // r = b - A y hold only then), which face_ghost_rows ensures: face-interior ghost rows are their face stencils
-    const bool last_g = dist() && L.deep && (deep_mask & 4) && (finest || mg[l + 1].xc_deep);
-    return mg_smooth<T, TB>(L, A, hf, B, b, x, x, other, finest, rdot, part, post, last_g, pg);
+    const bool last_g = dist() && L.deep && (deep_mask & 4) && (m.finest || mg[l + 1].xc_deep);
+    return mg_smooth<T, TB>(L, m.A, m.hf, m.B, b, x, first, other, toz, rdot, part, post, last_g, pg);
+  }
+  // z = M^-1 r on level l (b = r_l); the finest level passes rdot = r for the <r, z> partials and
+  // writes z (fp64) directly from its last smoothing step
+  // (every level smooths with the finest level's degrees: fewer steps on the latency-bound coarse levels
+  // cost more pressure iterations than their launches save, round 3 r8e / r8f)
+  template <typename T, typename TB>
+  T* vcycle(int l, const TB* b, const double* rdot, double* part) {
+    if (l == 0) {
+      if constexpr (std::is_same<T, TB>::value) return mg_coarse<T>(b);
+      else throw Error(PUCFEM_ESTATE, "multigrid hierarchy has a single level");
+    }
+    T* x = mg_pre<T, TB>(l, b);
+    mg_halo(mg[l], x);
+    mg_resid<T, TB>(l, b, (const T*)x);
+    mg_restrict<T>(l);
+    T* xc = vcycle<T, T>(l - 1, bufs<T>(mg[l - 1]).b, nullptr, nullptr);
+    const bool pg = mg_prolong<T>(l, xc, x);
+    return mg_post<T, TB>(l, b, x, l == (int)mg.size() - 1, rdot, part, pg);
   }
   // z = M^-1 r (finest level), <r, z> partials in part_d + 2 MAXB.  The fp32 cycle reads r32 (owned
   // rows written by k_cg_init / k_cg_upd; its ghosts are exchanged by the cycle); the fp64 one r itself
@@ -1977,6 +2032,16 @@ struct Ctx {
       halo(cg_r[0]);
       vcycle<double, double>((int)mg.size() - 1, cg_r[0], cg_r[0], rz_part);
     }
+  }
+  // precondition() as the standard PCG calls it, with <r, z> reduced (nb: the grid of the cycle's last step)
+  Red precondition_rz(int nb) {
+    ro_rz = ro(redbuf + 32, CNT_RZ, 1);
+    precondition();
+    ro_rz = RedOut{};
+    Red rz{redbuf + 32, 1, 1};
+    if (ro(redbuf + 32, CNT_RZ, 1).out) red_done(redbuf + 32, 1, false);
+    else rz = reduce_global(part_d + 2 * MAXB, nb, 1, false, 4);
+    return rz;
   }
   // Chronopoulos-Gear PCG (k_cgcg_*): the multi-rank pressure solves, one all-reduce per iteration instead of three;
   // PUCFEM_CGCG=1 / 0 forces it on / off (measurement and test knob: the single-rank path keeps the standard form,
@@ -2183,12 +2248,7 @@ struct Ctx {
           if (pcg_trace) trace_pcg(which, it + 1);
           continue;
         }
-        ro_rz = ro(redbuf + 32, CNT_RZ, 1);
-        precondition();
-        ro_rz = RedOut{};
-        Red rz{redbuf + 32, 1, 1};
-        if (ro(redbuf + 32, CNT_RZ, 1).out) red_done(redbuf + 32, 1, false);
-        else rz = reduce_global(part_d + 2 * MAXB, nb, 1, false, 4);
+        const Red rz = precondition_rz(nb);
         if (!z_cur) {
           if (mg_single) mg_halo(mg.back(), z32);
           else halo(z);
@@ -4695,6 +4755,99 @@ void build(Ctx& c) {
 }  // namespace
 
 // =====================================================================================================
+// One piece of the multigrid cycle on caller-numbered fp64 vectors (see pucfem.h).  The vectors go into the
+// buffers the cycle itself uses (rounded to its type) and every launch is made by the member the cycle calls.
+template <typename T>
+void mg_probe_run(Ctx& c, int piece, int l, const double* b, const double* x, double* out, double* rz) {
+  const int Lv = (int)c.mg.size() - 1;
+  auto size_of = [&](int lv) { return (i64)c.mg[lv].ord.new2old.size(); };
+  std::vector<T> h;
+  auto up = [&](int lv, const double* src, T* dst) {
+    const Ordering& o = c.mg[lv].ord;
+    const i64 n = size_of(lv);
+    h.resize((size_t)n);
+    for (i64 g = 0; g < n; ++g) h[g] = (T)src[o.new2old[g]];
+    c.h2d(dst, h.data(), sizeof(T) * (size_t)n);
+    HIPCHK(hipStreamSynchronize(c.st));  // (h is reused)
+  };
+  auto down = [&](int lv, const T* src) {
+    const Ordering& o = c.mg[lv].ord;
+    const i64 n = size_of(lv);
+    h.resize((size_t)n);
+    c.d2h(h.data(), src, sizeof(T) * (size_t)n);
+    HIPCHK(hipStreamSynchronize(c.st));
+    for (i64 g = 0; g < n; ++g) out[o.new2old[g]] = (double)h[g];
+  };
+  // the right-hand side of level lv where the cycle reads it
+  auto rhs = [&](int lv) -> T* {
+    if (lv < Lv) return bufs<T>(c.mg[lv]).b;
+    if constexpr (std::is_same<T, float>::value) return c.r32;
+    else return c.cg_r[0];
+  };
+  auto zbuf = [&]() -> T* {
+    if constexpr (std::is_same<T, float>::value) return c.z32;
+    else return c.z;
+  };
+  MgBufs<T>& B = bufs<T>(c.mg[l]);
+  // the solves' control words: a converged solve leaves its flag set, and every cycle kernel returns at once then
+  int ctl0[6];
+  c.d2h(ctl0, c.ctl, sizeof(ctl0));
+  HIPCHK(hipMemsetAsync(c.ctl, 0, 2 * sizeof(int), c.st));
+  switch (piece) {
+    case PUCFEM_MG_RESID:
+      up(l, b, rhs(l));
+      up(l, x, B.x);
+      c.mg_resid<T, T>(l, rhs(l), (const T*)B.x);
+      down(l, B.res);
+      break;
+    case PUCFEM_MG_SMOOTH0:
+      up(l, b, rhs(l));
+      down(l, c.mg_pre<T, T>(l, rhs(l)));
+      break;
+    case PUCFEM_MG_SMOOTHX:
+      up(l, b, rhs(l));
+      up(l, x, B.x);
+      down(l, c.mg_post<T, T>(l, rhs(l), B.x, false, nullptr, nullptr));
+      break;
+    case PUCFEM_MG_RESTRICT:
+      up(l, x, B.res);
+      c.mg_restrict<T>(l);
+      down(l - 1, bufs<T>(c.mg[l - 1]).b);
+      break;
+    case PUCFEM_MG_PROLONG:
+      up(l - 1, b, bufs<T>(c.mg[l - 1]).x);
+      up(l, x, B.x);
+      c.mg_prolong<T>(l, bufs<T>(c.mg[l - 1]).x, B.x);
+      down(l, B.x);
+      break;
+    case PUCFEM_MG_COARSE:
+      up(0, b, rhs(0));
+      down(0, c.mg_coarse<T>(rhs(0)));
+      break;
+    case PUCFEM_MG_CYCLE: {
+      up(l, b, rhs(l));
+      const T* r = c.vcycle<T, T>(l, rhs(l), nullptr, nullptr);
+      down(l, r ? r : zbuf());  // (the finest level's last step writes z)
+      break;
+    }
+    default: {  // PUCFEM_MG_PRECOND
+      const i64 n = size_of(Lv);
+      std::vector<double> rd((size_t)n);
+      for (i64 g = 0; g < n; ++g) rd[g] = b[c.mg[Lv].ord.new2old[g]];
+      c.h2d(c.cg_r[0], rd.data(), sizeof(double) * (size_t)n);
+      HIPCHK(hipStreamSynchronize(c.st));
+      if constexpr (std::is_same<T, float>::value) up(Lv, b, c.r32);
+      const Red red = c.precondition_rz(Ctx::grid_part(c.fP.part(), c.dPp));
+      c.d2h(rz, red.p, sizeof(double));
+      down(Lv, zbuf());
+      break;
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c.st));
+  c.h2d(c.ctl, ctl0, sizeof(ctl0));
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+
 extern "C" {
 
 int pucfem_abi_version(void) { return PUCFEM_ABI_VERSION; }
@@ -6752,6 +6905,29 @@ int pucfem_comm_selftest(void* ctx, double* out4) {
     out4[1] = e1;
     out4[2] = e2;
     out4[3] = dynamic_cast<NcclComm*>(c.comm.get()) ? 2 : 1;
+  });
+}
+
+int pucfem_mg_probe(void* ctx, int32_t piece, int32_t level, const double* b, const double* x, double* out,
+                    double* rz) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.need_built();
+    require(c.use_mg && c.mg.size() >= 2, "mg_probe needs a context built with a multigrid hierarchy");
+    if (c.host_only) throw Error(PUCFEM_ESTATE, "mg_probe runs the cycle's kernels: it needs a device context");
+    require(!c.dist(), "mg_probe needs a single-rank context");
+    const int Lv = (int)c.mg.size() - 1;
+    require(piece >= PUCFEM_MG_RESID && piece <= PUCFEM_MG_PRECOND, "piece");
+    const bool needs_b = piece != PUCFEM_MG_RESTRICT;
+    const bool needs_x = piece == PUCFEM_MG_RESID || piece == PUCFEM_MG_SMOOTHX || piece == PUCFEM_MG_RESTRICT ||
+                         piece == PUCFEM_MG_PROLONG;
+    require(out != nullptr && (!needs_b || b != nullptr) && (!needs_x || x != nullptr), "null vector");
+    if (piece == PUCFEM_MG_COARSE) require(level == 0, "the coarse solve is level 0");
+    else if (piece == PUCFEM_MG_PRECOND) require(level == Lv && rz != nullptr, "precondition is the finest level, with rz");
+    else if (piece == PUCFEM_MG_CYCLE) require(level >= 0 && level <= Lv, "level");
+    else require(level >= 1 && level <= Lv, "level (this piece exists on levels >= 1)");
+    if (c.mg_single) mg_probe_run<float>(c, piece, level, b, x, out, rz);
+    else mg_probe_run<double>(c, piece, level, b, x, out, rz);
   });
 }
 

@@ -433,6 +433,38 @@ class Context:
         self._c(self.L.pucfem_mg_lmax(self.h, int(level), o))
         return dict(lmax=o[0], lam_device=o[1], lam_host=o[2], gershgorin=o[3])
 
+    MG_PIECES = ("resid", "smooth0", "smoothx", "restrict", "prolong", "coarse", "cycle", "precondition")
+
+    def mg_level_size(self, level):
+        """Nodes of multigrid level `level` (0 = coarsest)."""
+        n, nnz = ct.c_int64(), ct.c_int64()
+        self._c(self.L.pucfem_host_get_csr(self.h, 100 + 3 * int(level), ct.byref(n), ct.byref(nnz), None, None, None))
+        return n.value
+
+    def mg_probe(self, piece, level, b=None, x=None):
+        """One piece of the pressure V-cycle on caller-numbered fp64 vectors (pucfem_mg_probe; test
+        infrastructure).  piece: a name of MG_PIECES.  b, x: the piece's inputs as include/pucfem.h lists them
+        (b lives on level - 1 for "prolong", the output on level - 1 for "restrict").  Returns the output vector,
+        and for "precondition" the pair (z, <r, z>)."""
+        k = self.MG_PIECES.index(piece)
+        level = int(level)
+        # (sizes: the library reads and writes whole level vectors; a level that does not exist is its error)
+        lv = {"restrict": (None, level, level - 1), "prolong": (level - 1, level, level)}.get(piece, (level, level, level))
+        if piece == "coarse":
+            lv = (0, None, 0)
+        need = [None if q is None or q < 0 else self.mg_level_size(q) for q in lv]
+        b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+        x = None if x is None else np.ascontiguousarray(x, dtype=np.float64)
+        for name, v, n in (("b", b, need[0]), ("x", x, need[1])):
+            if v is not None and n is not None and v.shape != (n,):
+                raise ValueError(f"mg_probe {piece}: {name} has shape {v.shape}, level vector is ({n},)")
+        out = np.zeros(need[2] if need[2] is not None else 1)
+        rz = ct.c_double(0.0)
+        self._c(self.L.pucfem_mg_probe(self.h, k, int(level), None if b is None else _lib.dptr(b),
+                                       None if x is None else _lib.dptr(x), _lib.dptr(out),
+                                       ct.cast(ct.byref(rz), ct.POINTER(ct.c_double))))
+        return (out, rz.value) if piece == "precondition" else out
+
     def proj_info(self):
         """Projected pressure guesses (pucfem_proj_info): re-seeds, monitor restarts, last guess residuals."""
         o = (ct.c_double * 4)()

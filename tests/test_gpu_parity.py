@@ -11,6 +11,7 @@ from scipy.spatial import KDTree
 
 import oracle as O
 from conftest import has_gpu, load_pkg
+from mg_reference import synthetic_mesh
 
 pytestmark = pytest.mark.gpu
 
@@ -378,14 +379,16 @@ def test_viscous_chebyshev_post_check(monkeypatch):
     b.close()
 
 
-@pytest.mark.parametrize("refine", [3, 5])
+@pytest.mark.parametrize("mesh_name,refine", [("fine", 3), ("fine", 5), ("synthetic", 6)], ids=["3", "5", "synthetic-6"])
 @pytest.mark.parametrize("knob,key", [("PUCFEM_VISC_PAIR", "visc_step_pairs"), ("PUCFEM_MG_PAIR", "mg_step_pairs")])
-def test_step_pairs_equal_single_steps(monkeypatch, refine, knob, key):
+def test_step_pairs_equal_single_steps(monkeypatch, mesh_name, refine, knob, key):
     """Two Chebyshev steps in one pass on the face interiors (x_{a+1} in LDS, the skeleton rows in their
     own launches): the viscous solve's (k_vcheb_pair) and the finest multigrid level's smoothing
     (k_cheb_pair) do k_vcheb's / k_cheb's operations row by row, so the production run at L3 / L5 with
-    step pairs is bit-identical to the one that runs every step as its own launch."""
-    mesh = pf.load_mesh("fine", refine=refine)
+    step pairs is bit-identical to the one that runs every step as its own launch.  On `fine` every face
+    is one work item; the synthetic 24-face mesh at lattice size 64 has two items per face, whose windows
+    overlap and whose x_{a+1} halos come from the neighbouring item's rows."""
+    mesh = synthetic_mesh(refine) if mesh_name == "synthetic" else pf.load_mesh("fine", refine=refine)
     a = stokes(mesh, tol=S.Tolerances.production())
     monkeypatch.setenv(knob, "0")
     b = stokes(mesh, tol=S.Tolerances.production())
