@@ -879,6 +879,48 @@ struct Ctx {
       host_copy(static_cast<char*>(dst) + prev_off, stage[prev_k], prev_len);
     }
   }
+  // A caller-numbered host array <-> device buffers in internal numbering (to_internal / to_caller,
+  // pucfem_host.hpp): rows r0 .. r0 + n - 1 of `o`, comp values per row, `planes` whole fields on the caller's
+  // side; on the device the window alone, planes dense, comp interleaved in d0 or (pairs) split into d0 and d1.
+  // put is ordered on st and does not synchronise: h2d has consumed the staging vector when it returns (its
+  // small branch is a pageable hipMemcpyAsync, which the runtime completes before it returns; its large branch
+  // copies into the pinned chunks itself), so the vector may die here.  get returns with the data in dst (d2h
+  // waits for st).  pinned = false: the pageable copy at every size, for a run's u, u* and c, as before this layer: at 14 MB
+  // u measured slower through the pinned chunks (profiles/field_io_time.txt; larger sizes not measured).
+  template <class T, class S>
+  void put(const Ordering& o, i64 r0, i64 n, int comp, i64 planes, const S* src, T* d0, T* d1 = nullptr,
+           bool pinned = true) {
+    const i64 per = (d1 ? 1 : comp) * n, half = d1 ? planes * per : 0;
+    if (planes * per == 0) return;
+    std::vector<T> h((size_t)(planes * per + half));
+    to_internal(o, r0, n, comp, planes, comp * (i64)o.new2old.size(), src, per, h.data(), d1 ? h.data() + half : nullptr);
+    auto copy = [&](T* d, const T* s) {
+      if (pinned) h2d(d, s, sizeof(T) * (size_t)(planes * per));
+      else HIPCHK(hipMemcpyAsync(d, s, sizeof(T) * (size_t)(planes * per), hipMemcpyHostToDevice, st));
+    };
+    copy(d0, h.data());
+    if (d1) copy(d1, h.data() + half);
+  }
+  template <class T, class D>
+  void get(const Ordering& o, i64 r0, i64 n, int comp, i64 planes, D* dst, const T* d0, const T* d1 = nullptr,
+           bool pinned = true) {
+    const i64 per = (d1 ? 1 : comp) * n, half = d1 ? planes * per : 0;
+    if (planes * per == 0) return;
+    std::vector<T> h((size_t)(planes * per + half));
+    auto copy = [&](T* d, const T* s) {
+      if (pinned) return d2h(d, s, sizeof(T) * (size_t)(planes * per));
+      HIPCHK(hipMemcpyAsync(d, s, sizeof(T) * (size_t)(planes * per), hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+    };
+    copy(h.data(), d0);
+    if (d1) copy(h.data() + half, d1);
+    to_caller(o, r0, n, comp, planes, comp * (i64)o.new2old.size(), dst, per, h.data(), d1 ? h.data() + half : nullptr);
+  }
+  // the whole single-rank field / this rank's owned rows, in the context's own ordering
+  template <class T, class S>
+  void put_all(int comp, i64 planes, const S* src, T* d0, T* d1 = nullptr) { put(ord, 0, mesh.N, comp, planes, src, d0, d1); }
+  template <class T, class D>
+  void get_all(int comp, i64 planes, D* dst, const T* d0, const T* d1 = nullptr) { get(ord, 0, mesh.N, comp, planes, dst, d0, d1); }
   // int16 column deltas for a square operator's SELL (prm.idx32 = 0 and the band fits); nloc: the
   // local vector length (owned + ghost), the wrap modulus
   void attach_c16(const Sell& S, i64 nloc, DevSell& D) {
@@ -1089,11 +1131,7 @@ struct Ctx {
     }
     dye_steps = 0;
     dye_nb = 0;
-    if (K == 0) return;
-    std::vector<double> x((size_t)K * (size_t)N);
-    for (int k = 0; k < K; ++k)
-      for (i64 g = 0; g < N; ++g) x[(size_t)k * N + g] = buf[(size_t)k * N + ord.new2old[g]];
-    h2d(dye_cur, x.data(), sizeof(double) * x.size());
+    put_all(1, K, buf, dye_cur);
     HIPCHK(hipStreamSynchronize(st));
   }
   size_t dye_dev_bytes() const {
@@ -2451,6 +2489,50 @@ struct Ctx {
                          energy ? a : (const double*)nullptr, 0.0, (double*)nullptr, part, r);
     });
     KCHK();
+  }
+  // Where the owned rows of a one-component field lie (null: not such a field).  The fields the step does not store
+  // are formed first, on st, into dst() -- called only then: p / p2 kept in y (the slaves not copied), div u*, the
+  // final divergence (the implicit dye variant keeps its own copy) and the vorticity, from u (whose ghosts are
+  // current after every write of u).  pucfem_get_field forms them in place, the samplers in buffers of their own.
+  template <class Dst>
+  const double* formed(int32_t field, Dst&& dst) {
+    const bool stokes = scheme == PUCFEM_STOKES_COLOR || scheme == PUCFEM_STOKES_FOOD;
+    switch (field) {
+      case PUCFEM_F_P:
+      case PUCFEM_F_P2: {
+        const bool first = field == PUCFEM_F_P;
+        if (!p_from_y) return first ? p : p2;
+        double* s = dst();
+        hipLaunchKernelGGL(k_cg_fin, dim3(grid_ew(lp.n_own)), dim3(BS), 0, st, lp.n_own, 1, (const double*)nullptr,
+                           (const double*)(first ? yp : yp2), (const double*)nullptr, s, (double*)nullptr,
+                           (const int32_t*)dmaster_of);
+        KCHK();
+        return s;
+      }
+      case PUCFEM_F_DIV_STAR:
+      case PUCFEM_F_FINAL_DIV: {
+        const bool star = field == PUCFEM_F_DIV_STAR;
+        if (!stokes || (!star && dye_impl)) return star ? div_star : final_div;
+        double* s = dst();
+        div(star ? usx : ux, star ? usy : uy, s, false);
+        return s;
+      }
+      case PUCFEM_F_VORTICITY: {
+        if (!stokes) throw Error(PUCFEM_ESTATE, "vorticity needs a Stokes context");
+        double* s = dst();
+        curl(ux, s, false);
+        return s;
+      }
+      case PUCFEM_F_DIV_U: return div_u;
+      case PUCFEM_F_SCALAR: return scalar;
+      default: return nullptr;
+    }
+  }
+  // the context's interleaved-u scratch (x at [0], y at [1], stride 2; 4 x nloc in all, pucfem_solve's four vectors):
+  // the unit operations put a caller's u here as the step stores it, and the step's state stays untouched
+  double* u_scratch() {
+    if (!solve_tmp) solve_tmp = dalloc<double>(4 * nloc);
+    return solve_tmp;
   }
   // sb_fused: the preceding k_div reduced sum(braw) into redbuf slot 3 itself (div_rhs)
   // PUCFEM_RHS_FUSE=0 (measurement knob): the pressure right-hand side always in its own pass (k_pres_rhs)
@@ -4752,6 +4834,58 @@ void build(Ctx& c) {
   }
 }
 
+// ---- tracer I/O of a run and of an ensemble's members: tracers first .. first + count - 1 of the arrays
+// new positions from (count, 2) pairs, with what goes with them: status 0, not captured (-1), and the nctr step
+// counters at trstep back to 0.  Ordered on st, not synchronised.
+void tracers_put(Ctx& c, double* trx, double* try_, double* trs, int32_t* trcap, int32_t* trstep, i64 nctr, i64 first,
+                 i64 count, const double* buf) {
+  std::vector<double> xy(2 * (size_t)count);
+  for (i64 k = 0; k < count; ++k) {
+    xy[k] = buf[2 * k];
+    xy[count + k] = buf[2 * k + 1];
+  }
+  HIPCHK(hipMemsetAsync(trstep, 0, sizeof(int32_t) * nctr, c.st));
+  if (count == 0) return;
+  c.h2d(trx + first, xy.data(), sizeof(double) * count);
+  c.h2d(try_ + first, xy.data() + count, sizeof(double) * count);
+  HIPCHK(hipMemsetAsync(trs + first, 0, sizeof(double) * count, c.st));
+  HIPCHK(hipMemsetAsync(trcap + first, 0xFF, sizeof(int32_t) * count, c.st));
+}
+void tracers_get(Ctx& c, const double* trx, const double* try_, i64 first, i64 count, double* buf) {
+  if (count == 0) return;
+  std::vector<double> xy(2 * (size_t)count);
+  c.d2h(xy.data(), trx + first, sizeof(double) * count);
+  c.d2h(xy.data() + count, try_ + first, sizeof(double) * count);
+  for (i64 k = 0; k < count; ++k) {
+    buf[2 * k] = xy[k];
+    buf[2 * k + 1] = xy[count + k];
+  }
+}
+void capture_steps_get(Ctx& c, const int32_t* trcap, i64 first, i64 count, double* buf) {
+  if (count == 0) return;
+  std::vector<int32_t> cs((size_t)count);
+  c.d2h(cs.data(), trcap + first, sizeof(int32_t) * count);
+  for (i64 k = 0; k < count; ++k) buf[k] = (double)cs[k];
+}
+
+// ms per launch of `iters` launches on the context's stream (the caller has made its untimed first launch); the
+// events are released on every path
+template <class F>
+double time_launches(Ctx& c, int iters, F&& launch) {
+  struct Ev {
+    hipEvent_t e = nullptr;
+    Ev() { HIPCHK(hipEventCreate(&e)); }
+    ~Ev() { (void)hipEventDestroy(e); }
+  } a, b;
+  HIPCHK(hipEventRecord(a.e, c.st));
+  for (int k = 0; k < iters; ++k) launch();
+  HIPCHK(hipEventRecord(b.e, c.st));
+  HIPCHK(hipEventSynchronize(b.e));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, a.e, b.e));
+  return (double)ms / iters;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -4761,23 +4895,9 @@ template <typename T>
 void mg_probe_run(Ctx& c, int piece, int l, const double* b, const double* x, double* out, double* rz) {
   const int Lv = (int)c.mg.size() - 1;
   auto size_of = [&](int lv) { return (i64)c.mg[lv].ord.new2old.size(); };
-  std::vector<T> h;
-  auto up = [&](int lv, const double* src, T* dst) {
-    const Ordering& o = c.mg[lv].ord;
-    const i64 n = size_of(lv);
-    h.resize((size_t)n);
-    for (i64 g = 0; g < n; ++g) h[g] = (T)src[o.new2old[g]];
-    c.h2d(dst, h.data(), sizeof(T) * (size_t)n);
-    HIPCHK(hipStreamSynchronize(c.st));  // (h is reused)
-  };
-  auto down = [&](int lv, const T* src) {
-    const Ordering& o = c.mg[lv].ord;
-    const i64 n = size_of(lv);
-    h.resize((size_t)n);
-    c.d2h(h.data(), src, sizeof(T) * (size_t)n);
-    HIPCHK(hipStreamSynchronize(c.st));
-    for (i64 g = 0; g < n; ++g) out[o.new2old[g]] = (double)h[g];
-  };
+  // a level's vector in the level's own ordering, rounded to / widened from the cycle's type
+  auto up = [&](int lv, const double* src, auto* dst) { c.put(c.mg[lv].ord, 0, size_of(lv), 1, 1, src, dst); };
+  auto down = [&](int lv, const T* src) { c.get(c.mg[lv].ord, 0, size_of(lv), 1, 1, out, src); };
   // the right-hand side of level lv where the cycle reads it
   auto rhs = [&](int lv) -> T* {
     if (lv < Lv) return bufs<T>(c.mg[lv]).b;
@@ -4831,11 +4951,7 @@ void mg_probe_run(Ctx& c, int piece, int l, const double* b, const double* x, do
       break;
     }
     default: {  // PUCFEM_MG_PRECOND
-      const i64 n = size_of(Lv);
-      std::vector<double> rd((size_t)n);
-      for (i64 g = 0; g < n; ++g) rd[g] = b[c.mg[Lv].ord.new2old[g]];
-      c.h2d(c.cg_r[0], rd.data(), sizeof(double) * (size_t)n);
-      HIPCHK(hipStreamSynchronize(c.st));
+      up(Lv, b, c.cg_r[0]);
       if constexpr (std::is_same<T, float>::value) up(Lv, b, c.r32);
       const Red red = c.precondition_rz(Ctx::grid_part(c.fP.part(), c.dPp));
       c.d2h(rz, red.p, sizeof(double));
@@ -5047,46 +5163,32 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
         const int k = field - PUCFEM_F_DYE0;
         require(k < c.ndye, "dye channel index >= the number of channels");
         require(count == N && buf != nullptr, "a dye channel must be (N,)");
-        std::vector<double> x(N);
-        for (i64 g = 0; g < N; ++g) x[g] = buf[c.ord.new2old[g]];
-        c.h2d(c.dye_cur + (size_t)k * N, x.data(), sizeof(double) * N);
+        c.put_all(1, 1, buf, c.dye_cur + (size_t)k * N);
         HIPCHK(hipStreamSynchronize(c.st));
       }
       return;
     }
-    auto own2 = [&](double* a, double*) {  // (the interleaved velocity: a = its pairs)
+    auto own2 = [&](double* a) {  // (the interleaved velocity: a = its pairs)
       require(count == 2 * N, "field must be (N, 2)");
-      std::vector<double> xy(2 * no);
-      for (i64 i = 0; i < no; ++i) {
-        const i64 o = c.ord.new2old[c.lp.r0 + i];
-        xy[2 * i] = buf[2 * o];
-        xy[2 * i + 1] = buf[2 * o + 1];
-      }
-      HIPCHK(hipMemcpyAsync(a, xy.data(), sizeof(double) * 2 * no, hipMemcpyHostToDevice, c.st));
+      c.put(c.ord, c.lp.r0, no, 2, 1, buf, a, (double*)nullptr, false);
       HIPCHK(hipStreamSynchronize(c.st));
       c.halo_v(a);
     };
-    auto own1 = [&](double* a) {
-      require(count == N, "field must be (N,)");
-      std::vector<double> x(no);
-      for (i64 i = 0; i < no; ++i) x[i] = buf[c.ord.new2old[c.lp.r0 + i]];
-      HIPCHK(hipMemcpyAsync(a, x.data(), sizeof(double) * no, hipMemcpyHostToDevice, c.st));
-      c.halo(a);
-    };
     switch (field) {
       case PUCFEM_F_U:
-        own2(c.ux, c.uy);
+        own2(c.ux);
         c.have_vinc = 0;  // a new state: no last viscous increment
         break;
-      case PUCFEM_F_USTAR: own2(c.usx, c.usy); break;
-      case PUCFEM_F_SCALAR: own1(c.scalar); break;
-      case PUCFEM_F_C: {
-        require(count == N, "c must be (N,)");
-        std::vector<double> x(N);
-        for (i64 g = 0; g < N; ++g) x[g] = buf[c.ord.new2old[g]];
-        HIPCHK(hipMemcpyAsync(c.c_full, x.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+      case PUCFEM_F_USTAR: own2(c.usx); break;
+      case PUCFEM_F_SCALAR:
+        require(count == N, "field must be (N,)");
+        c.put(c.ord, c.lp.r0, no, 1, 1, buf, c.scalar);
+        c.halo(c.scalar);
         break;
-      }
+      case PUCFEM_F_C:
+        require(count == N, "c must be (N,)");
+        c.put(c.ord, 0, N, 1, 1, buf, c.c_full, (double*)nullptr, false);
+        break;
       case PUCFEM_F_TRACERS: {
         require(count % 2 == 0, "tracers must be (n, 2)");
         const i64 n = count / 2;
@@ -5106,21 +5208,12 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
           c.part_tr = c.dalloc<double>(TRACER_CLOUD_MAXB);
           c.trcensus = c.dalloc<unsigned long long>(2);
         }
-        std::vector<double> x(n), y(n);
-        for (i64 k = 0; k < n; ++k) {
-          x[k] = buf[2 * k];
-          y[k] = buf[2 * k + 1];
-        }
-        HIPCHK(hipMemcpyAsync(c.trx, x.data(), sizeof(double) * n, hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemcpyAsync(c.try_, y.data(), sizeof(double) * n, hipMemcpyHostToDevice, c.st));
-        HIPCHK(hipMemsetAsync(c.trs, 0, sizeof(double) * n, c.st));
-        HIPCHK(hipMemsetAsync(c.trcap, 0xFF, sizeof(int32_t) * std::max<i64>(1, n), c.st));  // -1: not captured
-        HIPCHK(hipMemsetAsync(c.trstep, 0, sizeof(int32_t), c.st));
+        tracers_put(c, c.trx, c.try_, c.trs, c.trcap, c.trstep, 1, 0, n, buf);
         break;
       }
       case PUCFEM_F_STATUS:
         require(count == c.ntr, "status must match the tracer count");
-        HIPCHK(hipMemcpyAsync(c.trs, buf, sizeof(double) * count, hipMemcpyHostToDevice, c.st));
+        c.h2d(c.trs, buf, sizeof(double) * count);
         break;
       default: throw Error(PUCFEM_EINVAL, "field cannot be set");
     }
@@ -5143,100 +5236,50 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
       require(count == (i64)nk * N, field == PUCFEM_F_DYES ? "dyes are (K, N)" : "a dye channel is (N,)");
       if (nk == 0) return;
       require(buf != nullptr, "null output");
-      std::vector<double> x((size_t)nk * (size_t)N);
-      c.d2h(x.data(), c.dye_cur + (size_t)k0 * N, sizeof(double) * x.size());
-      for (int k = 0; k < nk; ++k)
-        for (i64 g = 0; g < N; ++g) buf[(size_t)k * N + c.ord.new2old[g]] = x[(size_t)k * N + g];
+      c.get_all(1, nk, buf, c.dye_cur + (size_t)k0 * N);
       return;
     }
-    auto get2 = [&](const double* a, const double*) {  // (the interleaved velocity)
-      require(count == 2 * N, "field is (N, 2)");
-      std::vector<double> xy(2 * no);
-      HIPCHK(hipMemcpyAsync(xy.data(), a, sizeof(double) * 2 * no, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 i = 0; i < no; ++i) {
-        const i64 o = c.ord.new2old[c.lp.r0 + i];
-        buf[2 * o] = xy[2 * i];
-        buf[2 * o + 1] = xy[2 * i + 1];
-      }
-    };
-    auto get1 = [&](const double* a) {
-      require(count == N, "field is (N,)");
-      std::vector<double> x(no);
-      HIPCHK(hipMemcpyAsync(x.data(), a, sizeof(double) * no, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 i = 0; i < no; ++i) buf[c.ord.new2old[c.lp.r0 + i]] = x[i];
-    };
     switch (field) {
-      case PUCFEM_F_U: get2(c.ux, c.uy); break;
-      case PUCFEM_F_USTAR: get2(c.usx, c.usy); break;
-      case PUCFEM_F_P:  // with p_from_y the step keeps p in y (slaves not copied): p formed when read
-      case PUCFEM_F_P2: {
-        double* pf = field == PUCFEM_F_P ? c.p : c.p2;
-        if (c.p_from_y) {
-          const i64 n = c.lp.n_own;
-          hipLaunchKernelGGL(k_cg_fin, dim3(Ctx::grid_ew(n)), dim3(BS), 0, c.st, n, 1, (const double*)nullptr,
-                             (const double*)(field == PUCFEM_F_P ? c.yp : c.yp2), (const double*)nullptr, pf,
-                             (double*)nullptr, (const int32_t*)c.dmaster_of);
-          KCHK();
-        }
-        get1(pf);
+      case PUCFEM_F_P:
+      case PUCFEM_F_P2:
+      case PUCFEM_F_DIV_STAR:
+      case PUCFEM_F_DIV_U:
+      case PUCFEM_F_FINAL_DIV:
+      case PUCFEM_F_VORTICITY:
+      case PUCFEM_F_SCALAR: {  // one component, formed first (in place) when the step does not store it
+        const double* a = c.formed(field, [&] {
+          return field == PUCFEM_F_P           ? c.p
+                 : field == PUCFEM_F_P2        ? c.p2
+                 : field == PUCFEM_F_DIV_STAR  ? c.div_star
+                 : field == PUCFEM_F_FINAL_DIV ? c.final_div
+                                               : c.smp_scratch<double>(8, (size_t)c.nloc);
+        });
+        require(count == N, "field is (N,)");
+        c.get(c.ord, c.lp.r0, no, 1, 1, buf, a);
         break;
       }
-      case PUCFEM_F_DIV_STAR:  // computed from u* when read (the step records only its max)
-        if (c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD) c.div(c.usx, c.usy, c.div_star, false);
-        get1(c.div_star);
+      case PUCFEM_F_U:
+      case PUCFEM_F_USTAR:  // (the interleaved velocity)
+        require(count == 2 * N, "field is (N, 2)");
+        c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)(field == PUCFEM_F_U ? c.ux : c.usx), (const double*)nullptr, false);
         break;
-      case PUCFEM_F_DIV_U: get1(c.div_u); break;
-      case PUCFEM_F_FINAL_DIV:  // likewise from u (the implicit dye variant keeps its own copy)
-        if ((c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD) && !c.dye_impl)
-          c.div(c.ux, c.uy, c.final_div, false);
-        get1(c.final_div);
-        break;
-      case PUCFEM_F_VORTICITY: {  // from u when read; the owned rows (u's ghosts are current after every write of u)
-        if (c.scheme != PUCFEM_STOKES_COLOR && c.scheme != PUCFEM_STOKES_FOOD)
-          throw Error(PUCFEM_ESTATE, "vorticity needs a Stokes context");
-        double* s = c.smp_scratch<double>(8, (size_t)c.nloc);
-        c.curl(c.ux, s, false);
-        get1(s);
-        break;
-      }
-      case PUCFEM_F_SCALAR: get1(c.scalar); break;
-      case PUCFEM_F_C: {
+      case PUCFEM_F_C:
         require(count == N, "c is (N,)");
         c.allgather_full(c.c_full);  // multi-rank: collective (every rank reads c), the full field
-        std::vector<double> x(N);
-        HIPCHK(hipMemcpyAsync(x.data(), c.c_full, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (i64 g = 0; g < N; ++g) buf[c.ord.new2old[g]] = x[g];
+        c.get(c.ord, 0, N, 1, 1, buf, (const double*)c.c_full, (const double*)nullptr, false);
         break;
-      }
-      case PUCFEM_F_TRACERS: {
+      case PUCFEM_F_TRACERS:
         require(count == 2 * (i64)c.ntr, "tracers are (n, 2)");
-        std::vector<double> x(c.ntr), y(c.ntr);
-        HIPCHK(hipMemcpyAsync(x.data(), c.trx, sizeof(double) * c.ntr, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipMemcpyAsync(y.data(), c.try_, sizeof(double) * c.ntr, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (i64 k = 0; k < c.ntr; ++k) {
-          buf[2 * k] = x[k];
-          buf[2 * k + 1] = y[k];
-        }
+        tracers_get(c, c.trx, c.try_, 0, c.ntr, buf);
         break;
-      }
       case PUCFEM_F_STATUS:
         require(count == c.ntr, "status is (n,)");
-        HIPCHK(hipMemcpyAsync(buf, c.trs, sizeof(double) * count, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
+        c.d2h(buf, c.trs, sizeof(double) * count);
         break;
-      case PUCFEM_F_CAPTURE_STEP: {
+      case PUCFEM_F_CAPTURE_STEP:
         require(count == c.ntr, "capture steps are (n,)");
-        std::vector<int32_t> cs((size_t)c.ntr);
-        if (c.ntr > 0)
-          HIPCHK(hipMemcpyAsync(cs.data(), c.trcap, sizeof(int32_t) * cs.size(), hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (size_t k = 0; k < cs.size(); ++k) buf[k] = (double)cs[k];
+        capture_steps_get(c, c.trcap, 0, c.ntr, buf);
         break;
-      }
       default: throw Error(PUCFEM_EINVAL, "unknown field");
     }
   });
@@ -5657,27 +5700,12 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
     if (f.per == 0) return;
-    std::vector<double> x((size_t)(nm * f.per)), y;
-    if (field == PUCFEM_F_TRACERS) {
-      y.resize(x.size() / 2);
-      for (i64 k = 0; k < nm * e.ntr; ++k) {
-        x[k] = buf[2 * k];
-        y[k] = buf[2 * k + 1];
-      }
-      HIPCHK(hipMemcpyAsync(e.trx + m0 * e.ntr, x.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
-      HIPCHK(hipMemcpyAsync(e.try_ + m0 * e.ntr, y.data(), sizeof(double) * nm * e.ntr, hipMemcpyHostToDevice, c.st));
-      HIPCHK(hipMemsetAsync(e.trs + m0 * e.ntr, 0, sizeof(double) * nm * e.ntr, c.st));  // (as pucfem_set_field)
-      HIPCHK(hipMemsetAsync(e.trcap + m0 * e.ntr, 0xFF, sizeof(int32_t) * nm * e.ntr, c.st));
-      HIPCHK(hipMemsetAsync(e.trstep + m0, 0, sizeof(int32_t) * nm, c.st));
-    } else {
-      for (i64 m = 0; m < nm; ++m)
-        for (i64 g = 0; g < e.n && f.comp > 0; ++g) {
-          const i64 o = c.ord.new2old[g];
-          for (int q = 0; q < f.comp; ++q) x[m * f.per + f.comp * g + q] = buf[m * f.per + f.comp * o + q];
-        }
-      const double* src = f.comp > 0 ? x.data() : buf;
-      HIPCHK(hipMemcpyAsync(f.a + m0 * f.per, src, sizeof(double) * nm * f.per, hipMemcpyHostToDevice, c.st));
-    }
+    if (field == PUCFEM_F_TRACERS)
+      tracers_put(c, e.trx, e.try_, e.trs, e.trcap, e.trstep + m0, nm, m0 * e.ntr, nm * e.ntr, buf);
+    else if (f.comp > 0)  // (the members are the planes)
+      c.put_all(f.comp, nm, buf, f.a + m0 * f.per);
+    else
+      c.h2d(f.a + m0 * f.per, buf, sizeof(double) * nm * f.per);
     HIPCHK(hipStreamSynchronize(c.st));
   });
 }
@@ -5691,37 +5719,13 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
     if (f.per == 0) return;
-    if (field == PUCFEM_F_CAPTURE_STEP) {
-      std::vector<int32_t> cs((size_t)(nm * e.ntr));
-      HIPCHK(hipMemcpyAsync(cs.data(), e.trcap + m0 * e.ntr, sizeof(int32_t) * cs.size(), hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (size_t k = 0; k < cs.size(); ++k) buf[k] = (double)cs[k];
-      return;
-    }
-    if (field == PUCFEM_F_TRACERS) {
-      std::vector<double> x((size_t)(nm * e.ntr)), y(x.size());
-      HIPCHK(hipMemcpyAsync(x.data(), e.trx + m0 * e.ntr, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipMemcpyAsync(y.data(), e.try_ + m0 * e.ntr, sizeof(double) * y.size(), hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (size_t k = 0; k < x.size(); ++k) {
-        buf[2 * k] = x[k];
-        buf[2 * k + 1] = y[k];
-      }
-      return;
-    }
+    if (field == PUCFEM_F_CAPTURE_STEP) return capture_steps_get(c, e.trcap, m0 * e.ntr, nm * e.ntr, buf);
+    if (field == PUCFEM_F_TRACERS) return tracers_get(c, e.trx, e.try_, m0 * e.ntr, nm * e.ntr, buf);
     if (field == PUCFEM_F_VORTICITY) ens_curl(c, e, (int32_t)m0, (int32_t)nm, true, false);
-    std::vector<double> x((size_t)(nm * f.per));
-    HIPCHK(hipMemcpyAsync(x.data(), f.a + m0 * f.per, sizeof(double) * x.size(), hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipStreamSynchronize(c.st));
-    if (f.comp == 0) {
-      std::memcpy(buf, x.data(), sizeof(double) * x.size());
-      return;
-    }
-    for (i64 m = 0; m < nm; ++m)
-      for (i64 g = 0; g < e.n; ++g) {
-        const i64 o = c.ord.new2old[g];
-        for (int q = 0; q < f.comp; ++q) buf[m * f.per + f.comp * o + q] = x[m * f.per + f.comp * g + q];
-      }
+    if (f.comp > 0)  // (the members are the planes)
+      c.get_all(f.comp, nm, buf, f.a + m0 * f.per);
+    else
+      c.d2h(buf, f.a + m0 * f.per, sizeof(double) * nm * f.per);
   });
 }
 
@@ -5812,7 +5816,6 @@ void sample_push(SampleFields& F, const double* p, int32_t stride, int64_t membe
 SampleFields sample_fields(Ctx& c, int32_t nfields, const int32_t* fields) {
   require(nfields >= 1 && fields != nullptr, "nfields < 1");
   SampleFields F{};
-  const i64 n = c.lp.n_own;
   for (int32_t k = 0; k < nfields; ++k) {
     switch (fields[k]) {
       case PUCFEM_F_U:
@@ -5824,43 +5827,17 @@ SampleFields sample_fields(Ctx& c, int32_t nfields, const int32_t* fields) {
         sample_push(F, c.usy, VS, 0);
         break;
       case PUCFEM_F_P:
-      case PUCFEM_F_P2: {
-        const bool first = fields[k] == PUCFEM_F_P;
-        const double* pf = first ? c.p : c.p2;
-        if (c.p_from_y) {  // (p kept in y, the slaves not copied: pucfem_get_field's pass, into a buffer of ours)
-          double* s = c.smp_scratch<double>(first ? 4 : 5, (size_t)c.nloc);
-          hipLaunchKernelGGL(k_cg_fin, dim3(Ctx::grid_ew(n)), dim3(BS), 0, c.st, n, 1, (const double*)nullptr,
-                             (const double*)(first ? c.yp : c.yp2), (const double*)nullptr, s, (double*)nullptr,
-                             (const int32_t*)c.dmaster_of);
-          KCHK();
-          pf = s;
-        }
-        sample_push(F, pf, 1, 0);
-        break;
-      }
-      case PUCFEM_F_DIV_STAR: {  // from u*, as pucfem_get_field computes it
-        double* s = c.smp_scratch<double>(6, (size_t)c.nloc);
-        c.div(c.usx, c.usy, s, false);
-        sample_push(F, s, 1, 0);
-        break;
-      }
-      case PUCFEM_F_DIV_U: sample_push(F, c.div_u, 1, 0); break;
+      case PUCFEM_F_P2:
+      case PUCFEM_F_DIV_STAR:
+      case PUCFEM_F_DIV_U:
       case PUCFEM_F_FINAL_DIV:
-        if (c.dye_impl) {
-          sample_push(F, c.final_div, 1, 0);
-        } else {
-          double* s = c.smp_scratch<double>(7, (size_t)c.nloc);
-          c.div(c.ux, c.uy, s, false);
-          sample_push(F, s, 1, 0);
-        }
-        break;
-      case PUCFEM_F_C: sample_push(F, c.c_full, 1, 0); break;
-      case PUCFEM_F_VORTICITY: {  // from u, as pucfem_get_field computes it
-        double* s = c.smp_scratch<double>(8, (size_t)c.nloc);
-        c.curl(c.ux, s, false);
-        sample_push(F, s, 1, 0);
+      case PUCFEM_F_VORTICITY: {  // (formed, when the step does not store it, into scratch slots 4..8)
+        const int32_t f = fields[k];
+        const int slot = f == PUCFEM_F_P ? 4 : f == PUCFEM_F_P2 ? 5 : f == PUCFEM_F_DIV_STAR ? 6 : f == PUCFEM_F_FINAL_DIV ? 7 : 8;
+        sample_push(F, c.formed(fields[k], [&] { return c.smp_scratch<double>(slot, (size_t)c.nloc); }), 1, 0);
         break;
       }
+      case PUCFEM_F_C: sample_push(F, c.c_full, 1, 0); break;
       default:
         if (fields[k] >= PUCFEM_F_DYE0 && fields[k] < PUCFEM_F_DYE0 + DYE_MAX) {
           const int ch = fields[k] - PUCFEM_F_DYE0;
@@ -5995,20 +5972,9 @@ int pucfem_raster_probe(void* ctx, int32_t nfields, const int32_t* fields, int32
                          dcnt);
     KCHK();
     launch_raster(c, p, F, dout);  // (untimed: the first launch)
-    hipEvent_t ea, eb;
-    HIPCHK(hipEventCreate(&ea));
-    HIPCHK(hipEventCreate(&eb));
-    HIPCHK(hipEventRecord(ea, c.st));
-    for (int k = 0; k < iters; ++k) launch_raster(c, p, F, dout);
-    HIPCHK(hipEventRecord(eb, c.st));
-    HIPCHK(hipEventSynchronize(eb));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
+    out4[0] = time_launches(c, iters, [&] { launch_raster(c, p, F, dout); });
     unsigned long long h[2] = {0, 0};
     c.d2h(h, dcnt, sizeof(h));
-    out4[0] = (double)ms / iters;
     out4[1] = (double)h[0];
     out4[2] = (double)h[1];
     out4[3] = (double)(sizeof(float) * count);
@@ -6096,18 +6062,7 @@ int pucfem_streamlines_probe(void* ctx, int64_t nseeds, const double* seeds, dou
     int32_t* dst = c.smp_scratch<int32_t>(12, 2 * lines);
     c.h2d(dseeds, seeds, sizeof(double) * 2 * (size_t)nseeds);
     sln_launch(c, A, F, dseeds, dpts, dst, nullptr);  // (untimed: the first launch)
-    hipEvent_t ea, eb;
-    HIPCHK(hipEventCreate(&ea));
-    HIPCHK(hipEventCreate(&eb));
-    HIPCHK(hipEventRecord(ea, c.st));
-    for (int k = 0; k < iters; ++k) sln_launch(c, A, F, dseeds, dpts, dst, nullptr);
-    HIPCHK(hipEventRecord(eb, c.st));
-    HIPCHK(hipEventSynchronize(eb));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
-    out2[0] = (double)ms / iters;
+    out2[0] = time_launches(c, iters, [&] { sln_launch(c, A, F, dseeds, dpts, dst, nullptr); });
     out2[1] = (double)(sizeof(double) * 2 * per + sizeof(int32_t) * 2 * lines);
   });
 }
@@ -6145,28 +6100,23 @@ int pucfem_apply(void* ctx, int32_t op, const double* x, double* y) {
     c.need_built();
     require(!c.dist(), "pucfem_apply is single-rank");
     const i64 N = c.mesh.N;
-    auto perm_in = [&](const double* src, int ncomp, double* d0, double* d1) {
-      std::vector<double> a(N), b(N);
-      for (i64 g = 0; g < N; ++g) {
-        const i64 o = c.ord.new2old[g];
-        a[g] = src[ncomp * o];
-        if (ncomp > 1) b[g] = src[ncomp * o + 1];
-      }
-      HIPCHK(hipMemcpyAsync(d0, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-      if (ncomp > 1) HIPCHK(hipMemcpyAsync(d1, b.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-    };
-    auto perm_out = [&](double* dst, int ncomp, const double* d0, const double* d1) {
-      std::vector<double> a(N), b(N);
-      HIPCHK(hipMemcpyAsync(a.data(), d0, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      if (ncomp > 1) HIPCHK(hipMemcpyAsync(b.data(), d1, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 g = 0; g < N; ++g) {
-        const i64 o = c.ord.new2old[g];
-        dst[ncomp * o] = a[g];
-        if (ncomp > 1) dst[ncomp * o + 1] = b[g];
-      }
-    };
+    auto perm_in = [&](const double* src, int ncomp, double* d0, double* d1) { c.put_all(ncomp, 1, src, d0, d1); };
+    auto perm_out = [&](double* dst, int ncomp, double* d0, double* d1) { c.get_all(ncomp, 1, dst, d0, d1); };
     double *t0 = c.cg_pa[0], *t1 = c.cg_pa[1], *o0 = c.cg_q[0], *o1 = c.cg_q[1];
+    // the unscaled action of a scaled operator, S^-1 A^ S^-1 x: x / s in (same operands, same order as one loop over
+    // the permutation), A^ by `mv`, the product / s out
+    auto scaled = [&](const double* ds, auto&& mv) {
+      std::vector<double> s(N), v(N);
+      c.d2h(s.data(), ds, sizeof(double) * N);
+      to_internal(c.ord, 0, N, 1, 1, N, x, N, v.data());
+      for (i64 g = 0; g < N; ++g) v[g] = v[g] / s[g];
+      c.h2d(t0, v.data(), sizeof(double) * N);
+      mv();
+      KCHK();
+      c.d2h(v.data(), o0, sizeof(double) * N);
+      for (i64 g = 0; g < N; ++g) v[g] = v[g] / s[g];
+      to_caller(c.ord, 0, N, 1, 1, N, y, N, v.data());
+    };
     switch (op) {
       case PUCFEM_OP_K:
       case PUCFEM_OP_GX:
@@ -6188,19 +6138,7 @@ int pucfem_apply(void* ctx, int32_t op, const double* x, double* y) {
           perm_out(y, 1, o0, nullptr);
           break;
         }
-        perm_in(x, 1, t0, nullptr);
-        // unscaled action: S^-1 A^ S^-1 x
-        std::vector<double> s(N);
-        HIPCHK(hipMemcpyAsync(s.data(), c.dsp, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        std::vector<double> a(N), xs(N);
-        for (i64 g = 0; g < N; ++g) xs[g] = x[c.ord.new2old[g]] / s[g];
-        HIPCHK(hipMemcpyAsync(t0, xs.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-        spmv_on(c.st, c.dPp, FaceDev{}, c.dKp, t0, o0);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(a.data(), o0, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (i64 g = 0; g < N; ++g) y[c.ord.new2old[g]] = a[g] / s[g];
+        scaled(c.dsp, [&] { spmv_on(c.st, c.dPp, FaceDev{}, c.dKp, t0, o0); });
         break;
       }
       case PUCFEM_OP_LIT: {
@@ -6242,20 +6180,7 @@ int pucfem_apply(void* ctx, int32_t op, const double* x, double* y) {
         perm_out(y, 2, o0, o1);
         break;
       }
-      case PUCFEM_OP_VISC: {
-        // unscaled A_visc x = S^-1 A^ S^-1 x
-        std::vector<double> s(N), xs(N), a(N);
-        HIPCHK(hipMemcpyAsync(s.data(), c.dsv, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (i64 g = 0; g < N; ++g) xs[g] = x[c.ord.new2old[g]] / s[g];
-        HIPCHK(hipMemcpyAsync(t0, xs.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-        spmv_on(c.st, c.dP, c.fVisc.full(), c.dKv, t0, o0);
-        KCHK();
-        HIPCHK(hipMemcpyAsync(a.data(), o0, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-        HIPCHK(hipStreamSynchronize(c.st));
-        for (i64 g = 0; g < N; ++g) y[c.ord.new2old[g]] = a[g] / s[g];
-        break;
-      }
+      case PUCFEM_OP_VISC: scaled(c.dsv, [&] { spmv_on(c.st, c.dP, c.fVisc.full(), c.dKv, t0, o0); }); break;
       default: throw Error(PUCFEM_EINVAL, "unknown op");
     }
   });
@@ -6300,17 +6225,10 @@ int pucfem_solve(void* ctx, int32_t op, const double* b, double* x, double rtol,
     int it = 0;
     // standalone solves run on scratch buffers with their own iteration-hint slots (3, 4) and no
     // projection basis: a context that is stepping keeps u, p, the warm starts and the bases intact
-    if (!c.solve_tmp) c.solve_tmp = c.dalloc<double>(4 * c.nloc);
-    double *s0 = c.solve_tmp, *s1 = s0 + c.nloc, *s2 = s1 + c.nloc, *s3 = s2 + c.nloc;
+    double *s0 = c.u_scratch(), *s1 = s0 + c.nloc, *s2 = s1 + c.nloc, *s3 = s2 + c.nloc;
     if (op == PUCFEM_OP_VISC) {
       // rhs = b (as u^n, initial guess b): the viscous CG without BCs
-      std::vector<double> bxy(2 * N);  // (k_visc_prep reads u interleaved: s0 / s0 + 1 over 2 N of scratch)
-      for (i64 g = 0; g < N; ++g) {
-        bxy[2 * g] = b[2 * c.ord.new2old[g]];
-        bxy[2 * g + 1] = b[2 * c.ord.new2old[g] + 1];
-      }
-      HIPCHK(hipMemcpyAsync(s0, bxy.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
+      c.put_all(2, 1, b, s0);  // (k_visc_prep reads u interleaved: s0 / s0 + 1 over 2 N of scratch)
       hipLaunchKernelGGL(k_visc_prep<false>, dim3(Ctx::grid_ew(N)), dim3(BS), 0, c.st, N, c.dsv, s0, s0 + 1,
                          c.bvx, c.bvy, c.yvx, c.yvy, VincDev{});
       KCHK();
@@ -6320,29 +6238,22 @@ int pucfem_solve(void* ctx, int32_t op, const double* b, double* x, double rtol,
       hipLaunchKernelGGL(k_cg_fin, dim3(Ctx::grid_ew(N)), dim3(BS), 0, c.st, N, 2, c.dsv, c.yvx, c.yvy, s2, s3,
                          (const int32_t*)nullptr);
       KCHK();
-      std::vector<double> ox(N), oy(N);
-      HIPCHK(hipMemcpyAsync(ox.data(), s2, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipMemcpyAsync(oy.data(), s3, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 g = 0; g < N; ++g) {
-        x[2 * c.ord.new2old[g]] = ox[g];
-        x[2 * c.ord.new2old[g] + 1] = oy[g];
-      }
+      c.get_all(2, 1, x, s2, s3);
     } else if (op == PUCFEM_OP_PRES) {
       require(c.dKp || c.dKp_raw, "no pressure operator");
       // b = b_p: braw = (M + 1e-12) * b_p, then the same path as the step (slot 4: no projection)
       std::vector<double> mp(N), br(N);
-      HIPCHK(hipMemcpyAsync(mp.data(), c.dmp, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
+      c.d2h(mp.data(), c.dmp, sizeof(double) * N);
+      to_internal(c.ord, 0, N, 1, 1, N, b, N, br.data());
       double sum = 0.0;
       for (i64 g = 0; g < N; ++g) {
-        br[g] = mp[g] * b[c.ord.new2old[g]];
+        br[g] = mp[g] * br[g];
         sum += br[g];
       }
-      HIPCHK(hipMemcpyAsync(c.braw, br.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+      c.h2d(c.braw, br.data(), sizeof(double) * N);
       std::vector<double> part(4 * MAXB, 0.0);
       part[MAXB] = sum;
-      HIPCHK(hipMemcpyAsync(c.part_d, part.data(), sizeof(double) * part.size(), hipMemcpyHostToDevice, c.st));
+      c.h2d(c.part_d, part.data(), sizeof(double) * part.size());
       // pressure() reduces part_d + MAXB over nb_for(dP) blocks: only entry 0 is non-zero
       HIPCHK(hipMemsetAsync(s0, 0, sizeof(double) * c.nloc, c.st));
       pucfem_params save = c.prm;
@@ -6355,24 +6266,13 @@ int pucfem_solve(void* ctx, int32_t op, const double* b, double* x, double rtol,
         throw;
       }
       c.prm = save;
-      std::vector<double> o(N);
-      HIPCHK(hipMemcpyAsync(o.data(), s1, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 g = 0; g < N; ++g) x[c.ord.new2old[g]] = o[g];
+      c.get_all(1, 1, x, s1);
     } else if (op == PUCFEM_OP_LIT) {
       require(c.dLitv, "no literal operator");
-      std::vector<double> bb(N), x0(N);
-      for (i64 g = 0; g < N; ++g) {
-        bb[g] = b[c.ord.new2old[g]];
-        x0[g] = x[c.ord.new2old[g]];
-      }
-      HIPCHK(hipMemcpyAsync(c.bh, bb.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-      HIPCHK(hipMemcpyAsync(c.scalar, x0.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+      c.put_all(1, 1, b, c.bh);
+      c.put_all(1, 1, (const double*)x, c.scalar);
       it = c.bicgstab(c.scalar, c.bh, rtol, maxit);
-      std::vector<double> o(N);
-      HIPCHK(hipMemcpyAsync(o.data(), c.scalar, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-      HIPCHK(hipStreamSynchronize(c.st));
-      for (i64 g = 0; g < N; ++g) x[c.ord.new2old[g]] = o[g];
+      c.get_all(1, 1, x, c.scalar);
     } else {
       throw Error(PUCFEM_EINVAL, "op cannot be solved");
     }
@@ -6387,30 +6287,14 @@ int pucfem_sl_advect(void* ctx, const double* cin, const double* u, double dt, d
     c.need_built();
     require(!c.dist() && c.has_cgrid, "sl_advect needs a single-rank Stokes context");
     const i64 N = c.mesh.N;
-    std::vector<double> a(N), bxy(2 * N);
-    for (i64 g = 0; g < N; ++g) {
-      const i64 o = c.ord.new2old[g];
-      a[g] = cin[o];
-      bxy[2 * g] = u[2 * o];
-      bxy[2 * g + 1] = u[2 * o + 1];
-    }
-    // u as the step stores it (interleaved pairs) in scratch: the step's state stays untouched
-    if (!c.solve_tmp) c.solve_tmp = c.dalloc<double>(4 * c.nloc);
-    double *cf = c.litw[0] ? c.litw[0] : c.cg_pa[0], *cn = c.cg_pb[0], *tx = c.solve_tmp, *ty = tx + 1;
-    HIPCHK(hipMemcpyAsync(cf, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(tx, bxy.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c.st));
+    double *cf = c.litw[0] ? c.litw[0] : c.cg_pa[0], *cn = c.cg_pb[0], *tx = c.u_scratch(), *ty = tx + 1;
+    c.put_all(1, 1, cin, cf);
+    c.put_all(2, 1, u, tx);
     const int nb = c.nb_sl(N);
     c.sl_launch(nb, 0, N, tx, ty, dt, cf, cn, c.dwmix, c.dnotfound);
     KCHK();
-    std::vector<double> o(N);
-    std::vector<int32_t> nf(N);
-    HIPCHK(hipMemcpyAsync(o.data(), cn, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipMemcpyAsync(nf.data(), c.dnotfound, sizeof(int32_t) * N, hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipStreamSynchronize(c.st));
-    for (i64 g = 0; g < N; ++g) {
-      cout[c.ord.new2old[g]] = o[g];
-      if (notfound) notfound[c.ord.new2old[g]] = nf[g];
-    }
+    c.get_all(1, 1, cout, cn);
+    if (notfound) c.get_all(1, 1, notfound, c.dnotfound);
   });
 }
 
@@ -6422,15 +6306,8 @@ int pucfem_apply_bc(void* ctx, int32_t which, double* u) {
     require(!c.dist() && (c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD),
             "apply_bc needs a single-rank Stokes context");
     require(which >= 1 && which <= 3, "apply_bc: which must be 1 (periodic), 2 (Dirichlet) or 3 (both)");
-    const i64 N = c.mesh.N;
-    std::vector<double> bx(N), by(N);
-    for (i64 g = 0; g < N; ++g) {
-      bx[g] = u[2 * c.ord.new2old[g]];
-      by[g] = u[2 * c.ord.new2old[g] + 1];
-    }
     double *tx = c.cg_q[0], *ty = c.cg_q[1];  // scratch (the step's state stays untouched)
-    HIPCHK(hipMemcpyAsync(tx, bx.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(ty, by.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+    c.put_all(2, 1, (const double*)u, tx, ty);
     const int ncopy = (which & 1) ? c.ncopy : 0, ndir = (which & 2) ? c.ndir : 0;
     if (ncopy + ndir > 0) {
       if (c.bc_gather && ncopy > 0) {
@@ -6444,13 +6321,7 @@ int pucfem_apply_bc(void* ctx, int32_t which, double* u) {
                          1);
       KCHK();
     }
-    HIPCHK(hipMemcpyAsync(bx.data(), tx, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipMemcpyAsync(by.data(), ty, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipStreamSynchronize(c.st));
-    for (i64 g = 0; g < N; ++g) {
-      u[2 * c.ord.new2old[g]] = bx[g];
-      u[2 * c.ord.new2old[g] + 1] = by[g];
-    }
+    c.get_all(2, 1, u, tx, ty);
   });
 }
 
@@ -6460,24 +6331,12 @@ int pucfem_dye_step(void* ctx, const double* cin, const double* u, double* cout,
     c.need_dev();
     c.need_built();
     require(c.dye_impl, "dye_step needs a context built with dye_scheme = 1 (implicit)");
-    const i64 N = c.mesh.N;
-    std::vector<double> a(N), bxy(2 * N);
-    for (i64 g = 0; g < N; ++g) {
-      const i64 o = c.ord.new2old[g];
-      a[g] = cin[o];
-      bxy[2 * g] = u[2 * o];
-      bxy[2 * g + 1] = u[2 * o + 1];
-    }
-    // u as the step stores it (interleaved pairs) in scratch: the step's state stays untouched
-    if (!c.solve_tmp) c.solve_tmp = c.dalloc<double>(4 * c.nloc);
-    double *tx = c.solve_tmp, *ty = tx + 1, *cf = c.cg_pa[0], *cn = c.cg_pb[0], *dv = c.litw[8];
-    HIPCHK(hipMemcpyAsync(cf, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
-    HIPCHK(hipMemcpyAsync(tx, bxy.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c.st));
+    double *tx = c.u_scratch(), *ty = tx + 1, *cf = c.cg_pa[0], *cn = c.cg_pb[0], *dv = c.litw[8];
+    c.put_all(1, 1, cin, cf);
+    c.put_all(2, 1, u, tx);
     c.div(tx, ty, dv, false);
     const int it = c.dye_step(tx, ty, dv, cf, cn);
-    HIPCHK(hipMemcpyAsync(a.data(), cn, sizeof(double) * N, hipMemcpyDeviceToHost, c.st));
-    HIPCHK(hipStreamSynchronize(c.st));
-    for (i64 g = 0; g < N; ++g) cout[c.ord.new2old[g]] = a[g];
+    c.get_all(1, 1, cout, cn);
     if (iters) *iters = it;
   });
 }
@@ -6489,13 +6348,7 @@ int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps) {
     c.need_built();
     require(!c.dist(), "tracer_step unit op is single-rank");
     require(c.has_tgrid, "tracer_step needs a STOKES_FOOD context (the tracer grid)");
-    const i64 N = c.mesh.N;
-    std::vector<double> bxy(2 * N);  // (u interleaved, as the step stores it)
-    for (i64 g = 0; g < N; ++g) {
-      bxy[2 * g] = u[2 * c.ord.new2old[g]];
-      bxy[2 * g + 1] = u[2 * c.ord.new2old[g] + 1];
-    }
-    HIPCHK(hipMemcpyAsync(c.ux, bxy.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice, c.st));
+    c.put_all(2, 1, u, c.ux);  // (u interleaved, as the step stores it)
     for (int s = 0; s < nsteps; ++s) c.tracer_advance(dt);
     HIPCHK(hipStreamSynchronize(c.st));
   });
@@ -6548,11 +6401,8 @@ int pucfem_tracer_info(void* ctx, int32_t member, int64_t* out6) {
 // context: the two weighted sums, then the weighted variance about mu (k_mix2), then k_stats
 static void mixing_dev(Ctx& c, const double* cf, const double* w, double* out3);
 static void mixing_on(Ctx& c, const double* cin, const double* w, double* out3) {
-  const i64 N = c.mesh.N;
-  std::vector<double> a(N);
-  for (i64 g = 0; g < N; ++g) a[g] = cin[c.ord.new2old[g]];
   double* cf = c.cg_pa[0];
-  HIPCHK(hipMemcpyAsync(cf, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+  c.put_all(1, 1, cin, cf);
   mixing_dev(c, cf, w, out3);
 }
 // the same of a field cf already on the device (internal order; pucfem_dyes_mixing: a channel where it lies)
@@ -6600,11 +6450,8 @@ int pucfem_mixing_index_w(void* ctx, const double* cin, const double* w, double*
     c.need_built();
     require(!c.dist(), "mixing_index unit op is single-rank");
     require(w != nullptr, "mixing_index_w: weights");
-    const i64 N = c.mesh.N;
-    std::vector<double> a(N);
-    for (i64 g = 0; g < N; ++g) a[g] = w[c.ord.new2old[g]];
     double* dw = c.cg_q[0];
-    HIPCHK(hipMemcpyAsync(dw, a.data(), sizeof(double) * N, hipMemcpyHostToDevice, c.st));
+    c.put_all(1, 1, w, dw);
     mixing_on(c, cin, dw, out3);
   });
 }
@@ -6646,30 +6493,15 @@ int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* cin, const doub
     require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
     const i64 N = c.mesh.N;
     const size_t tot = (size_t)nch * (size_t)N;
-    std::vector<double> a(tot), bxy(2 * N);
-    for (i64 g = 0; g < N; ++g) {
-      const i64 o = c.ord.new2old[g];
-      for (int k = 0; k < nch; ++k) a[(size_t)k * N + g] = cin[(size_t)k * N + o];
-      bxy[2 * g] = u[2 * o];
-      bxy[2 * g + 1] = u[2 * o + 1];
-    }
-    // u as the step stores it (interleaved pairs) in scratch: the step's state stays untouched
-    if (!c.solve_tmp) c.solve_tmp = c.dalloc<double>(4 * c.nloc);
-    double *tx = c.solve_tmp, *ty = tx + 1;
+    double *tx = c.u_scratch(), *ty = tx + 1;
     double* din = c.smp_scratch<double>(14, tot);
     double* dout = c.smp_scratch<double>(15, tot);
     int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    c.h2d(din, a.data(), sizeof(double) * tot);
-    c.h2d(tx, bxy.data(), sizeof(double) * 2 * N);
+    c.put_all(1, nch, cin, din);
+    c.put_all(2, 1, u, tx);
     c.dye_launch(0, N, tx, ty, dt, nch, din, dout, c.dnotfound, dpart);
-    std::vector<int32_t> nf(N);
-    c.d2h(a.data(), dout, sizeof(double) * tot);
-    c.d2h(nf.data(), c.dnotfound, sizeof(int32_t) * N);
-    for (i64 g = 0; g < N; ++g) {
-      const i64 o = c.ord.new2old[g];
-      for (int k = 0; k < nch; ++k) cout[(size_t)k * N + o] = a[(size_t)k * N + g];
-      if (notfound) notfound[o] = nf[g];
-    }
+    c.get_all(1, nch, cout, dout);
+    if (notfound) c.get_all(1, 1, notfound, c.dnotfound);
   });
 }
 
@@ -6687,18 +6519,7 @@ int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2) {
     HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
     auto launch = [&] { c.dye_launch(0, N, c.ux, c.uy, c.prm.dt, nch, din, dout, nullptr, dpart); };
     launch();  // (untimed: the first launch)
-    hipEvent_t ea, eb;
-    HIPCHK(hipEventCreate(&ea));
-    HIPCHK(hipEventCreate(&eb));
-    HIPCHK(hipEventRecord(ea, c.st));
-    for (int k = 0; k < iters; ++k) launch();
-    HIPCHK(hipEventRecord(eb, c.st));
-    HIPCHK(hipEventSynchronize(eb));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
-    out2[0] = (double)ms / iters;
+    out2[0] = time_launches(c, iters, launch);
     out2[1] = c.dye_launch_bytes(nch, N);
   });
 }
@@ -7235,18 +7056,7 @@ int pucfem_bench_dir(void* ctx, int32_t variant, int32_t nblocks, int32_t iters,
       KCHK();
     };
     launch();
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
-    HIPCHK(hipEventRecord(a, c.st));
-    for (int k = 0; k < iters; ++k) launch();
-    HIPCHK(hipEventRecord(b, c.st));
-    HIPCHK(hipEventSynchronize(b));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
-    *ms_out = ms / iters;
+    *ms_out = time_launches(c, iters, launch);
   });
 }
 
@@ -7434,19 +7244,11 @@ int pucfem_bench_kernel(void* ctx, int32_t kernel, int32_t iters, double* ms_bat
       }
     };
     launch(nullptr, nullptr);
-    hipEvent_t ea, eb;
-    HIPCHK(hipEventCreate(&ea));
-    HIPCHK(hipEventCreate(&eb));
-    HIPCHK(hipEventRecord(ea, c.st));
-    for (int k = 0; k < iters; ++k) {
+    *ms_batch = time_launches(c, iters, [&] {
       launch(nullptr, nullptr);
       fill();
-    }
-    HIPCHK(hipEventRecord(eb, c.st));
-    HIPCHK(hipEventSynchronize(eb));
+    });
     float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, ea, eb));
-    *ms_batch = ms / iters;
     std::vector<hipEvent_t> ev(2 * (size_t)iters);
     for (auto& x : ev) HIPCHK(hipEventCreate(&x));
     for (int k = 0; k < iters; ++k) {
@@ -7462,8 +7264,6 @@ int pucfem_bench_kernel(void* ctx, int32_t kernel, int32_t iters, double* ms_bat
     }
     *ms_each = tot / iters;
     for (auto& x : ev) (void)hipEventDestroy(x);
-    (void)hipEventDestroy(ea);
-    (void)hipEventDestroy(eb);
     *bytes = by;
   });
 }

@@ -12,6 +12,7 @@
 #include <string>
 #include <algorithm>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <functional>
 #include <vector>
@@ -171,6 +172,42 @@ void make_ordering(const HostMesh& m, int nstrips, Ordering& ord);
 // rank -- on every level it appears on
 void make_ordering_cuts(const HostMesh& m, const std::vector<double>& cuts, Ordering& ord);
 int auto_strips(i64 N);
+
+// Caller numbering <-> internal numbering, for every array an entry point moves.  Internal rows r0 .. r0 + n - 1
+// (a rank's owned window, or all of them); `comp` (1 or 2) values per row, `planes` planes.  The caller's side holds
+// whole fields, comp interleaved, plane p at caller + p * cstride; the internal side holds the window alone, plane p
+// at + p * istride, comp interleaved in `in` (in1 null) or, for pairs, split into `in` and `in1`.  The element types
+// convert by a cast.  Serial on purpose (one loop to hand to parallel_for later).
+// f(index in the internal plane, in the second array?, index in the caller's plane) for every value of a plane's
+// rows; comp is a compile-time constant inside (a run-time comp made the loops 2.5 times slower)
+template <class F>
+void number_rows(const i32* n2o, i64 n, int comp, bool split, F&& f) {
+  auto rows = [&](auto K) {
+    constexpr int k = decltype(K)::value;
+    for (i64 i = 0; i < n; ++i)
+      for (int q = 0; q < k; ++q) f(split ? i : k * i + q, split && q, (i64)k * n2o[i] + q);
+  };
+  if (comp == 1) rows(std::integral_constant<int, 1>{});
+  else rows(std::integral_constant<int, 2>{});
+}
+template <class I, class C>
+void to_internal(const Ordering& ord, i64 r0, i64 n, int comp, i64 planes, i64 cstride, const C* caller, i64 istride,
+                 I* in, I* in1 = nullptr) {
+  for (i64 p = 0; p < planes; ++p) {
+    const C* c = caller + p * cstride;
+    I *a = in + p * istride, *b = in1 ? in1 + p * istride : nullptr;
+    number_rows(ord.new2old.data() + r0, n, comp, b != nullptr, [=](i64 i, bool second, i64 o) { (second ? b : a)[i] = (I)c[o]; });
+  }
+}
+template <class I, class C>
+void to_caller(const Ordering& ord, i64 r0, i64 n, int comp, i64 planes, i64 cstride, C* caller, i64 istride,
+               const I* in, const I* in1 = nullptr) {
+  for (i64 p = 0; p < planes; ++p) {
+    C* c = caller + p * cstride;
+    const I *a = in + p * istride, *b = in1 ? in1 + p * istride : nullptr;
+    number_rows(ord.new2old.data() + r0, n, comp, b != nullptr, [=](i64 i, bool second, i64 o) { c[o] = (C)(second ? b : a)[i]; });
+  }
+}
 
 // Node-adjacency pattern (incl. diagonal) in internal numbering, sorted columns.
 // node -> incident triangles (internal ids; ascending triangle ids per node)
