@@ -145,6 +145,9 @@ enum pucfem_field {
      channels" below.  pucfem_set_field with count = K * N defines K (0 .. PUCFEM_MAX_DYES); count = 0 removes the
      channels (buf may then be NULL). */
   PUCFEM_F_DYES = 13,
+  /* u_a (N,2) of the last inertial step, read only (setting it is PUCFEM_EINVAL): the velocity the viscous solve
+     took as its right-hand side, see "inertia" below.  PUCFEM_ESTATE before the first inertial step. */
+  PUCFEM_F_U_ADV = 14,
   /* channel k is field PUCFEM_F_DYE0 + k (N values, k < K) */
   PUCFEM_F_DYE0 = 64
 };
@@ -312,6 +315,31 @@ int pucfem_dyes_mixing(void* ctx, double* out /* K x 3 */);
    launch; out2[1]: algorithmic bytes per launch. */
 int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2);
 
+/* ---- inertia: semi-Lagrangian advection of the velocity in front of the viscous solve ---- */
+/* The reference's step is at Reynolds number zero: its viscous solve takes u + DT * 0 as the right-hand side
+   (StokesColor.py:540-547), the inertial term still a placeholder.  With inertia on, every pucfem_step first advects
+   the velocity by itself, each component by advect_semilagrange (StokesColor.py:347-389),
+     u_a = SL(u^n; u^n, dt),   u* = A_visc^-1 u_a,   then the projections, the dye / the tracers as before
+   (Stam's "stable fluids" splitting).  A step with inertia on holds, bit for bit on the direct-solve paths, what a
+   step without it computes after pucfem_set_field(PUCFEM_F_U, pucfem_sl_advect_vel(u, u, dt)); the iterative paths
+   also start the viscous solve from u_a and its increments.  A row whose departure point is not found keeps its
+   value.  Single-rank PUCFEM_STOKES_COLOR (either dye scheme) and PUCFEM_STOKES_FOOD contexts after
+   pucfem_build_operators, on every solver path, with or without dye channels; else PUCFEM_ESTATE (multi-rank, heat,
+   Poisson; before the build); PUCFEM_ENODEV on a host-only context.  Ensembles step without inertia:
+   pucfem_ens_create on a context with inertia on, and switching it on while an ensemble exists, are PUCFEM_ESTATE.
+   The N x 2 buffer of u_a is allocated when inertia is first switched on; pucfem_build_operators and
+   pucfem_ctx_destroy free it and switch inertia off.  Switching it on or off resets the viscous solve's
+   extrapolation history, as setting u does.  A small-mesh context steps from its captured graph only while inertia
+   is off; with it on it runs the same launches uncaptured behind the inertial one. */
+int pucfem_set_inertia(void* ctx, int32_t on);
+/* out[0] on, [1] inertial steps since it was switched on, [2] not-found rows of the last inertial launch (0 before
+   the first), [3] device bytes held for it */
+int pucfem_inertia_info(void* ctx, int64_t* out4);
+/* Measurement: the inertial launch (f = u = the context's current u, its dt, a scratch output), launched once untimed
+   and then `iters` times back to back between two events.  out2[0]: milliseconds per launch; out2[1]: algorithmic
+   bytes per launch. */
+int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2);
+
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,
    good_visualization.py:738).  These calls integrate the context's current u from caller-given seeds with the
@@ -392,6 +420,12 @@ int pucfem_sl_advect(void* ctx, const double* c, const double* u, double dt, dou
    context's channels are not touched.  Readiness as for the dye channels (below). */
 int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* c /* nch x N */, const double* u, double dt,
                            double* c_out /* nch x N */, int32_t* notfound /* N or NULL */);
+/* pucfem_sl_advect for the two components of an interleaved field f (N,2) at once, through the inertial step's
+   kernel on scratch buffers: one back-trace and one point location per node, each vertex's pair one load.
+   Component k of f_out and notfound (N or NULL) hold the bits pucfem_sl_advect returns for the vector f[:, k].
+   f may be u.  The step's state is not touched.  Readiness as for inertia (above). */
+int pucfem_sl_advect_vel(void* ctx, const double* f /* N x 2 */, const double* u /* N x 2 */, double dt,
+                         double* f_out /* N x 2 */, int32_t* notfound /* N or NULL */);
 /* tracer step (StokesFood.py:482-499) on the tracers held in the context, with u given */
 int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps);
 /* the context's tracer set (member = -1) or that of member `member` of its ensemble: out[0] tracers, [1] tracers

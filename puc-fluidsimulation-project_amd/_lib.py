@@ -21,6 +21,7 @@ F_CAPTURE_STEP = 11
 F_VORTICITY = 12
 F_DYES = 13  # all dye channels (K, N); channel k is field F_DYE0 + k
 F_DYE0 = 64
+F_U_ADV = 14  # u_a (N, 2) of the last inertial step, read only
 MAX_DYES = 16
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 OP_CURL = 11
@@ -107,6 +108,10 @@ SIGNATURES = {
     "pucfem_dyes_info": ([_P, _I64], ct.c_int),
     "pucfem_dyes_mixing": ([_P, _D], ct.c_int),
     "pucfem_dyes_probe": ([_P, ct.c_int32, ct.c_int32, _D], ct.c_int),
+    "pucfem_set_inertia": ([_P, ct.c_int32], ct.c_int),
+    "pucfem_inertia_info": ([_P, _I64], ct.c_int),
+    "pucfem_sl_advect_vel": ([_P, _D, _D, ct.c_double, _D, _I32], ct.c_int),
+    "pucfem_inertia_probe": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_dye_step": ([_P, _D, _D, _D, _I32], ct.c_int),
     "pucfem_comm_info": ([_P, ct.POINTER(ct.c_int64)], ct.c_int),

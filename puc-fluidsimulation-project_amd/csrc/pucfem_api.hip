@@ -30,6 +30,7 @@
 #include "pucfem_sample.hpp"
 #include "pucfem_streamline.hpp"
 #include "pucfem_dye_channels.hpp"
+#include "pucfem_inertia.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -563,8 +564,8 @@ struct Ctx {
   // Slot 9: the partials of the vorticity pass (4 x MAXB) and, behind them, pucfem_flow_info's four reduced values
   // Slots 10..13: pucfem_streamlines / pucfem_ens_streamlines (pucfem_streamline.hpp): the seeds, the points, the
   // status and npts (one buffer), the values along the lines
-  // Slots 14..16: pucfem_sl_advect_multi / pucfem_dyes_probe (pucfem_dye_channels.hpp): the fields in, the fields
-  // out, the blocks' not-found counts
+  // Slots 14..16: pucfem_sl_advect_multi / pucfem_dyes_probe (pucfem_dye_channels.hpp) and pucfem_sl_advect_vel /
+  // pucfem_inertia_probe (pucfem_inertia.hpp): the fields in, the fields out, the blocks' not-found counts
   static constexpr int SMP_SLOTS = 17;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
@@ -781,6 +782,7 @@ struct Ctx {
       if (graph_k) (void)hipGraphDestroy(graph_k);
       for (void* a : allocs) (void)hipFree(a);
       drop_dyes();
+      drop_inertia();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1138,6 +1140,90 @@ struct Ctx {
     return ndye ? 2 * sizeof(double) * (size_t)ndye * (size_t)mesh.N + sizeof(int32_t) * SLB : 0;
   }
 
+  // ------------------------------------------------------------------ inertia (pucfem_inertia.hpp)
+  // With inertia on, stokes_step advects the velocity by itself, u_a = SL(u^n; u^n, dt), in front of the viscous
+  // solve, which then reads u_a wherever it read u^n: as its right-hand side and as the base of its start and of its
+  // increments.  u_adv is one N x 2 interleaved buffer in the internal numbering, allocated when inertia is first
+  // switched on and freed by drop_inertia (it is not in `allocs`): a context that never enables it holds no new
+  // memory and launches nothing new.
+  bool inertia = false;
+  double* u_adv = nullptr;
+  int32_t* adv_nfpart = nullptr;  // per block of the last inertial launch: its not-found rows
+  int adv_nb = 0;                 // that launch's blocks (0: none since inertia was switched on)
+  i64 adv_steps = 0;              // inertial steps since inertia was switched on
+  bool adv_valid = false;         // u_adv holds the u_a of an inertial step
+  // per row: coordinates 16, u 16, the locator's share as sl_launch counts it (lattice: home face 4, cell entries 8,
+  // radii 8), the pair written 16 (the gathered vertices' lines are the rows' own)
+  double vel_launch_bytes(i64 n) const { return (48.0 + (lat_sl ? 20.0 : 0.0)) * (double)n; }
+  // the single-rank Stokes context inertia lives on
+  void inertia_ready() const {
+    need_built();
+    auto state = [](bool ok, const char* msg) {
+      if (!ok) throw Error(PUCFEM_ESTATE, msg);
+    };
+    state(scheme == PUCFEM_STOKES_COLOR || scheme == PUCFEM_STOKES_FOOD, "inertia needs a Stokes context");
+    state(!dist() && world == 1, "inertia is single-rank (a multi-rank context would need a wide halo of u)");
+    need_dev();
+    state(has_cgrid && (lat_sl ? llgrid.face != nullptr : lgrid.rec != nullptr), "the context has no point locator");
+  }
+  // k_sl_vel over rows [row0, row0 + n) on the current stream: out = SL(f; u, dt), all three interleaved pairs
+  void vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* out2, int32_t* nf,
+                  int32_t* nfpart) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
+    const dbl2* f = reinterpret_cast<const dbl2*>(f2);
+    dbl2* out = reinterpret_cast<dbl2*>(out2);
+    if (lat_sl)
+      klaunch(-1, vel_launch_bytes(n), k_sl_vel<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, cgrid, (int64_t)row0,
+              (int64_t)n, u, dt, f, out, nf, nfpart);
+    else
+      klaunch(-1, vel_launch_bytes(n), k_sl_vel<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0,
+              (int64_t)n, u, dt, f, out, nf, nfpart);
+    KCHK();
+  }
+  // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity)
+  void inertia_step() {
+    if (!inertia) return;
+    vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, adv_nfpart);
+    adv_nb = nb_dye(lp.n_own);
+    ++adv_steps;
+    adv_valid = true;
+  }
+  void drop_inertia() {
+    inertia = false;
+    adv_nb = 0;
+    adv_steps = 0;
+    adv_valid = false;
+    if (!u_adv && !adv_nfpart) return;
+    if (st) (void)hipStreamSynchronize(st);
+    for (void* q : {(void*)u_adv, (void*)adv_nfpart})
+      if (q) (void)hipFree(q);
+    u_adv = nullptr;
+    adv_nfpart = nullptr;
+  }
+  void set_inertia(bool on) {
+    inertia_ready();
+    if (on && ens) throw Error(PUCFEM_ESTATE, "inertia cannot be switched on while the context has an ensemble");
+    if (on == inertia) return;
+    if (on && !u_adv) {
+      const size_t bytes = sizeof(double) * 2 * (size_t)mesh.N;
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&u_adv), bytes));
+      HIPCHK(hipMalloc(reinterpret_cast<void**>(&adv_nfpart), sizeof(int32_t) * SLB));
+      HIPCHK(hipMemsetAsync(u_adv, 0, bytes, st));
+      HIPCHK(hipMemsetAsync(adv_nfpart, 0, sizeof(int32_t) * SLB, st));
+      HIPCHK(hipStreamSynchronize(st));
+    }
+    inertia = on;
+    if (on) {
+      adv_steps = 0;
+      adv_nb = 0;
+    }
+    have_vinc = 0;  // the viscous solve's right-hand side changes its meaning: no last increment
+  }
+  size_t inertia_dev_bytes() const {
+    return u_adv ? sizeof(double) * 2 * (size_t)mesh.N + sizeof(int32_t) * SLB : 0;
+  }
 
 
   // ------------------------------------------------------------------ fused reductions
@@ -2369,14 +2455,17 @@ struct Ctx {
   void halo_v(double* vx) { halo2(reinterpret_cast<dbl2*>(vx)); }
   int viscous(int& iters) {  // StokesColor.py:540-547
     const i64 n = lp.n_own;
+    // the right-hand side and the base of the start and of the increments: u^n, or with inertia on the advected u_a
+    // (inertia_step ran in front)
+    const double *rx = inertia ? u_adv : ux, *ry = rx + 1;
     if (dense) {  // u* = A_visc^-1 (u + DT * 0)
       if (dbcsrc && dir_ncomp == 2) {  // (velocity BCs: both components copied / set)
-        hipLaunchKernelGGL(k_dense_mv2_bc, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, ux,
-                           uy, usx, usy, (const int32_t*)dbcsrc, (const int32_t*)dbcdir, (const double*)ddval,
+        hipLaunchKernelGGL(k_dense_mv2_bc, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, rx,
+                           ry, usx, usy, (const int32_t*)dbcsrc, (const int32_t*)dbcdir, (const double*)ddval,
                            dir_ncomp);
         KCHK();
       } else {
-        hipLaunchKernelGGL(k_dense_mv2, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, ux, uy,
+        hipLaunchKernelGGL(k_dense_mv2, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, rx, ry,
                            usx, usy);
         KCHK();
         bc(usx, usy);
@@ -2403,11 +2492,11 @@ struct Ctx {
     const double prep_bytes = (56.0 + 8.0 * vd.order) * (double)n;
     if (cheb)
       klaunch(13, prep_bytes, k_visc_prep<true>, dim3(grid_ew(n)), dim3(BS), (int64_t)n, (const double*)dsv,
-              (const double*)ux, (const double*)uy, reinterpret_cast<double*>(vb2),
+              rx, ry, reinterpret_cast<double*>(vb2),
               (double*)nullptr, reinterpret_cast<double*>(vx2[0]), (double*)nullptr, vd);
     else
       klaunch(13, prep_bytes, k_visc_prep<false>, dim3(grid_ew(n)), dim3(BS), (int64_t)n, (const double*)dsv,
-              (const double*)ux, (const double*)uy, bvx, bvy, yvx, yvy, vd);
+              rx, ry, bvx, bvy, yvx, yvy, vd);
     KCHK();
     // with the extrapolated start the solve's last Chebyshev step also does k_visc_fin's work
     const int last = 2 * (visc_extrap - 1);
@@ -2415,14 +2504,14 @@ struct Ctx {
     if (cheb) {
       ViscFin vf{};
       const bool fuse = ext;
-      if (fuse) vf = ViscFin{dsv, {ux, uy}, {usx, usy}, {dvinc[last], dvinc[last + 1]}};
+      if (fuse) vf = ViscFin{dsv, {rx, ry}, {usx, usy}, {dvinc[last], dvinc[last + 1]}};
       dbl2* yo = vx2[0];  // the converged iterate (one of the solve's buffers)
       iters = vcheb(dP, fVisc, dKv, vx2[0], vb2, prm.rtol_visc, prm.maxit_visc, 0, &yo, fuse ? &vf : nullptr,
                     &fin_done);
       if (!fin_done) {  // u* = S y (and the increment)
         algo_bytes += (ext ? 64.0 : 40.0) * (double)n;  // s, y (, u) read; u* (, the fp32 increment) written
         hipLaunchKernelGGL(k_visc_fin, dim3(grid_ew(n)), dim3(BS), 0, st, (int64_t)n, (const double*)dsv,
-                           (const dbl2*)yo, (const double*)ux, (const double*)uy, usx, usy,
+                           (const dbl2*)yo, rx, ry, usx, usy,
                            ext ? dvinc[last] : (float*)nullptr, ext ? dvinc[last + 1] : (float*)nullptr);
       }
     } else {
@@ -2441,7 +2530,7 @@ struct Ctx {
       if (ext) {
         algo_bytes += 64.0 * (double)n;  // s, y, u read; u*, the fp32 increment written
         hipLaunchKernelGGL(k_visc_fin_soa, dim3(grid_ew(n)), dim3(BS), 0, st, (int64_t)n, (const double*)dsv,
-                           (const double*)yvx, (const double*)yvy, (const double*)ux, (const double*)uy, usx, usy,
+                           (const double*)yvx, (const double*)yvy, rx, ry, usx, usy,
                            dvinc[last], dvinc[last + 1]);
       } else {
         algo_bytes += 40.0 * (double)n;
@@ -2989,6 +3078,7 @@ struct Ctx {
   void stokes_step(double* rec, int32_t* its) {
     int itv = 0;
     ring_in_mix = false;
+    inertia_step();  // (reads u, as the previous step's dye tail on the side stream does: no join)
     viscous(itv);
     dye_tail_dist();  // (W > 1: the previous step's dye tail)
     // max |div u*| -> vals[0]; the div u* field itself is computed when read (pucfem_get_field): nothing in the
@@ -5140,6 +5230,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     }
     c.drop_step_graphs();
     if (!c.host_only) c.drop_dyes();
+    if (!c.host_only) c.drop_inertia();
     build(c);
   });
 }
@@ -5263,6 +5354,12 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
         require(count == 2 * N, "field is (N, 2)");
         c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)(field == PUCFEM_F_U ? c.ux : c.usx), (const double*)nullptr, false);
         break;
+      case PUCFEM_F_U_ADV:  // (the u_a of the last inertial step)
+        c.inertia_ready();
+        if (!c.adv_valid) throw Error(PUCFEM_ESTATE, "no inertial step has been taken: u_adv holds nothing");
+        require(count == 2 * N, "field is (N, 2)");
+        c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)c.u_adv, (const double*)nullptr, false);
+        break;
       case PUCFEM_F_C:
         require(count == N, "c is (N,)");
         c.allgather_full(c.c_full);  // multi-rank: collective (every rank reads c), the full field
@@ -5297,8 +5394,9 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       double* rec = c.dalloc<double>(8 * (i64)nsteps);
       int* dits = c.dalloc<int>(3 * (i64)nsteps);
       std::vector<int32_t> its(3 * (size_t)nsteps);
-      // (a context with dye channels steps uncaptured: the channels' buffers swap every step)
-      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0) {
+      // (a context with dye channels steps uncaptured: the channels' buffers swap every step; so does one with
+      // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step)
+      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -5593,6 +5691,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     state(c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD, "ensembles step Stokes contexts");
     state(!c.dist(), "ensembles run on a single-rank context");
     state(!c.dye_impl, "ensembles step the semi-Lagrangian dye, not the implicit variant");
+    state(!c.inertia, "ensembles step without inertia: switch it off first (pucfem_set_inertia)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
               c.sl_rec_wave(c.lp.n_own) && (c.scheme != PUCFEM_STOKES_FOOD || c.has_tgrid),
@@ -6521,6 +6620,65 @@ int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2) {
     launch();  // (untimed: the first launch)
     out2[0] = time_launches(c, iters, launch);
     out2[1] = c.dye_launch_bytes(nch, N);
+  });
+}
+
+// ---- inertia (pucfem_inertia.hpp)
+int pucfem_set_inertia(void* ctx, int32_t on) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.set_inertia(on != 0);
+  });
+}
+
+int pucfem_inertia_info(void* ctx, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();
+    require(out4 != nullptr, "null output");
+    int64_t nf = 0;
+    if (c.adv_nfpart && c.adv_nb > 0) {  // the blocks' counts of the last launch, in block order
+      std::vector<int32_t> part((size_t)c.adv_nb);
+      c.d2h(part.data(), c.adv_nfpart, sizeof(int32_t) * part.size());
+      for (int32_t v : part) nf += v;
+    }
+    out4[0] = c.inertia ? 1 : 0;
+    out4[1] = c.adv_steps;
+    out4[2] = nf;
+    out4[3] = (int64_t)c.inertia_dev_bytes();
+  });
+}
+
+int pucfem_sl_advect_vel(void* ctx, const double* f, const double* u, double dt, double* f_out, int32_t* notfound) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();
+    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    double* tu = c.u_scratch();
+    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    c.put_all(2, 1, f, din);
+    c.put_all(2, 1, u, tu);
+    c.vel_launch(0, N, tu, dt, din, dout, c.dnotfound, dpart);
+    c.get_all(2, 1, f_out, dout);
+    if (notfound) c.get_all(1, 1, notfound, c.dnotfound);
+  });
+}
+
+int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    const i64 N = c.mesh.N;
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    auto launch = [&] { c.vel_launch(0, N, c.ux, c.prm.dt, c.ux, dout, nullptr, dpart); };
+    launch();  // (untimed: the first launch)
+    out2[0] = time_launches(c, iters, launch);
+    out2[1] = c.vel_launch_bytes(N);
   });
 }
 

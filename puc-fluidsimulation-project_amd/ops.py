@@ -183,6 +183,27 @@ def advect_semilagrange_multi(C, u, DT, nodes=None, triangles=None):
     return nf.astype(bool)
 
 
+def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None):
+    """advect_semilagrange of the two components of f (N, 2) at once (pucfem_sl_advect_vel, the inertial step's
+    kernel): one back-trace and one point location per node, each component's bits those of advect_semilagrange
+    on f[:, k] alone.  f may be u (the inertial term's u_a = SL(u; u, DT)).  In place on f like the reference
+    (f[:] = f_new); returns the not-found mask (N,), the same for both components."""
+    if nodes is None or triangles is None:
+        m = _mesh_or_global(None)
+        nodes, triangles = m.coords, m.triangles
+    fin = np.ascontiguousarray(f, dtype=np.float64)
+    if fin.shape != (len(nodes), 2):
+        raise ValueError(f"advect_semilagrange_vector: f must have shape ({len(nodes)}, 2)")
+    ctx = context_for(nodes, triangles)
+    uu =np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros_like(fin)
+    nf = np.zeros(len(fin), dtype=np.int32)
+    _lib.check(ctx.L.pucfem_sl_advect_vel(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
+                                          _lib.iptr(nf)), ctx.h)
+    f[:] = out
+    return nf.astype(bool)
+
+
 def buildStiffnessMatrix(nodes, triangles, g_source=1.0):
     """StokesColor.py:98-128: (A, -B) with B = 0 (the reference never fills it)."""
     ctx = context_for(nodes, triangles)

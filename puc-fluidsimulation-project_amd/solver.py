@@ -499,6 +499,24 @@ class Context:
         self._c(self.L.pucfem_dyes_probe(self.h, int(nch), int(iters), o))
         return dict(kernel_ms=o[0], algo_bytes=o[1])
 
+    def set_inertia(self, on):
+        """Switch the inertial term on or off (pucfem_set_inertia): with it on, every step advects the velocity by
+        itself, u_a = SL(u; u, dt), in front of the viscous solve."""
+        self._c(self.L.pucfem_set_inertia(self.h, 1 if on else 0))
+
+    def inertia_info(self):
+        """The context's inertial term (pucfem_inertia_info): whether it is on, the inertial steps since it was
+        switched on, the not-found rows of the last inertial launch and the device bytes held for it."""
+        o = (ct.c_int64 * 4)()
+        self._c(self.L.pucfem_inertia_info(self.h, o))
+        return dict(on=bool(o[0]), steps=o[1], notfound=o[2], bytes=o[3])
+
+    def inertia_probe(self, iters=10):
+        """Kernel time of one inertial launch on the current u (pucfem_inertia_probe; tools/inertia_bench.py)."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_inertia_probe(self.h, int(iters), o))
+        return dict(kernel_ms=o[0], algo_bytes=o[1])
+
     def flow_info(self, member=None):
         """Flow summaries of the current u, reduced on the device (pucfem_flow_info; one launch, four doubles
         copied): max |vorticity|, the enstrophy 1/2 sum w vorticity^2, the kinetic energy 1/2 sum w |u|^2 and the
@@ -596,7 +614,7 @@ class StokesSimulation:
     or on one rank of a torch.distributed job (dist=(rank, world, unique_id))."""
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
-                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0):
+                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False):
         self.mesh = mesh
         self.bc = bc or SquirmerBC()
         self.dt = dt
@@ -621,6 +639,12 @@ class StokesSimulation:
             pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
             self.ctx.set_field(_lib.F_TRACERS, pts)
             self.n_tracers = len(pts)
+        if inertia:
+            try:
+                self.ctx.set_inertia(True)
+            except Exception:
+                self.ctx.close()
+                raise
 
     def step(self, n=1):
         st = self.ctx.step(n)
@@ -665,6 +689,27 @@ class StokesSimulation:
             self.ctx._c(self.ctx.L.pucfem_set_field(self.ctx.h, _lib.F_DYES, None, 0))
         else:
             self.ctx.set_field(_lib.F_DYES, a)
+
+    @property
+    def inertia(self):
+        """Whether the steps carry the inertial term: u_a = SL(u; u, dt), each velocity component advected by the
+        semi-Lagrangian scheme of the dye, in front of the viscous solve (finite Reynolds number; off: the
+        reference's Stokes step).  Setting it takes effect at the next step."""
+        return self.ctx.inertia_info()["on"]
+
+    @inertia.setter
+    def inertia(self, on):
+        self.ctx.set_inertia(bool(on))
+
+    @property
+    def u_advected(self):
+        """(N, 2) the u_a of the last inertial step (PUCFEM_F_U_ADV): what its viscous solve took as right-hand side."""
+        return self.ctx.get_field(_lib.F_U_ADV, (self.mesh.N, 2))
+
+    def inertia_info(self):
+        """Context.inertia_info of this run as (on, steps, notfound, bytes)."""
+        d = self.ctx.inertia_info()
+        return d["on"], d["steps"], d["notfound"], d["bytes"]
 
     def dye_mixing(self):
         """(K, 3): mixing_index (StokesColor.py:391-403) (I, mu, var) of every dye channel over marker == 0, reduced
@@ -1074,19 +1119,23 @@ class Result:
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
-          tol: Tolerances | None = None, log=None, dyes=None):
+          tol: Tolerances | None = None, log=None, dyes=None, inertia=False):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
     backward Euler), 'poisson' = poisson.py (one steady solve).  `log`, if given, receives the
     reference's per-step print line (StokesColor.py:586 / StokesFood.py:505).  dyes (scheme 'color'): (K, N) dye
-    channels advected beside c (StokesSimulation.dyes); the result's `dyes` holds them after the last step."""
+    channels advected beside c (StokesSimulation.dyes); the result's `dyes` holds them after the last step.
+    inertia (schemes 'color' and 'food'): every step advects the velocity by itself in front of the viscous solve
+    (StokesSimulation.inertia)."""
     if dyes is not None and scheme != "color":
         raise ValueError("dyes belong to scheme 'color'")
+    if inertia and scheme not in ("color", "food"):
+        raise ValueError("inertia belongs to the Stokes schemes 'color' and 'food'")
     if scheme in ("color", "food"):
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
-        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol)
+        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia)
         if dyes is not None:
             sim.dyes = dyes
         st = sim.step(steps) if steps else []
