@@ -238,7 +238,10 @@ int pucfem_ens_destroy(void* ctx);
 /* fields PUCFEM_F_U, _USTAR, _P, _P2, _C, _TRACERS, _STATUS (and, read only, _CAPTURE_STEP and _VORTICITY, the
    latter formed from the members' u when read into a buffer of the ensemble's own) in the caller's numbering;
    member = -1: all members, member-major (count = members x the field's values per member).  Setting
-   TRACERS clears the status, the capture steps and the step count of the members it sets. */
+   TRACERS clears the status, the capture steps and the step count of the members it sets.
+   PUCFEM_F_U_ADV, read only (setting it is PUCFEM_EINVAL): the member's u_a of its last inertial step, see
+   pucfem_ens_set_inertia; PUCFEM_ESTATE when a requested member has taken none since it was switched on (with
+   member = -1: as soon as any member has taken none). */
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count);
 int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, int64_t count);
 /* nsteps steps of every member (StokesColor.py:537-586 / StokesFood.py:441-505 per member); stats: NULL or
@@ -325,8 +328,9 @@ int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2);
    also start the viscous solve from u_a and its increments.  A row whose departure point is not found keeps its
    value.  Single-rank PUCFEM_STOKES_COLOR (either dye scheme) and PUCFEM_STOKES_FOOD contexts after
    pucfem_build_operators, on every solver path, with or without dye channels; else PUCFEM_ESTATE (multi-rank, heat,
-   Poisson; before the build); PUCFEM_ENODEV on a host-only context.  Ensembles step without inertia:
-   pucfem_ens_create on a context with inertia on, and switching it on while an ensemble exists, are PUCFEM_ESTATE.
+   Poisson; before the build); PUCFEM_ENODEV on a host-only context.  The context's flag is for pucfem_step alone:
+   ensembles carry their own flags, one per member (pucfem_ens_set_inertia below), and the two stay apart --
+   pucfem_ens_create on a context whose flag is on, and switching it on while an ensemble exists, are PUCFEM_ESTATE.
    The N x 2 buffer of u_a is allocated when inertia is first switched on; pucfem_build_operators and
    pucfem_ctx_destroy free it and switch inertia off.  Switching it on or off resets the viscous solve's
    extrapolation history, as setting u does.  A small-mesh context steps from its captured graph only while inertia
@@ -339,6 +343,19 @@ int pucfem_inertia_info(void* ctx, int64_t* out4);
    and then `iters` times back to back between two events.  out2[0]: milliseconds per launch; out2[1]: algorithmic
    bytes per launch. */
 int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2);
+/* Inertia per ensemble member: the reference's comparison of swimmers at finite Reynolds number, or a Stokes twin
+   beside each inertial swimmer, in one launch chain.  A member whose flag is on steps u_a = SL(u^n; u^n, dt) and then
+   the ensemble's step with u_a as the viscous product's input: bit for bit a pucfem_step run with inertia on and the
+   member's boundary values.  A member whose flag is off steps as without this call.  Flags may differ between
+   members; a flag set between two pucfem_ens_step calls takes effect at the next step, and switching a member on
+   starts its counts again.  The step stays one captured chain, with the inertial launch in front while at least one
+   flag is on.  The members' u_a (members x N x 2) and the launch's partials are allocated when a flag is first
+   switched on, are counted in pucfem_ens_info's bytes and are freed with the ensemble.
+   member = -1: every member.  PUCFEM_ESTATE without an ensemble; PUCFEM_EINVAL for a member out of range. */
+int pucfem_ens_set_inertia(void* ctx, int32_t member /* -1 = all */, int32_t on);
+/* member 0 .. members - 1: out[0] on, [1] inertial steps since the member was switched on, [2] not-found rows of its
+   last inertial launch (summed on the device; 0 before the first), [3] device bytes the ensemble holds for inertia */
+int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4);
 
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,

@@ -149,7 +149,20 @@ struct Ens {
   // partials (M x 4 nb_div), the reduced values (M x ENS_VALS, slots 0..3) and the launch's ticket counters (M)
   double *vort = nullptr, *part_curl = nullptr, *flow = nullptr;
   unsigned* cnt_curl = nullptr;
-  int nb_tr = 1;              // blocks in x of the tracer launch (1: k_ens_tracer)
+  // inertia per member (pucfem_ens_set_inertia; k_ens_sl_vel), allocated when a flag is first switched on and kept:
+  // the members' u_a (M x 2n), the flags as the kernels read them (M), the launch's partials (M x nb_sl) and ticket
+  // counters (M).  A member's not-found count of its last inertial launch is slot 10 of its vals.
+  double *ua = nullptr, *part_adv = nullptr;
+  int32_t* adv_on_dev = nullptr;
+  unsigned* cnt_adv = nullptr;
+  size_t adv_bytes = 0;
+  std::vector<int32_t> adv_on;     // the flags (empty: never enabled)
+  std::vector<int64_t> adv_steps;  // per member: inertial steps since it was switched on
+  std::vector<double> adv_vals;    // host copy of vals, current while !adv_stale (the not-found counts)
+  bool adv_stale = true;
+  int adv_any = 0;                 // members with their flag on
+  bool chain_adv = false;          // the captured graphs hold the inertial launch
+  int nb_tr = 1;             // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
   int ring_steps = 0;
@@ -168,11 +181,17 @@ struct Ens {
     bytes += b;
     return (T*)q;
   }
-  ~Ens() {
+  // the cached step graphs (the caller has synchronised the stream): the next pucfem_ens_step captures again
+  void drop_graphs() {
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
     if (gexec_k) (void)hipGraphExecDestroy(gexec_k);
     if (graph_k) (void)hipGraphDestroy(graph_k);
+    graph = graph_k = nullptr;
+    gexec = gexec_k = nullptr;
+  }
+  ~Ens() {
+    drop_graphs();
     for (void* a : allocs) (void)hipFree(a);
   }
 };
@@ -5556,9 +5575,21 @@ void ens_enqueue_step(Ctx& c) {
   const int tiles = (M + ENS_TM - 1) / ENS_TM;
   hipStream_t st = c.st;
   const DevSell& A = c.dP;
+  // with at least one member's inertia on: u_a = SL(u^n; u^n, dt) of those members in front, and the viscous product
+  // takes it as their input (Ctx::inertia_step / Ctx::viscous of the single path)
+  const bool adv = e.adv_any > 0;
+  if (adv) {
+    const RedOut ra{e.vals + 10, nullptr, e.cnt_adv, 1, 0, 0u};
+    hipLaunchKernelGGL(k_ens_sl_vel, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
+                       c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, e.ua,
+                       e.part_adv, ra);
+    KCHK();
+  }
   hipLaunchKernelGGL(k_ens_mv2_bc<ENS_TM>, dim3(e.gx_dense, tiles), dim3(BS), e.lds_mv, st, (int64_t)n, M,
                      (const double*)c.dVinv, (const double*)e.u, e.us, (const int32_t*)c.dbcsrc,
-                     (const int32_t*)c.dbcdir, (const double*)e.dval, (int64_t)e.dstride);
+                     (const int32_t*)c.dbcdir, (const double*)e.dval, (int64_t)e.dstride,
+                     adv ? (const double*)e.ua : (const double*)nullptr,
+                     adv ? (const int32_t*)e.adv_on_dev : (const int32_t*)nullptr);
   KCHK();
   // max |div| into vals slot `slot`; with rhs the pressure right-hand side and its sum (slot 9)
   auto div = [&](const double* u, int slot, bool rhs) {
@@ -5661,12 +5692,15 @@ EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
     case PUCFEM_F_P2: return {e.p2, e.n, 1};
     case PUCFEM_F_C: return {e.c, e.n, 1};
     case PUCFEM_F_VORTICITY: ens_flow_bufs(c, e); return {e.vort, e.n, 1};  // (read only; ens_curl fills it)
+    case PUCFEM_F_U_ADV:  // (read only: the members' u_a of their last inertial step)
+      if (!e.ua) throw Error(PUCFEM_ESTATE, "no member has taken an inertial step: u_adv holds nothing");
+      return {e.ua, 2 * e.n, 2};
     case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
     case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
     case PUCFEM_F_CAPTURE_STEP: return {nullptr, (i64)e.ntr, 0};
     default:
       throw Error(PUCFEM_EINVAL,
-                  "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, TRACERS, STATUS, CAPTURE_STEP)");
+                  "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, U_ADV, TRACERS, STATUS, CAPTURE_STEP)");
   }
 }
 }  // namespace
@@ -5788,6 +5822,65 @@ int pucfem_ens_info(void* ctx, int64_t* out4) {
   });
 }
 
+// ---- inertia per member (k_ens_sl_vel, pucfem_ensemble.hpp)
+int pucfem_ens_set_inertia(void* ctx, int32_t member, int32_t on) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    c.inertia_ready();
+    const size_t sM = (size_t)e.M;
+    const int32_t v = on != 0 ? 1 : 0;
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
+    if (e.adv_on.empty()) {
+      if (!v) return;  // (nothing was ever on: nothing to switch off, and nothing is allocated)
+      const size_t before = e.bytes;
+      e.ua = e.alloc<double>(sM * 2 * e.n, c.st);
+      e.part_adv = e.alloc<double>(sM * e.nb_sl, c.st);
+      e.adv_on_dev = e.alloc<int32_t>(sM, c.st);
+      e.cnt_adv = e.alloc<unsigned>(sM, c.st);
+      e.adv_bytes = e.bytes - before;
+      e.adv_on.assign(sM, 0);
+      e.adv_steps.assign(sM, 0);
+    }
+    bool changed = false;
+    for (size_t m = m0; m < m1; ++m) {
+      if (e.adv_on[m] == v) continue;
+      e.adv_on[m] = v;
+      changed = true;
+      if (v) {  // (switched on: its counts start again, as pucfem_set_inertia's do)
+        e.adv_steps[m] = 0;
+        HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 10, 0, sizeof(double), c.st));
+        e.adv_stale = true;
+      }
+    }
+    if (!changed) return;
+    e.adv_any = (int)std::count(e.adv_on.begin(), e.adv_on.end(), 1);
+    c.h2d(e.adv_on_dev, e.adv_on.data(), sizeof(int32_t) * sM);
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= 0 && member < e.M, "member index out of range");
+    require(out4 != nullptr, "null output");
+    const size_t m = (size_t)member;
+    const bool have = !e.adv_on.empty();
+    if (have && e.adv_stale) {  // (one copy serves the calls for every member until the next step)
+      e.adv_vals.resize((size_t)e.M * ENS_VALS);
+      c.d2h(e.adv_vals.data(), e.vals, sizeof(double) * e.adv_vals.size());
+      e.adv_stale = false;
+    }
+    out4[0] = have ? e.adv_on[m] : 0;
+    out4[1] = have ? e.adv_steps[m] : 0;
+    out4[2] = have ? (int64_t)std::llround(e.adv_vals[ENS_VALS * m + 10]) : 0;
+    out4[3] = (int64_t)e.adv_bytes;
+  });
+}
+
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
@@ -5795,6 +5888,7 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     require(member >= -1 && member < e.M, "member index out of range");
     require(field != PUCFEM_F_CAPTURE_STEP, "capture steps cannot be set");
     require(field != PUCFEM_F_VORTICITY, "the vorticity cannot be set");
+    require(field != PUCFEM_F_U_ADV, "u_adv cannot be set: it is the inertial step's own output");
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
@@ -5817,6 +5911,10 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
+    if (field == PUCFEM_F_U_ADV)  // (every requested member's plane must hold the u_a of a step of its own)
+      for (i64 m = m0; m < m0 + nm; ++m)
+        if (e.adv_steps[(size_t)m] == 0)
+          throw Error(PUCFEM_ESTATE, "a requested member has taken no inertial step since it was switched on");
     if (f.per == 0) return;
     if (field == PUCFEM_F_CAPTURE_STEP) return capture_steps_get(c, e.trcap, m0 * e.ntr, nm * e.ntr, buf);
     if (field == PUCFEM_F_TRACERS) return tracers_get(c, e.trx, e.try_, m0 * e.ntr, nm * e.ntr, buf);
@@ -5849,6 +5947,13 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       HIPCHK(hipStreamEndCapture(c.st, &gr));
       HIPCHK(hipGraphInstantiate(&ex, gr, nullptr, nullptr, 0));
     };
+    // (the chain has the inertial launch iff a member's flag is on: graphs of the other chain are dropped.  Which
+    // members are on is read from device memory by the kernels, so it needs no new capture.)
+    if (e.chain_adv != (e.adv_any > 0)) {
+      HIPCHK(hipStreamSynchronize(c.st));
+      e.drop_graphs();
+      e.chain_adv = e.adv_any > 0;
+    }
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
     std::vector<double> h(stats ? 8 * sM * (size_t)nsteps : 0);
@@ -5873,6 +5978,11 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     }
     HIPCHK(hipStreamSynchronize(c.st));
     e.steps += nsteps;
+    if (e.adv_any > 0) {
+      for (size_t m = 0; m < sM; ++m)
+        if (e.adv_on[m]) e.adv_steps[m] += nsteps;
+      e.adv_stale = true;
+    }
     if (stats)
       for (size_t k = 0; k < (size_t)nsteps * sM; ++k) {
         pucfem_step_stats& o = stats[k];
@@ -6036,6 +6146,7 @@ int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t
     SampleFields F{};
     for (int32_t k = 0; k < nfields; ++k) {
       require(fields[k] != PUCFEM_F_TRACERS && fields[k] != PUCFEM_F_STATUS, "tracer fields are not rasterised");
+      require(fields[k] != PUCFEM_F_U_ADV, "u_adv is read with pucfem_ens_get_field, not rasterised");
       const EnsField f = ens_field(c, e, fields[k]);
       for (int q = 0; q < f.comp; ++q) sample_push(F, f.a + q, f.comp, f.per);
     }

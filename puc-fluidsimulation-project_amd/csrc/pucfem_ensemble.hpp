@@ -21,7 +21,9 @@ namespace pucfem {
 namespace dev {
 
 constexpr int ENS_TM = 4;     // members per block of the dense products
-constexpr int ENS_VALS = 16;  // per-member value slots (k_stats' layout in 0..6; 8: scratch maximum, 9: sum(braw))
+// per-member value slots (k_stats' layout in 0..6; 8: scratch maximum, 9: sum(braw), 10: not-found rows of the
+// member's last inertial launch)
+constexpr int ENS_VALS = 16;
 
 // the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
 // (NP partial arrays of gridDim.x blocks per member)
@@ -39,18 +41,21 @@ __device__ __forceinline__ RedOut ens_red(const RedOut& ro, int32_t m, double*& 
 // k_dense_mv2_bc for a tile of members: u* = A_visc^-1 u with the velocity BCs of the result.  u, us: M x 2n;
 // dval: M x dstride (the member's Dirichlet values in the context's entry order).  Dynamic LDS: 2 n ENS_TM doubles
 // (component-major per member: consecutive lanes read consecutive doubles).  A ragged last tile computes its
-// missing members as copies of the last member and does not store them.
+// missing members as copies of the last member and does not store them.  With inertia (advon non-null: the members'
+// flags) a member whose flag is set stages its plane of ua (M x 2n, k_ens_sl_vel's output) instead of its u: the
+// single path's viscous product takes u_a as its input.  The rows' accumulation is the same either way.
 template <int TM>
 __global__ __launch_bounds__(BS) void k_ens_mv2_bc(int64_t n, int32_t M, const double* __restrict__ Ainv,
                                                    const double* __restrict__ u, double* __restrict__ us,
                                                    const int32_t* __restrict__ bsrc, const int32_t* __restrict__ bdir,
-                                                   const double* __restrict__ dval, int64_t dstride) {
+                                                   const double* __restrict__ dval, int64_t dstride,
+                                                   const double* __restrict__ ua, const int32_t* __restrict__ advon) {
   extern __shared__ __align__(16) double ens_xl[];
   const int32_t m0 = (int32_t)blockIdx.y * TM;
 #pragma unroll
   for (int t = 0; t < TM; ++t) {
     const int32_t mt = m0 + t < M ? m0 + t : M - 1;
-    const dbl2* x = reinterpret_cast<const dbl2*>(u) + (int64_t)mt * n;
+    const dbl2* x = reinterpret_cast<const dbl2*>(advon && advon[mt] ? ua : u) + (int64_t)mt * n;
     for (int64_t j = threadIdx.x; j < n; j += BS) {
       const dbl2 q = x[j];
       ens_xl[(2 * t) * n + j] = q.x;
@@ -372,6 +377,65 @@ __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, 
       for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
       red_part(R, part, v, a);
     }
+  }
+  red_finish(R, part, sh);
+}
+
+// The inertial launch per member (pucfem_ens_set_inertia): ua = SL(u; u, dt) of the member's own interleaved
+// velocity, in front of k_ens_mv2_bc.  k_ens_sl's back-trace and locate, call for call, on k_ens_sl's grid in x (one
+// wave per row), then k_sl_vel's interpolation (pucfem_inertia.hpp): sl_value's weights with pdx, computed once,
+// component k = w1 * f[a].k + w2 * f[b].k + w3 * f[d].k in that operand order, so a member's ua holds the bits of the
+// single path's u_adv.  Three 16-byte gathers from the member's u, one 16-byte store into its plane of ua; a row that
+// is not found keeps its own pair.  The sequence is restated, not shared with k_ens_sl or k_sl_vel, so those compile
+// to what they did.  A member whose flag is off leaves at once (a block-uniform exit in front of every barrier: its
+// ticket is not drawn).  The not-found rows of each member: per-block partials, summed by red_finish in block order.
+// u, ua: M x 2n (ua must not alias u: rows of other blocks still gather from u); on: M; part: M x gridDim.x.
+__global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                   const double* __restrict__ u, double dt,
+                                                   const int32_t* __restrict__ on, double* __restrict__ ua, double* part,
+                                                   RedOut ro) {
+  __shared__ double sw_[BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (!on[m]) return;
+  const dbl2* f = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  dbl2* out = reinterpret_cast<dbl2*>(ua) + (int64_t)m * n;
+  const RedOut R = ens_red<1>(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nnf = 0.0;
+  if (i < n) {
+    const dbl2 v = f[i];
+    double xb, yb;
+    sl_point(Mh, i, v.x, v.y, dt, xb, yb);
+    SlTri r;
+    double bestd;
+    float rho2;
+    const bool cand = sl_best_wave(L, xb, yb, r, bestd, rho2);
+    const bool ok = cand && (sl_fast(L, r, xb, yb, bestd, rho2) || sl_rank_ok_wave(G, xb, yb, bestd, r.id));
+    dbl2 o;
+    if (ok) {
+      const dbl2 fa = f[r.a], fb = f[r.b], fd = f[r.d];
+      // sl_value's weights (StokesColor.py:374-386), once for both components
+      const double x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2, x3 = r.x3, y3 = r.y3;
+      const double det = pdx(x2, x1) * (y3 - y1) - pdx(x3, x1) * (y2 - y1);
+      const double w1 = (pdx(x2, xb) * (y3 - yb) - pdx(x3, xb) * (y2 - yb)) / det;
+      const double w2 = (pdx(x3, xb) * (y1 - yb) - pdx(x1, xb) * (y3 - yb)) / det;
+      const double w3 = 1.0 - w1 - w2;
+      o.x = w1 * fa.x + w2 * fb.x + w3 * fd.x;
+      o.y = w1 * fa.y + w2 * fb.y + w3 * fd.y;
+    } else {
+      o = v;
+      nnf = 1.0;
+    }
+    if (lane == 0) out[i] = o;
+  }
+  if (lane == 0) sw_[wv] = nnf;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int k = 0; k < BS / 64; ++k) a += sw_[k];
+    red_part(R, part, 0, a);
   }
   red_finish(R, part, sh);
 }

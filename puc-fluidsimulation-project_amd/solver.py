@@ -795,6 +795,16 @@ def _check_ensemble_bcs(bcs):
     return bcs
 
 
+def _ensemble_flags(inertia, M):
+    """The inertia= argument of an ensemble of M members as an (M,) bool array: one bool for all, or M of them."""
+    a = np.asarray(inertia)
+    if a.ndim == 0:
+        return np.full(M, bool(a))
+    if a.shape != (M,):
+        raise ValueError(f"inertia must be a bool or one bool per member: {M} members, got shape {a.shape}")
+    return a.astype(bool)
+
+
 def ensemble_dirichlet_values(mesh: Mesh, bcs):
     """Dirichlet nodes and per-member values (M, n_dir, 2) of an ensemble: row m is stokes_setup(mesh, bcs[m])'s
     values (the wall values, then the squirmer surface values of makeDirBCU, StokesColor.py:405-427).  Host only."""
@@ -816,13 +826,16 @@ class StokesEnsemble:
     experiment (README.md:43-45: the neutral, pusher and puller squirmer on mesh.1) or a B1 / B2 sweep in one
     launch chain.  Members share nu, dt, the mesh and the swimmer's geometry and differ in their boundary values,
     fields and tracers; each member's fields are bit-identical to a StokesSimulation with its SquirmerBC.
-    Small meshes only (the dense path: N <= 1500), scheme 'color' (semi-Lagrangian dye) or 'food'."""
+    Small meshes only (the dense path: N <= 1500), scheme 'color' (semi-Lagrangian dye) or 'food'.
+    inertia: a bool for all members or one bool per member -- a member with it on steps as
+    StokesSimulation(..., inertia=True) does, bit for bit (finite Reynolds number); the others step as before."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
-                 tracers=None):
+                 tracers=None, inertia=False):
         self.bcs = _check_ensemble_bcs(bcs)
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
+        flags = _ensemble_flags(inertia, len(self.bcs))
         nodes, vals = ensemble_dirichlet_values(mesh, self.bcs)
         self.mesh = mesh
         self.dt = dt
@@ -846,6 +859,8 @@ class StokesEnsemble:
                 self.ctx.set_field(_lib.F_TRACERS, pts)
                 self.n_tracers = len(pts)
             self.ctx._c(self.ctx.L.pucfem_ens_create(self.ctx.h, self.M, _lib.dptr(vals)))
+            if flags.any():
+                self.inertia = flags
         except Exception:
             self.ctx.close()
             raise
@@ -895,6 +910,48 @@ class StokesEnsemble:
     def vorticity(self):
         """(M, N): every member's vorticity, formed on the device when read."""
         return self.get(_lib.F_VORTICITY)
+
+    # ---- inertia per member (pucfem_ens_set_inertia)
+    def set_inertia(self, on, member=None):
+        """Switch the inertial term of one member (or, member=None, of all) on or off; it takes effect at the next
+        step.  Switching a member on starts its counts (inertia_info) again."""
+        self.ctx._c(self.ctx.L.pucfem_ens_set_inertia(self.ctx.h, -1 if member is None else int(member),
+                                                      1 if on else 0))
+
+    def inertia_info(self, member=None):
+        """pucfem_ens_inertia_info: on, the inertial steps since the member was switched on, the not-found rows of its
+        last inertial launch and the device bytes the ensemble holds for inertia -- one member's dict, or
+        (member=None) a dict of (M,) arrays."""
+        def one(m):
+            o = (ct.c_int64 * 4)()
+            self.ctx._c(self.ctx.L.pucfem_ens_inertia_info(self.ctx.h, int(m), o))
+            return dict(on=bool(o[0]), steps=int(o[1]), notfound=int(o[2]), bytes=int(o[3]))
+
+        if member is not None:
+            return one(member)
+        rows = [one(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in ("on", "steps", "notfound", "bytes")}
+
+    @property
+    def inertia(self):
+        """(M,) bool: which members carry the inertial term u_a = SL(u; u, dt) in front of the viscous product
+        (StokesSimulation.inertia per member).  Set it with one bool for all or one per member."""
+        return self.inertia_info()["on"]
+
+    @inertia.setter
+    def inertia(self, on):
+        flags = _ensemble_flags(on, self.M)
+        if flags.all() or not flags.any():
+            self.set_inertia(bool(flags[0]))
+        else:
+            for m, f in enumerate(flags):
+                self.set_inertia(bool(f), m)
+
+    @property
+    def u_advected(self):
+        """(M, N, 2) every member's u_a of its last inertial step (PUCFEM_F_U_ADV); members that have taken none
+        since they were switched on make this an error: read one member with get(F_U_ADV, 2, member)."""
+        return self.get(_lib.F_U_ADV, 2)
 
     def flow_info(self):
         """Context.flow_info of every member (one call each): {name: (M,) array}."""
@@ -977,12 +1034,14 @@ class StokesEnsemble:
         self.ctx.close()
 
 
-def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None):
-    """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`."""
+def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
+                   inertia=False):
+    """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
+    for all members or one per member (StokesEnsemble.inertia)."""
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
-    ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol)
+    ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
