@@ -571,6 +571,13 @@ struct Ctx {
   DyeOp dyeop;  // host data of the implicit dye operator (built with the host operators)
   LatLocDev llgrid{};  // lattice locator (lat_sl): replaces lgrid's records on lattice hierarchies
   bool lat_sl = false;
+  // f(the context's locator), llgrid or lgrid: one launch site instantiates a kernel for both (as with_c16)
+  template <class F>
+  void with_loc(F&& f) const {
+    if (lat_sl) f(llgrid);
+    else f(lgrid);
+  }
+  bool has_locator() const { return lat_sl ? llgrid.face != nullptr : lgrid.rec != nullptr; }
   double* part_sl = nullptr;  // k_sl partials, 3 x SLB
   int32_t* sl_queue = nullptr; // k_sl -> k_sl_slow: rows off the lattice fast path (mesh.N)
   int32_t* sl_qcnt = nullptr; // per wave of k_sl: queued entries (SLB * BS / 64)
@@ -1083,6 +1090,13 @@ struct Ctx {
   int dye_nb = 0;                 // that launch's blocks (0: none since the channels were set)
   i64 dye_steps = 0;
   static int nb_dye(i64 n) { return (int)std::max<i64>(1, std::min<i64>(SLB, (n + BS - 1) / BS)); }
+  // the not-found rows of the last one-pass launch (k_sl_multi, k_sl_vel): its nb blocks' counts, in block order
+  int64_t nf_rows(const int32_t* nfpart, int nb) {
+    if (!nfpart || nb <= 0) return 0;
+    std::vector<int32_t> part((size_t)nb);
+    d2h(part.data(), nfpart, sizeof(int32_t) * part.size());
+    return std::accumulate(part.begin(), part.end(), (int64_t)0);
+  }
   // per row: coordinates 16, u 16 and the locator's share as sl_launch counts it (lattice: home face 4, cell
   // entries 8, radii 8); per channel and row: the old value read 8 (the vertices' lines are the rows' own), the
   // new one written 8
@@ -1098,19 +1112,17 @@ struct Ctx {
           "dye channels are single-rank (a multi-rank context would need the dye's wide halo per channel)");
     state(!dye_impl, "dye channels follow the semi-Lagrangian dye (dye_scheme = 0)");
     need_dev();
-    state(has_cgrid && (lat_sl ? llgrid.face != nullptr : lgrid.rec != nullptr), "the context has no point locator");
+    state(has_cgrid && has_locator(), "the context has no point locator");
   }
   // k_sl_multi over rows [row0, row0 + n) on the current stream: nch channels of leading dimension N
   void dye_launch(i64 row0, i64 n, const double* vx, const double* vy, double dt, int nch, const double* cin,
                   double* cout, int32_t* nf, int32_t* nfpart) {
     const MeshDev M{mx, my, mtri, mesh.T};
     const int nb = nb_dye(n);
-    if (lat_sl)
-      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, cgrid, (int64_t)row0,
-              (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
-    else
-      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0,
-              (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
+    with_loc([&](const auto& L) {
+      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+              (int64_t)row0, (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
+    });
     KCHK();
   }
   // the channels' part of a step, on the stream of the step's sl_launch, with the step's final u
@@ -1183,7 +1195,7 @@ struct Ctx {
     state(scheme == PUCFEM_STOKES_COLOR || scheme == PUCFEM_STOKES_FOOD, "inertia needs a Stokes context");
     state(!dist() && world == 1, "inertia is single-rank (a multi-rank context would need a wide halo of u)");
     need_dev();
-    state(has_cgrid && (lat_sl ? llgrid.face != nullptr : lgrid.rec != nullptr), "the context has no point locator");
+    state(has_cgrid && has_locator(), "the context has no point locator");
   }
   // k_sl_vel over rows [row0, row0 + n) on the current stream: out = SL(f; u, dt), all three interleaved pairs
   void vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* out2, int32_t* nf,
@@ -1193,12 +1205,10 @@ struct Ctx {
     const dbl2* u = reinterpret_cast<const dbl2*>(u2);
     const dbl2* f = reinterpret_cast<const dbl2*>(f2);
     dbl2* out = reinterpret_cast<dbl2*>(out2);
-    if (lat_sl)
-      klaunch(-1, vel_launch_bytes(n), k_sl_vel<LatLocDev>, dim3(nb), dim3(BS), M, llgrid, cgrid, (int64_t)row0,
-              (int64_t)n, u, dt, f, out, nf, nfpart);
-    else
-      klaunch(-1, vel_launch_bytes(n), k_sl_vel<LocDev>, dim3(nb), dim3(BS), M, lgrid, cgrid, (int64_t)row0,
-              (int64_t)n, u, dt, f, out, nf, nfpart);
+    with_loc([&](const auto& L) {
+      klaunch(-1, vel_launch_bytes(n), k_sl_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+              (int64_t)row0, (int64_t)n, u, dt, f, out, nf, nfpart);
+    });
     KCHK();
   }
   // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity)
@@ -6011,7 +6021,7 @@ void sample_ready(Ctx& c) {
   state(c.scheme == PUCFEM_STOKES_COLOR || c.scheme == PUCFEM_STOKES_FOOD,
         "sampling needs a Stokes context (heat / Poisson contexts have no point locator)");
   state(!c.dist(), "sampling is single-rank (the fields of a multi-rank context are partitioned)");
-  state(c.lat_sl ? c.llgrid.face != nullptr : c.lgrid.rec != nullptr, "the context has no point locator");
+  state(c.has_locator(), "the context has no point locator");
 }
 void sample_push(SampleFields& F, const double* p, int32_t stride, int64_t member) {
   require(F.ncomp < SMP_MAXC, "too many field components in one call (16)");
@@ -6084,10 +6094,10 @@ RasterPlan raster_plan(int32_t W, int32_t H, const double* w4) {
   return p;
 }
 void launch_raster(Ctx& c, const RasterPlan& p, const SampleFields& F, float* dout) {
-  if (c.lat_sl)
-    hipLaunchKernelGGL(k_raster<LatLocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.llgrid, p.R, p.tiles_x, p.ntiles, F, dout);
-  else
-    hipLaunchKernelGGL(k_raster<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles, F, dout);
+  c.with_loc([&](const auto& L) {
+    hipLaunchKernelGGL(k_raster<std::decay_t<decltype(L)>>, dim3(p.grid), dim3(BS), 0, c.st, L, p.R, p.tiles_x, p.ntiles,
+                       F, dout);
+  });
   KCHK();
 }
 }  // namespace
@@ -6106,12 +6116,10 @@ int pucfem_sample_points(void* ctx, int32_t nfields, const int32_t* fields, int6
     int32_t* dtri = tri_out ? c.smp_scratch<int32_t>(2, np) : nullptr;
     c.h2d(dxy, xy, sizeof(double) * 2 * np);
     const int grid = (int)std::min<int64_t>(65536, (npoints + BS - 1) / BS);
-    if (c.lat_sl)
-      hipLaunchKernelGGL(k_sample_points<LatLocDev>, dim3(grid), dim3(BS), 0, c.st, c.llgrid, npoints,
+    c.with_loc([&](const auto& L) {
+      hipLaunchKernelGGL(k_sample_points<std::decay_t<decltype(L)>>, dim3(grid), dim3(BS), 0, c.st, L, npoints,
                          (const double*)dxy, F, dout, dtri);
-    else
-      hipLaunchKernelGGL(k_sample_points<LocDev>, dim3(grid), dim3(BS), 0, c.st, c.lgrid, npoints, (const double*)dxy,
-                         F, dout, dtri);
+    });
     KCHK();
     c.d2h(out, dout, sizeof(double) * (size_t)F.ncomp * np);
     if (tri_out) c.d2h(tri_out, dtri, sizeof(int32_t) * np);
@@ -6174,12 +6182,10 @@ int pucfem_raster_probe(void* ctx, int32_t nfields, const int32_t* fields, int32
     float* dout = c.smp_scratch<float>(1, count);
     unsigned long long* dcnt = c.smp_scratch<unsigned long long>(3, 2);
     HIPCHK(hipMemsetAsync(dcnt, 0, 2 * sizeof(unsigned long long), c.st));
-    if (c.lat_sl)
-      hipLaunchKernelGGL(k_raster_count<LatLocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.llgrid, p.R, p.tiles_x, p.ntiles,
-                         dcnt);
-    else
-      hipLaunchKernelGGL(k_raster_count<LocDev>, dim3(p.grid), dim3(BS), 0, c.st, c.lgrid, p.R, p.tiles_x, p.ntiles,
-                         dcnt);
+    c.with_loc([&](const auto& L) {
+      hipLaunchKernelGGL(k_raster_count<std::decay_t<decltype(L)>>, dim3(p.grid), dim3(BS), 0, c.st, L, p.R, p.tiles_x,
+                         p.ntiles, dcnt);
+    });
     KCHK();
     launch_raster(c, p, F, dout);  // (untimed: the first launch)
     out4[0] = time_launches(c, iters, [&] { launch_raster(c, p, F, dout); });
@@ -6222,12 +6228,10 @@ SlnArgs sln_args(const Ctx& c, int64_t nseeds, const double* seeds, double h, in
 void sln_launch(Ctx& c, const SlnArgs& A, const SampleFields& F, const double* dseeds, double* dpts, int32_t* dst,
                 double* dval) {
   const int grid = (int)((A.lines + A.lanes - 1) / A.lanes);
-  if (c.lat_sl)
-    hipLaunchKernelGGL(k_streamlines<LatLocDev>, dim3(grid), dim3(SLN_BS), 0, c.st, c.llgrid, A, dseeds,
+  c.with_loc([&](const auto& L) {
+    hipLaunchKernelGGL(k_streamlines<std::decay_t<decltype(L)>>, dim3(grid), dim3(SLN_BS), 0, c.st, L, A, dseeds,
                        (const double*)c.ux, (const double*)c.uy, F, dpts, dst, dst + A.lines, dval);
-  else
-    hipLaunchKernelGGL(k_streamlines<LocDev>, dim3(grid), dim3(SLN_BS), 0, c.st, c.lgrid, A, dseeds,
-                       (const double*)c.ux, (const double*)c.uy, F, dpts, dst, dst + A.lines, dval);
+  });
   KCHK();
 }
 }  // namespace
@@ -6672,15 +6676,9 @@ int pucfem_dyes_info(void* ctx, int64_t* out4) {
     Ctx& c = *C(ctx);
     c.dye_ready();
     require(out4 != nullptr, "null output");
-    int64_t nf = 0;
-    if (c.ndye && c.dye_nb > 0) {  // the blocks' counts of the last launch, in block order
-      std::vector<int32_t> part((size_t)c.dye_nb);
-      c.d2h(part.data(), c.dye_nfpart, sizeof(int32_t) * part.size());
-      for (int32_t v : part) nf += v;
-    }
     out4[0] = c.ndye;
     out4[1] = c.dye_steps;
-    out4[2] = nf;
+    out4[2] = c.nf_rows(c.dye_nfpart, c.dye_nb);
     out4[3] = (int64_t)c.dye_dev_bytes();
   });
 }
@@ -6747,15 +6745,9 @@ int pucfem_inertia_info(void* ctx, int64_t* out4) {
     Ctx& c = *C(ctx);
     c.inertia_ready();
     require(out4 != nullptr, "null output");
-    int64_t nf = 0;
-    if (c.adv_nfpart && c.adv_nb > 0) {  // the blocks' counts of the last launch, in block order
-      std::vector<int32_t> part((size_t)c.adv_nb);
-      c.d2h(part.data(), c.adv_nfpart, sizeof(int32_t) * part.size());
-      for (int32_t v : part) nf += v;
-    }
     out4[0] = c.inertia ? 1 : 0;
     out4[1] = c.adv_steps;
-    out4[2] = nf;
+    out4[2] = c.nf_rows(c.adv_nfpart, c.adv_nb);
     out4[3] = (int64_t)c.inertia_dev_bytes();
   });
 }

@@ -8,11 +8,9 @@
 // stripe good_visualization2.py:520-524, the blob good_visualization.py:555-559); the channels carry them through
 // one run instead of one run each.
 //
-// One pass, one lane per row, blocks over rows as k_sl's (block_rows).  The locate is the existing passes', call
-// for call: the zero-velocity rows from the build-time table (LatLocDev::self, as k_sl), then the lattice fast path
-// (sl_lat_cell + the accept tests of sl_lat_value), then the general locate k_sl_slow runs (sl_best -> sl_fast ||
-// sl_rank_ok).  The passes' own design claim -- the general locate returns the fast path's triangle -- is what
-// makes one pass legal.  Every channel's value is sl_value on that triangle, or the row's own value when none is
+// One pass, one lane per row, blocks over rows as k_sl's (block_rows).  The locate is sl_locate_row
+// (pucfem_locate.hpp): the steps k_sl and its second pass take, in one lane.  The passes' own design claim -- the
+// general locate returns the fast path's triangle -- is what makes one pass legal.  Every channel's value is sl_value on that triangle, or the row's own value when none is
 // accepted: the expressions of the single-dye kernels (the library is built with -ffp-contract=off), so channel k
 // holds the bits c would hold in a run started from channel k's values (tests/test_gpu_dye_channels.py).
 //
@@ -37,7 +35,6 @@ __global__ __launch_bounds__(BS) void k_sl_multi(MeshDev M, LOC L, GridDev G, in
                                                  double dt, int32_t nch, const double* __restrict__ cin, double* __restrict__ cout,
                                                  int64_t ld, int32_t* __restrict__ notfound,
                                                  int32_t* __restrict__ nfpart) {
-  constexpr bool LAT = std::is_same<LOC, LatLocDev>::value;
   __shared__ double sh[4];
   double nnf = 0.0;
   int64_t r0, r1;
@@ -48,41 +45,8 @@ __global__ __launch_bounds__(BS) void k_sl_multi(MeshDev M, LOC L, GridDev G, in
     double xb, yb;
     sl_point(M, g, vx, vy, dt, xb, yb);
     SlTri r{};
-    bool ok = false, located = false;
-    int32_t mark = 1;
-    if constexpr (LAT) {
-      if (vx == 0.0 && vy == 0.0 && L.self) {
-        // q is the row's own node (no-slip walls): the answer settled once at build (k_sl_self), as k_sl reads it
-        const int32_t t = L.self[g];
-        if (t >= 0) {
-          const int32_t va = M.tri[3 * (int64_t)t], vb = M.tri[3 * (int64_t)t + 1], vc = M.tri[3 * (int64_t)t + 2];
-          r = SlTri{M.x[va], M.y[va], M.x[vb], M.y[vb], M.x[vc], M.y[vc], va, vb, vc, t};
-          ok = true;
-        }
-        located = true;
-        mark = ok ? 0 : 1;
-      } else {
-        // the lattice fast path's two stages; the rows k_sl finishes cheaply do not pay the general search
-        int32_t v0, v1, v2, id;
-        if (sl_lat_cell(L, L.home[g], xb, yb, v0, v1, v2, id)) {
-          const double2 P1 = L.xy[v0], P2 = L.xy[v1], P3 = L.xy[v2];
-          const float rho2 = L.rho2[id], rv1 = L.rv2[v0], rv2 = L.rv2[v1], rv3 = L.rv2[v2];
-          double unused;  // (the stage's own value of a zero field: the channels' values follow below)
-          if (sl_lat_value(L.probe, xb, yb, P1, P2, P3, 0.0, 0.0, 0.0, rho2, rv1, rv2, rv3, unused)) {
-            r = SlTri{P1.x, P1.y, P2.x, P2.y, P3.x, P3.y, v0, v1, v2, id};
-            ok = located = true;
-            mark = 0;
-          }
-        }
-      }
-    }
-    if (!located) {  // k_sl_slow's sequence
-      double bestd;
-      float rho2;
-      const bool cand = sl_best(L, -1, xb, yb, r, bestd, rho2);
-      ok = cand && (sl_fast(L, r, xb, yb, bestd, rho2) || sl_rank_ok(G, xb, yb, bestd, r.id, 0.0f, 0));
-      mark = ok ? ((L.probe & 2) ? 2 : 0) : 1;
-    }
+    int32_t mark;
+    const bool ok = sl_locate_row(M, L, G, g, vx, vy, xb, yb, r, mark);
     if (!ok) nnf += 1.0;
     if (notfound) notfound[i] = mark;
     for (int32_t k = 0; k < nch; ++k) {

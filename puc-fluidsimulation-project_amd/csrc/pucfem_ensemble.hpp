@@ -328,7 +328,7 @@ __global__ __launch_bounds__(BS) void k_ens_grad_proj1(SellDev A, const double* 
   }
 }
 
-// k_sl_rec_wave per member (row0 = 0: one rank): one wave per row, the single path's locator functions.
+// k_sl_rec_wave per member (row0 = 0: one rank): one wave per row, the single path's sl_row_wave (pucfem_locate.hpp).
 // u: M x 2n, c / cout: M x n, part: M x 3 gridDim.x.
 __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, int64_t n, const double* __restrict__ u,
                                                double dt, const double* __restrict__ c, double* __restrict__ cout,
@@ -345,20 +345,8 @@ __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, 
   const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
   double swc = 0.0, sw = 0.0, nnf = 0.0;
   if (i < n) {
-    double xb, yb;
-    sl_point(Mh, i, ux[VS * i], uy[VS * i], dt, xb, yb);
-    SlTri r;
-    double bestd;
-    float rho2;
-    const bool cand = sl_best_wave(L, xb, yb, r, bestd, rho2);
-    const bool ok = cand && (sl_fast(L, r, xb, yb, bestd, rho2) || sl_rank_ok_wave(G, xb, yb, bestd, r.id));
     double cn;
-    if (ok) {
-      cn = sl_value(r, xb, yb, cm);
-    } else {
-      cn = cm[i];
-      nnf = 1.0;
-    }
+    if (!sl_row_wave(Mh, L, G, i, ux[VS * i], uy[VS * i], dt, cm, cn)) nnf = 1.0;
     if (lane == 0) com[i] = cn;
     const double w = wmix[i];
     sw = w;
@@ -382,12 +370,10 @@ __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, 
 }
 
 // The inertial launch per member (pucfem_ens_set_inertia): ua = SL(u; u, dt) of the member's own interleaved
-// velocity, in front of k_ens_mv2_bc.  k_ens_sl's back-trace and locate, call for call, on k_ens_sl's grid in x (one
-// wave per row), then k_sl_vel's interpolation (pucfem_inertia.hpp): sl_value's weights with pdx, computed once,
-// component k = w1 * f[a].k + w2 * f[b].k + w3 * f[d].k in that operand order, so a member's ua holds the bits of the
-// single path's u_adv.  Three 16-byte gathers from the member's u, one 16-byte store into its plane of ua; a row that
-// is not found keeps its own pair.  The sequence is restated, not shared with k_ens_sl or k_sl_vel, so those compile
-// to what they did.  A member whose flag is off leaves at once (a block-uniform exit in front of every barrier: its
+// velocity, in front of k_ens_mv2_bc.  k_ens_sl's sl_row_wave on k_ens_sl's grid in x (one wave per row), with
+// k_sl_vel's field (pucfem_inertia.hpp): sl_value's pair form, so a member's ua holds the bits of the single path's
+// u_adv.  Three 16-byte gathers from the member's u, one 16-byte store into its plane of ua; a row that is not found
+// keeps its own pair.  A member whose flag is off leaves at once (a block-uniform exit in front of every barrier: its
 // ticket is not drawn).  The not-found rows of each member: per-block partials, summed by red_finish in block order.
 // u, ua: M x 2n (ua must not alias u: rows of other blocks still gather from u); on: M; part: M x gridDim.x.
 __global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev G, int64_t n,
@@ -406,28 +392,8 @@ __global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev
   double nnf = 0.0;
   if (i < n) {
     const dbl2 v = f[i];
-    double xb, yb;
-    sl_point(Mh, i, v.x, v.y, dt, xb, yb);
-    SlTri r;
-    double bestd;
-    float rho2;
-    const bool cand = sl_best_wave(L, xb, yb, r, bestd, rho2);
-    const bool ok = cand && (sl_fast(L, r, xb, yb, bestd, rho2) || sl_rank_ok_wave(G, xb, yb, bestd, r.id));
     dbl2 o;
-    if (ok) {
-      const dbl2 fa = f[r.a], fb = f[r.b], fd = f[r.d];
-      // sl_value's weights (StokesColor.py:374-386), once for both components
-      const double x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2, x3 = r.x3, y3 = r.y3;
-      const double det = pdx(x2, x1) * (y3 - y1) - pdx(x3, x1) * (y2 - y1);
-      const double w1 = (pdx(x2, xb) * (y3 - yb) - pdx(x3, xb) * (y2 - yb)) / det;
-      const double w2 = (pdx(x3, xb) * (y1 - yb) - pdx(x1, xb) * (y3 - yb)) / det;
-      const double w3 = 1.0 - w1 - w2;
-      o.x = w1 * fa.x + w2 * fb.x + w3 * fd.x;
-      o.y = w1 * fa.y + w2 * fb.y + w3 * fd.y;
-    } else {
-      o = v;
-      nnf = 1.0;
-    }
+    if (!sl_row_wave(Mh, L, G, i, v.x, v.y, dt, f, o)) nnf = 1.0;
     if (lane == 0) out[i] = o;
   }
   if (lane == 0) sw_[wv] = nnf;

@@ -35,6 +35,8 @@ constexpr int SLB = PUCFEM_SLB;
 // Velocity storage: u and u* are interleaved (x, y) pairs (one 16-B gather per neighbour in k_div, the tracers and
 // the dye weights); kernels take the component pointers ux = u2, uy = u2 + 1 and index them at VS * i
 constexpr int VS = 2;
+typedef double dbl2 __attribute__((ext_vector_type(2)));
+typedef float flt2 __attribute__((ext_vector_type(2)));
 #ifndef PUCFEM_FACE_RPT
 #define PUCFEM_FACE_RPT 4
 #endif

@@ -16,7 +16,7 @@
 // their own outputs.
 #pragma once
 #include "pucfem_kernels.hpp"
-#include "pucfem_kernels_impl.hpp"
+#include "pucfem_locate.hpp"
 
 namespace pucfem {
 namespace dev {
@@ -136,10 +136,7 @@ __global__ __launch_bounds__(BS) void k_ens_raster(LOC L, RasterWin R, int32_t t
 // has no such case: cnt[1] stays 0.
 __device__ __forceinline__ bool sample_first_face(const LocDev&, double, double) { return false; }
 __device__ __forceinline__ bool sample_first_face(const LatLocDev& L, double qx, double qy) {
-  const double gx = floor((qx - L.x0) * L.ihx), gy = floor((qy - L.y0) * L.ihy);
-  const int32_t ci = !(gx >= 0.0) ? 0 : (gx >= (double)L.nx ? L.nx - 1 : (int32_t)gx);
-  const int32_t cj = !(gy >= 0.0) ? 0 : (gy >= (double)L.ny ? L.ny - 1 : (int32_t)gy);
-  const int64_t gc = (int64_t)cj * L.nx + ci;
+  const int64_t gc = lat_gcell(L, qx, qy);
   const int32_t e = L.start[gc];
   if (e >= L.start[gc + 1]) return false;
   SlTri r;

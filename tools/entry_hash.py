@@ -142,6 +142,32 @@ def mg_pieces(tag, mesh, rng):
         sim.close()
 
 
+def inertia(tag, mesh, rng):
+    """k_sl_vel: the unit entry point, then two inertial steps beside three dye channels (k_sl_multi)"""
+    sim = S.StokesSimulation(mesh, S.SquirmerBC(), 0.05, "color", 0, None if tag == "mesh1" else S.Tolerances.production(),
+                             inertia=True)
+    ctx, N = sim.ctx, mesh.N
+    f = np.ascontiguousarray(rng.standard_normal((N, 2)))
+    u = np.ascontiguousarray(0.3 * rng.standard_normal((N, 2)))
+    out, nf = np.zeros((N, 2)), np.zeros(N, dtype=np.int32)
+    L.check(ctx.L.pucfem_sl_advect_vel(ctx.h, L.dptr(f), L.dptr(u), 0.05, L.dptr(out), L.iptr(nf)), ctx.h)
+    line(tag, "sl_advect_vel", out, nf)
+    sim.dyes = rng.random((3, N))
+    sim.step(2)
+    line(tag, "inertial steps, 3 dyes", sim.u, sim.c, sim.dyes, sim.u_advected)
+    sim.close()
+
+
+def ens_inertia(tag, mesh, rng):
+    """k_ens_sl_vel beside k_ens_sl: members 0 and 2 inertial, member 1 not"""
+    bcs = [S.SquirmerBC(B1=-2.0, B2=b2, nu=1.0) for b2 in (0.0, -5.0, 5.0)]
+    ens = S.StokesEnsemble(mesh, bcs, 0.01, "color", inertia=[True, False, True])
+    ens.set(L.F_C, rng.random((3, mesh.N)))
+    ens.step(2)
+    line(tag, "ens inertia mixed, 2 steps", ens.u, ens.c, ens.get(L.F_U_ADV, 2, 0), ens.get(L.F_U_ADV, 2, 2))
+    ens.close()
+
+
 def main():
     print("# library variant:", os.environ.get("PUCFEM_LIB_VARIANT", "default"), file=sys.stderr)
     for tag, mesh in (("mesh1", pf.load_mesh("mesh1")), ("fine1", pf.load_mesh("fine", refine=1))):
@@ -150,7 +176,10 @@ def main():
         sim = S.StokesSimulation(mesh, S.SquirmerBC(), 0.05, "color", 0, None if small else S.Tolerances.production())
         sections = [lambda: fields(tag, sim, rng), lambda: unit_ops(tag, sim, rng), lambda: food(tag, mesh, rng),
                     lambda: heat(tag, mesh, rng), lambda: dye_step(tag, mesh, rng),
-                    lambda: (ensemble if small else mg_pieces)(tag, mesh, rng)]
+                    lambda: (ensemble if small else mg_pieces)(tag, mesh, rng),
+                    lambda: inertia(tag, mesh, rng),
+                    # (ensembles take the dense small-mesh path: beside fine1, mesh_fine unrefined)
+                    lambda: ens_inertia(tag, mesh, rng) if small else ens_inertia("fine", pf.load_mesh("fine"), rng)]
         for k, section in enumerate(sections):  # (a refusal ends its section and is recorded by its message)
             try:
                 section()
