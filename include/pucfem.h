@@ -357,6 +357,42 @@ int pucfem_ens_set_inertia(void* ctx, int32_t member /* -1 = all */, int32_t on)
    last inertial launch (summed on the device; 0 before the first), [3] device bytes the ensemble holds for inertia */
 int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4);
 
+/* ---- MacCormack advection: second-order transport of the dye and of the velocity ---- */
+/* advect_semilagrange (StokesColor.py:347-389) is first order and its linear interpolation a diffusion of order
+   h^2 / dt that no parameter controls.  With the MacCormack scheme of Selle et al. (J. Sci. Comput. 35, 2008) a field
+   c moves by two such advections with the one velocity u and a clamp; per node g, every product and sum as written:
+     pass 1   ch[g] = SL(c; u, +dt)[g], T1 = the triangle its point location returned (none: ch[g] = c[g])
+     pass 2   cb    = SL(ch; u, -dt)[g], T2 its triangle
+              T1 none:  out[g] = c[g]      (mark bit 0)
+              T2 none:  out[g] = ch[g]     (mark bit 1; bit 1 is set whenever T2 is none, bit 0 decides the value)
+              else      e = ch[g] + 0.5 * (c[g] - cb), clamped into [min, max] of c at T1's three vertices
+   so ch and cb hold the bits of pucfem_sl_advect(c, u, dt) and pucfem_sl_advect(ch, u, -dt).  The limited result
+   stays inside the range of c; the scheme is not conservative (the discrete u is not divergence-free).
+   what is a mask: PUCFEM_ADV_DYE moves c and the dye channels of every pucfem_step this way, from one point location
+   per pass and node for all of them (single-rank PUCFEM_STOKES_COLOR with dye_scheme = 0, as the dye channels);
+   PUCFEM_ADV_VELOCITY the inertial step's u_a = MC(u^n; u^n, dt) (readiness as pucfem_set_inertia; it may be set
+   while inertia is off and takes effect when inertia is on).  Else PUCFEM_ESTATE (multi-rank, heat, Poisson, the
+   implicit dye, PUCFEM_ADV_DYE on STOKES_FOOD; before the build; while the context has an ensemble, and
+   pucfem_ens_create while a scheme is set); PUCFEM_ENODEV on a host-only context; PUCFEM_EINVAL for an unknown mask
+   or scheme.  With PUCFEM_ADV_SL (the default) a context steps as if this call did not exist.  The buffers -- per
+   set the intermediate fields, 16 bytes per node for T1 and the blocks' counts -- are allocated when a scheme is
+   first switched on, follow the number of dye channels, and are freed by pucfem_build_operators and
+   pucfem_ctx_destroy, which also set both schemes back to PUCFEM_ADV_SL.  Switching the velocity's scheme resets the
+   viscous solve's extrapolation history.  A small-mesh context steps from its captured graph only while the dye's
+   scheme is PUCFEM_ADV_SL (and inertia is off).  The step record's sl_notfound is pass 1's count. */
+enum { PUCFEM_ADV_DYE = 1, PUCFEM_ADV_VELOCITY = 2 };
+enum { PUCFEM_ADV_SL = 0, PUCFEM_ADV_MACCORMACK = 1 };
+int pucfem_set_advection(void* ctx, int32_t what /* bit mask */, int32_t scheme);
+/* out[0] the dye's scheme, [1] the velocity's, [2] MacCormack dye steps since the scheme was switched on, [3] velocity
+   steps, [4..6] of the last dye launch: rows whose back-trace found no triangle, rows whose forward trace found none,
+   clamped values (every field counts), [7..9] the same of the last velocity launch (both components count),
+   [10] device bytes held for both */
+int pucfem_advection_info(void* ctx, int64_t* out11);
+/* Measurement: the two passes on the context's current u and dt with scratch buffers -- what = PUCFEM_ADV_DYE: nch
+   zero fields; PUCFEM_ADV_VELOCITY: f = u (nch ignored) -- each launched once untimed and then `iters` times back to
+   back between two events.  out4: milliseconds per launch of pass 1, of pass 2, algorithmic bytes of each. */
+int pucfem_advection_probe(void* ctx, int32_t what, int32_t nch, int32_t iters, double* out4);
+
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,
    good_visualization.py:738).  These calls integrate the context's current u from caller-given seeds with the
@@ -443,6 +479,15 @@ int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* c /* nch x N */
    f may be u.  The step's state is not touched.  Readiness as for inertia (above). */
 int pucfem_sl_advect_vel(void* ctx, const double* f /* N x 2 */, const double* u /* N x 2 */, double dt,
                          double* f_out /* N x 2 */, int32_t* notfound /* N or NULL */);
+/* One MacCormack step (pucfem_set_advection above) of nch fields with a given u, on scratch buffers: the step's state
+   is not touched.  marks (N or NULL): bit 0 / bit 1 as above; tri (N or NULL): T1's id in the mesh's triangle order,
+   -1 when none.  Readiness and nch as pucfem_sl_advect_multi. */
+int pucfem_sl_advect_mc(void* ctx, int32_t nch, const double* c /* nch x N */, const double* u, double dt,
+                        double* c_out /* nch x N */, int32_t* marks /* N or NULL */, int32_t* tri /* N or NULL */);
+/* ... of an interleaved field f (N,2), the two components limited separately: component k of f_out holds the bits
+   pucfem_sl_advect_mc returns for the vector f[:, k].  f may be u.  Readiness as pucfem_sl_advect_vel. */
+int pucfem_sl_advect_vel_mc(void* ctx, const double* f /* N x 2 */, const double* u /* N x 2 */, double dt,
+                            double* f_out /* N x 2 */, int32_t* marks /* N or NULL */, int32_t* tri /* N or NULL */);
 /* tracer step (StokesFood.py:482-499) on the tracers held in the context, with u given */
 int pucfem_tracer_step(void* ctx, const double* u, double dt, int32_t nsteps);
 /* the context's tracer set (member = -1) or that of member `member` of its ensemble: out[0] tracers, [1] tracers

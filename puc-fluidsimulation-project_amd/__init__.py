@@ -11,7 +11,7 @@ The directory name contains hyphens, so import it with
 from ._lib import PucfemError, device_count, lib as _load_library  # noqa: F401
 from .mesh import (Mesh, boundary_sets, filter_wall_pairs, find_boundary_pairs, load_mesh, readEle,  # noqa: F401
                    readNode, readPoly, writeEle, writeNode, writePoly)
-from .ops import (advect_semilagrange, advect_semilagrange_multi, advect_semilagrange_vector, buildLumpedMassMatrix,  # noqa: F401
+from .ops import (advect_maccormack, advect_maccormack_vector, advect_semilagrange, advect_semilagrange_multi, advect_semilagrange_vector, buildLumpedMassMatrix,  # noqa: F401
                   buildStiffnessMatrix, calculate_divergence, build_mass_and_convection_mass, calculate_gradiant,
                   calculate_vorticity, dye_implicit_step,
                   makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous)

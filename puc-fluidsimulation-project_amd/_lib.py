@@ -23,6 +23,9 @@ F_DYES = 13  # all dye channels (K, N); channel k is field F_DYE0 + k
 F_DYE0 = 64
 F_U_ADV = 14  # u_a (N, 2) of the last inertial step, read only
 MAX_DYES = 16
+ADV_DYE, ADV_VELOCITY = 1, 2  # pucfem_set_advection: what (a mask)
+ADV_SL, ADV_MACCORMACK = 0, 1  # ... and the scheme
+MC_NO_BACK, MC_NO_FWD = 1, 2  # marks of pucfem_sl_advect_mc
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 OP_CURL = 11
 SLN_UNIT, SLN_EULER, SLN_BOTH = 1, 2, 4  # pucfem_streamline_flag
@@ -114,6 +117,11 @@ SIGNATURES = {
     "pucfem_inertia_probe": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_ens_set_inertia": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_ens_inertia_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_set_advection": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
+    "pucfem_advection_info": ([_P, _I64], ct.c_int),
+    "pucfem_sl_advect_mc": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
+    "pucfem_sl_advect_vel_mc": ([_P, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
+    "pucfem_advection_probe": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, _D], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_dye_step": ([_P, _D, _D, _D, _I32], ct.c_int),
     "pucfem_comm_info": ([_P, ct.POINTER(ct.c_int64)], ct.c_int),

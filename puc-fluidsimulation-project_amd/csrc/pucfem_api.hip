@@ -31,6 +31,7 @@
 #include "pucfem_streamline.hpp"
 #include "pucfem_dye_channels.hpp"
 #include "pucfem_inertia.hpp"
+#include "pucfem_maccormack.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -592,7 +593,9 @@ struct Ctx {
   // status and npts (one buffer), the values along the lines
   // Slots 14..16: pucfem_sl_advect_multi / pucfem_dyes_probe (pucfem_dye_channels.hpp) and pucfem_sl_advect_vel /
   // pucfem_inertia_probe (pucfem_inertia.hpp): the fields in, the fields out, the blocks' not-found counts
-  static constexpr int SMP_SLOTS = 17;
+  // Slots 17..21: pucfem_sl_advect_mc / pucfem_sl_advect_vel_mc / pucfem_advection_probe (pucfem_maccormack.hpp): the
+  // intermediate fields, the records, the marks, the triangle ids, pass 2's counts
+  static constexpr int SMP_SLOTS = 22;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -809,6 +812,7 @@ struct Ctx {
       for (void* a : allocs) (void)hipFree(a);
       drop_dyes();
       drop_inertia();
+      drop_advection();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1164,6 +1168,7 @@ struct Ctx {
     }
     dye_steps = 0;
     dye_nb = 0;
+    if (mc_ch) mc_dye_fit();  // (the MacCormack set holds one field per channel)
     put_all(1, K, buf, dye_cur);
     HIPCHK(hipStreamSynchronize(st));
   }
@@ -1214,7 +1219,13 @@ struct Ctx {
   // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity)
   void inertia_step() {
     if (!inertia) return;
-    vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, adv_nfpart);
+    if (adv_vel) {
+      mc_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, mcv_ch, u_adv, mcv_rec, nullptr, nullptr, adv_nfpart, mcv_cnt);
+      mcv_nb = nb_dye(lp.n_own);
+      ++mcv_steps;
+    } else {
+      vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, adv_nfpart);
+    }
     adv_nb = nb_dye(lp.n_own);
     ++adv_steps;
     adv_valid = true;
@@ -1252,6 +1263,191 @@ struct Ctx {
   }
   size_t inertia_dev_bytes() const {
     return u_adv ? sizeof(double) * 2 * (size_t)mesh.N + sizeof(int32_t) * SLB : 0;
+  }
+
+  // ------------------------------------------------------------------ MacCormack advection (pucfem_maccormack.hpp)
+  // pucfem_set_advection: the dye (c and its channels) and, with inertia on, the velocity move by the two-pass
+  // limited MacCormack step instead of the first-order one.  Per transported set: the intermediate fields ch, one
+  // 16-byte record per row (pass 1's triangle) and the blocks' counts.  The dye's and the velocity's sets are
+  // separate: a step's dye tail runs on the side stream beside the next step's inertial launch.  Allocated when a
+  // scheme is first switched on and freed by drop_advection (they are not in `allocs`): a context that never enables
+  // it holds no new memory and launches nothing new.
+  int adv_dye = 0, adv_vel = 0;  // PUCFEM_ADV_SL / PUCFEM_ADV_MACCORMACK
+  double* mc_ch = nullptr;       // (1 + K) x N: c's ch, then the channels'
+  int mc_fields = 0;             // the fields mc_ch holds
+  int4* mc_rec = nullptr;        // N
+  int32_t* mc_nfpart = nullptr;  // pass 1's not-found counts when there are no channels (else dye_nfpart) (SLB)
+  double* mc_nfd = nullptr;      // the same as doubles, for the step record's reduction (SLB)
+  int32_t* mc_cnt = nullptr;     // pass 2's three counts per block (3 x SLB)
+  int mc_nb = 0;                 // blocks of the last dye launch (0: none since the scheme was set)
+  i64 mc_steps = 0;
+  double* mcv_ch = nullptr;      // N x 2 interleaved
+  int4* mcv_rec = nullptr;
+  int32_t* mcv_cnt = nullptr;
+  int mcv_nb = 0;
+  i64 mcv_steps = 0;
+  // pass 1 as dye_launch_bytes / vel_launch_bytes count a first-order launch, plus the record written 16; pass 2: the
+  // coordinates, u and the locator's share again, the record read 16, per field c and ch read and the result written
+  double mc_bytes1(int nf, i64 n) const { return dye_launch_bytes(nf, n) + 16.0 * (double)n; }
+  double mc_bytes2(int nf, i64 n) const { return ((lat_sl ? 52.0 : 32.0) + 16.0 + 24.0 * nf) * (double)n; }
+  double mcv_bytes1(i64 n) const { return vel_launch_bytes(n) + 16.0 * (double)n; }
+  // (the pair form counts f as vel_launch_bytes does: the gathered vertices' lines are the rows' own, f = u)
+  double mcv_bytes2(i64 n) const { return ((lat_sl ? 52.0 : 32.0) + 16.0 + 32.0) * (double)n; }
+  void mc_fwd(i64 row0, i64 n, const double* vx, const double* vy, double dt, const double* c0, double* ch0, int nch,
+              const double* cin, double* chout, int4* rec, int32_t* nfpart, double* nfd) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    with_loc([&](const auto& L) {
+      klaunch(-1, mc_bytes1(nch + (c0 ? 1 : 0), n), k_mc_fwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+              (int64_t)row0, (int64_t)n, vx, vy, dt, c0, ch0, (int32_t)nch, cin, chout, (int64_t)mesh.N, rec, nfpart,
+              nfd);
+    });
+    KCHK();
+  }
+  void mc_bwd(i64 row0, i64 n, const double* vx, const double* vy, double dt, const double* c0, const double* ch0,
+              double* out0, int nch, const double* cin, const double* ch, double* cout, const int4* rec,
+              int32_t* marks, int32_t* tri, int32_t* cnt) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    with_loc([&](const auto& L) {
+      klaunch(-1, mc_bytes2(nch + (c0 ? 1 : 0), n), k_mc_bwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+              (int64_t)row0, (int64_t)n, vx, vy, dt, c0, ch0, out0, (int32_t)nch, cin, ch, cout, (int64_t)mesh.N, rec,
+              marks, tri, cnt);
+    });
+    KCHK();
+  }
+  // both passes of the pair form on the current stream: out = MC(f; u, dt); ch, out and f are three buffers
+  void mc_vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* ch2, double* out2,
+                     int4* rec, int32_t* marks, int32_t* tri, int32_t* nfpart, int32_t* cnt, int pass = 3) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
+    const dbl2* f = reinterpret_cast<const dbl2*>(f2);
+    dbl2* ch = reinterpret_cast<dbl2*>(ch2);
+    dbl2* out = reinterpret_cast<dbl2*>(out2);
+    with_loc([&](const auto& L) {
+      if (pass & 1)
+        klaunch(-1, mcv_bytes1(n), k_mc_fwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+                (int64_t)row0, (int64_t)n, u, dt, f, ch, rec, nfpart);
+      if (pass & 2)
+        klaunch(-1, mcv_bytes2(n), k_mc_bwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+                (int64_t)row0, (int64_t)n, u, dt, f, (const dbl2*)ch, out, (const int4*)rec, marks, tri, cnt);
+    });
+    KCHK();
+  }
+  // the dye's part of a step, where sl_launch + dyes_step stand, on their stream, with the step's final u:
+  // c_full -> cnew, the channels dye_cur -> dye_nxt (swapped here, as dyes_step does), and the mixing sums of cnew
+  // into part_sl as the implicit dye forms them
+  void mc_dye_step(double* cnew) {
+    const i64 n = lp.n_own, N = mesh.N;
+    mc_fwd(lp.r0, n, ux, uy, prm.dt, c_full, mc_ch, ndye, dye_cur, mc_ch + N, mc_rec, ndye ? dye_nfpart : mc_nfpart,
+           mc_nfd);
+    mc_bwd(lp.r0, n, ux, uy, prm.dt, c_full, mc_ch, cnew, ndye, dye_cur, mc_ch + N, dye_nxt, mc_rec, nullptr, nullptr,
+           mc_cnt);
+    mc_nb = nb_dye(n);
+    ++mc_steps;
+    if (ndye) {
+      std::swap(dye_cur, dye_nxt);
+      dye_nb = mc_nb;
+      ++dye_steps;
+    }
+    hipLaunchKernelGGL(k_wsum, dim3(mc_nb), dim3(BS), 0, st, lp.r0, n, (const double*)cnew, (const double*)dwmix,
+                       part_sl);
+    KCHK();
+  }
+  // ... and its sums: sum wc, sum w (k_wsum's blocks), then the step record's not-found entry, pass 1's
+  void mc_dye_reduce() {
+    reduce_into(part_sl, mc_nb, 2, false, 2, SLB);
+    reduce_into(mc_nfd, mc_nb, 1, false, 4, SLB);
+  }
+  // the three counts of a pass-2 launch, its nb blocks summed in block order
+  void mc_counts(const int32_t* cnt, int nb, int64_t* out3) {
+    out3[0] = out3[1] = out3[2] = 0;
+    if (!cnt || nb <= 0) return;
+    std::vector<int32_t> part(3 * (size_t)nb);
+    d2h(part.data(), cnt, sizeof(int32_t) * part.size());
+    for (int b = 0; b < nb; ++b)
+      for (int j = 0; j < 3; ++j) out3[j] += part[3 * (size_t)b + j];
+  }
+  // mc_ch sized for c and the current channels
+  void mc_dye_fit() {
+    if (mc_ch && mc_fields == 1 + ndye) return;
+    if (st) (void)hipStreamSynchronize(st);
+    if (st_sl) (void)hipStreamSynchronize(st_sl);
+    if (mc_ch) (void)hipFree(mc_ch);
+    mc_ch = nullptr;
+    mc_fields = 1 + ndye;
+    const size_t bytes = sizeof(double) * (size_t)mc_fields * (size_t)mesh.N;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&mc_ch), bytes));
+    HIPCHK(hipMemsetAsync(mc_ch, 0, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  void drop_advection() {
+    adv_dye = adv_vel = 0;
+    mc_nb = mcv_nb = 0;
+    mc_steps = mcv_steps = 0;
+    mc_fields = 0;
+    if (!mc_rec && !mcv_rec) return;
+    if (st) (void)hipStreamSynchronize(st);
+    if (st_sl) (void)hipStreamSynchronize(st_sl);
+    for (void* q : {(void*)mc_ch, (void*)mc_rec, (void*)mc_nfpart, (void*)mc_nfd, (void*)mc_cnt, (void*)mcv_ch,
+                    (void*)mcv_rec, (void*)mcv_cnt})
+      if (q) (void)hipFree(q);
+    mc_ch = mc_nfd = mcv_ch = nullptr;
+    mc_rec = mcv_rec = nullptr;
+    mc_nfpart = mc_cnt = mcv_cnt = nullptr;
+  }
+  template <class T>
+  void mc_alloc(T*& p, size_t count) {
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count));
+    HIPCHK(hipMemsetAsync(p, 0, sizeof(T) * count, st));
+  }
+  void set_advection(int what, int sch) {
+    if (what & ~(PUCFEM_ADV_DYE | PUCFEM_ADV_VELOCITY) || what == 0)
+      throw Error(PUCFEM_EINVAL, "what is a mask of PUCFEM_ADV_DYE and PUCFEM_ADV_VELOCITY");
+    if (sch != PUCFEM_ADV_SL && sch != PUCFEM_ADV_MACCORMACK) throw Error(PUCFEM_EINVAL, "unknown advection scheme");
+    if (what & PUCFEM_ADV_DYE) dye_ready();
+    if (what & PUCFEM_ADV_VELOCITY) inertia_ready();
+    if (sch && ens) throw Error(PUCFEM_ESTATE, "MacCormack advection cannot be switched on while the context has an ensemble");
+    const size_t N = (size_t)mesh.N;
+    if ((what & PUCFEM_ADV_DYE) && sch != adv_dye) {
+      if (st_sl) HIPCHK(hipStreamSynchronize(st_sl));
+      if (sch) {
+        mc_dye_fit();
+        if (!mc_rec) {
+          mc_alloc(mc_rec, N);
+          mc_alloc(mc_nfpart, (size_t)SLB);
+          mc_alloc(mc_nfd, (size_t)SLB);
+          mc_alloc(mc_cnt, 3 * (size_t)SLB);
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        mc_steps = 0;
+        mc_nb = 0;
+      }
+      adv_dye = sch;
+    }
+    if ((what & PUCFEM_ADV_VELOCITY) && sch != adv_vel) {
+      if (sch) {
+        if (!mcv_rec) {
+          mc_alloc(mcv_ch, 2 * N);
+          mc_alloc(mcv_rec, N);
+          mc_alloc(mcv_cnt, 3 * (size_t)SLB);
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        mcv_steps = 0;
+        mcv_nb = 0;
+      }
+      adv_vel = sch;
+      have_vinc = 0;  // (as switching inertia: the advected right-hand side changes)
+    }
+  }
+  size_t advection_dev_bytes() const {
+    const size_t N = (size_t)mesh.N;
+    size_t b = 0;
+    if (mc_ch) b += sizeof(double) * (size_t)mc_fields * N;
+    if (mc_rec) b += sizeof(int4) * N + sizeof(int32_t) * 4 * SLB + sizeof(double) * SLB;
+    if (mcv_rec) b += sizeof(double) * 2 * N + sizeof(int4) * N + sizeof(int32_t) * 3 * SLB;
+    return b;
   }
 
 
@@ -3060,11 +3256,16 @@ struct Ctx {
   void dye_tail_sl(double* rec) {
     const int nb = nb_sl(lp.n_own);
     const RedOut rs = ro(vals + 2, CNT_DYE_SL, 3, SLB);
-    sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
-    KCHK();
-    dyes_step();  // (before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
+    if (adv_dye) {
+      mc_dye_step(c_new);  // (c and the channels; before ev_sl is recorded, as below)
+    } else {
+      sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
+      KCHK();
+      dyes_step();  // (before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
+    }
     std::swap(c_full, c_new);
-    if (!rs.out) reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
+    if (adv_dye) mc_dye_reduce();
+    else if (!rs.out) reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
     const int nbm = nb_rows(lp.n_own);
     algo_bytes += 16.0 * (double)lp.n_own;  // c, w
     const RedOut rm = ro(vals + 5, CNT_DYE_MIX, 1);
@@ -3173,6 +3374,8 @@ struct Ctx {
         its[1] = itp;
         its[2] = itp2;
         return;
+      } else if (adv_dye) {
+        mc_dye_step(c_new);
       } else {
         sl_ro = ro(vals + 2, CNT_SL, 3, SLB);
         sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, sl_ro);
@@ -3187,7 +3390,8 @@ struct Ctx {
       } else if (!mix_copy) {
         std::swap(c_full, c_new);
       }
-      if (sl_ro.out) red_done(vals + 2, 3, false);
+      if (adv_dye && !dye_impl) mc_dye_reduce();
+      else if (sl_ro.out) red_done(vals + 2, 3, false);
       else reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
       sl_ro = RedOut{};
       const int nbm = nb_rows(lp.n_own);
@@ -5260,6 +5464,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     c.drop_step_graphs();
     if (!c.host_only) c.drop_dyes();
     if (!c.host_only) c.drop_inertia();
+    if (!c.host_only) c.drop_advection();
     build(c);
   });
 }
@@ -5424,8 +5629,9 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       int* dits = c.dalloc<int>(3 * (i64)nsteps);
       std::vector<int32_t> its(3 * (size_t)nsteps);
       // (a context with dye channels steps uncaptured: the channels' buffers swap every step; so does one with
-      // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step)
-      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia) {
+      // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step; so does one
+      // whose dye moves by MacCormack steps)
+      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -5736,6 +5942,8 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     state(!c.dist(), "ensembles run on a single-rank context");
     state(!c.dye_impl, "ensembles step the semi-Lagrangian dye, not the implicit variant");
     state(!c.inertia, "ensembles step without inertia: switch it off first (pucfem_set_inertia)");
+    state(!c.adv_dye && !c.adv_vel,
+          "ensembles step the first-order advection: switch MacCormack off first (pucfem_set_advection)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
               c.sl_rec_wave(c.lp.n_own) && (c.scheme != PUCFEM_STOKES_FOOD || c.has_tgrid),
@@ -6782,6 +6990,127 @@ int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2) {
     launch();  // (untimed: the first launch)
     out2[0] = time_launches(c, iters, launch);
     out2[1] = c.vel_launch_bytes(N);
+  });
+}
+
+// ---- MacCormack advection (pucfem_maccormack.hpp)
+int pucfem_set_advection(void* ctx, int32_t what, int32_t scheme) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.set_advection(what, scheme);
+  });
+}
+
+int pucfem_advection_info(void* ctx, int64_t* out11) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();  // (a single-rank Stokes context on a device, built)
+    require(out11 != nullptr, "null output");
+    out11[0] = c.adv_dye;
+    out11[1] = c.adv_vel;
+    out11[2] = c.mc_steps;
+    out11[3] = c.mcv_steps;
+    if (c.st_sl) HIPCHK(hipStreamSynchronize(c.st_sl));
+    c.mc_counts(c.mc_cnt, c.mc_nb, out11 + 4);
+    c.mc_counts(c.mcv_cnt, c.mcv_nb, out11 + 7);
+    out11[10] = (int64_t)c.advection_dev_bytes();
+  });
+}
+
+int pucfem_sl_advect_mc(void* ctx, int32_t nch, const double* cin, const double* u, double dt, double* cout,
+                        int32_t* marks, int32_t* tri) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.dye_ready();
+    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    const size_t tot = (size_t)nch * (size_t)N;
+    double *tx = c.u_scratch(), *ty = tx + 1;
+    double* din = c.smp_scratch<double>(14, tot);
+    double* dout = c.smp_scratch<double>(15, tot);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    double* dch = c.smp_scratch<double>(17, tot);
+    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
+    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
+    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    c.put_all(1, nch, cin, din);
+    c.put_all(2, 1, u, tx);
+    c.mc_fwd(0, N, tx, ty, dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr);
+    c.mc_bwd(0, N, tx, ty, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt);
+    c.get_all(1, nch, cout, dout);
+    if (marks) c.get_all(1, 1, marks, dmark);
+    if (tri) c.get_all(1, 1, tri, dtri);
+  });
+}
+
+int pucfem_sl_advect_vel_mc(void* ctx, const double* f, const double* u, double dt, double* f_out, int32_t* marks,
+                            int32_t* tri) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();
+    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    double* tu = c.u_scratch();
+    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
+    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
+    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
+    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    c.put_all(2, 1, f, din);
+    c.put_all(2, 1, u, tu);
+    c.mc_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt);
+    c.get_all(2, 1, f_out, dout);
+    if (marks) c.get_all(1, 1, marks, dmark);
+    if (tri) c.get_all(1, 1, tri, dtri);
+  });
+}
+
+int pucfem_advection_probe(void* ctx, int32_t what, int32_t nch, int32_t iters, double* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(what == PUCFEM_ADV_DYE || what == PUCFEM_ADV_VELOCITY, "what is PUCFEM_ADV_DYE or PUCFEM_ADV_VELOCITY");
+    if (what == PUCFEM_ADV_DYE) c.dye_ready();
+    else c.inertia_ready();
+    require(iters >= 1 && out4 != nullptr, "iters < 1 or null output");
+    const i64 N = c.mesh.N;
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    if (what == PUCFEM_ADV_DYE) {
+      require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+      const size_t tot = (size_t)nch * (size_t)N;
+      double* din = c.smp_scratch<double>(14, tot);
+      double* dout = c.smp_scratch<double>(15, tot);
+      double* dch = c.smp_scratch<double>(17, tot);
+      HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
+      auto p1 = [&] { c.mc_fwd(0, N, c.ux, c.uy, c.prm.dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr); };
+      auto p2 = [&] {
+        c.mc_bwd(0, N, c.ux, c.uy, c.prm.dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, nullptr, nullptr,
+                 dcnt);
+      };
+      p1();  // (untimed: the first launches)
+      p2();
+      out4[0] = time_launches(c, iters, p1);
+      out4[1] = time_launches(c, iters, p2);
+      out4[2] = c.mc_bytes1(nch, N);
+      out4[3] = c.mc_bytes2(nch, N);
+    } else {
+      double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+      double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
+      auto pass = [&](int which) {
+        c.mc_vel_launch(0, N, c.ux, c.prm.dt, c.ux, dch, dout, drec, nullptr, nullptr, dpart, dcnt, which);
+      };
+      pass(3);  // (untimed: the first launches)
+      out4[0] = time_launches(c, iters, [&] { pass(1); });
+      out4[1] = time_launches(c, iters, [&] { pass(2); });
+      out4[2] = c.mcv_bytes1(N);
+      out4[3] = c.mcv_bytes2(N);
+    }
   });
 }
 

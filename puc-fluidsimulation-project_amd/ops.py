@@ -204,6 +204,55 @@ def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None):
     return nf.astype(bool)
 
 
+def advect_maccormack(c, u, DT, nodes=None, triangles=None, tri=None):
+    """One limited MacCormack step (pucfem_sl_advect_mc; Selle et al. 2008) of the field c (N,) or of the K fields
+    c (K, N), K = 1 .. 16, from one point location per pass and node: ch = SL(c; u, DT), cb = SL(ch; u, -DT),
+    ch + (c - cb) / 2 clamped into the range of c at the vertices of ch's departure triangle.  In place on c as
+    advect_semilagrange; returns the marks (N,) int32: bit 0 the back-trace found no triangle (the node kept c),
+    bit 1 the forward trace found none (it kept ch).  tri (N,) int32, if given, receives the departure triangle's
+    index in `triangles` (-1: none)."""
+    if nodes is None or triangles is None:
+        m = _mesh_or_global(None)
+        nodes, triangles = m.coords, m.triangles
+    cin = np.ascontiguousarray(c, dtype=np.float64)
+    if cin.ndim not in (1, 2) or cin.shape[-1] != len(nodes):
+        raise ValueError(f"advect_maccormack: c must have shape ({len(nodes)},) or (K, {len(nodes)})")
+    ctx = context_for(nodes, triangles)
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros_like(cin)
+    marks = np.zeros(len(nodes), dtype=np.int32)
+    t = np.zeros(len(nodes), dtype=np.int32)
+    _lib.check(ctx.L.pucfem_sl_advect_mc(ctx.h, 1 if cin.ndim == 1 else cin.shape[0], _lib.dptr(cin), _lib.dptr(uu),
+                                         float(DT), _lib.dptr(out), _lib.iptr(marks), _lib.iptr(t)), ctx.h)
+    c[:] = out
+    if tri is not None:
+        tri[:] = t
+    return marks
+
+
+def advect_maccormack_vector(f, u, DT, nodes=None, triangles=None, tri=None):
+    """advect_maccormack of the two components of f (N, 2) at once (pucfem_sl_advect_vel_mc, the inertial step's
+    kernels): each vertex's pair one load, the components limited separately, each with the bits of
+    advect_maccormack on f[:, k] alone.  f may be u.  In place on f; returns the marks (N,)."""
+    if nodes is None or triangles is None:
+        m = _mesh_or_global(None)
+        nodes, triangles = m.coords, m.triangles
+    fin = np.ascontiguousarray(f, dtype=np.float64)
+    if fin.shape != (len(nodes), 2):
+        raise ValueError(f"advect_maccormack_vector: f must have shape ({len(nodes)}, 2)")
+    ctx = context_for(nodes, triangles)
+    uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros_like(fin)
+    marks = np.zeros(len(fin), dtype=np.int32)
+    t = np.zeros(len(fin), dtype=np.int32)
+    _lib.check(ctx.L.pucfem_sl_advect_vel_mc(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
+                                             _lib.iptr(marks), _lib.iptr(t)), ctx.h)
+    f[:] = out
+    if tri is not None:
+        tri[:] = t
+    return marks
+
+
 def buildStiffnessMatrix(nodes, triangles, g_source=1.0):
     """StokesColor.py:98-128: (A, -B) with B = 0 (the reference never fills it)."""
     ctx = context_for(nodes, triangles)

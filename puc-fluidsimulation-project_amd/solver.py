@@ -22,6 +22,18 @@ SAMPLE_FIELDS = {"u": (_lib.F_U, 2), "u_star": (_lib.F_USTAR, 2), "p": (_lib.F_P
                  "c": (_lib.F_C, 1), "vorticity": (_lib.F_VORTICITY, 1)}
 FLOW_KEYS = ("max_vorticity", "enstrophy", "kinetic_energy", "max_speed")
 _SAMPLE_NCOMP = {f: n for f, n in SAMPLE_FIELDS.values()}
+ADVECTION_NAMES = ("sl", "maccormack")  # pucfem_set_advection's schemes, by PUCFEM_ADV_SL / PUCFEM_ADV_MACCORMACK
+
+
+def advection_scheme(name):
+    """The PUCFEM_ADV_* scheme of advection='sl' | 'maccormack' (an int passes through)."""
+    if isinstance(name, str):
+        if name not in ADVECTION_NAMES:
+            raise ValueError(f"advection must be one of {ADVECTION_NAMES}, got {name!r}")
+        return ADVECTION_NAMES.index(name)
+    if int(name) not in (0, 1):
+        raise ValueError(f"advection must be one of {ADVECTION_NAMES}, got {name!r}")
+    return int(name)
 
 
 def dye_field(name):
@@ -517,6 +529,27 @@ class Context:
         self._c(self.L.pucfem_inertia_probe(self.h, int(iters), o))
         return dict(kernel_ms=o[0], algo_bytes=o[1])
 
+    def set_advection(self, what, scheme):
+        """The advection scheme (pucfem_set_advection) of the dye (what = ADV_DYE), of the inertial step's velocity
+        (ADV_VELOCITY) or of both (their sum): 'sl' the reference's first-order step, 'maccormack' two of them and
+        a clamp (second order)."""
+        self._c(self.L.pucfem_set_advection(self.h, int(what), advection_scheme(scheme)))
+
+    def advection_info(self):
+        """pucfem_advection_info: the two schemes, the MacCormack steps since each was switched on, the counts of
+        the last launch of each (rows whose back-trace / forward trace found no triangle, clamped values) and the
+        device bytes held."""
+        o = (ct.c_int64 * 11)()
+        self._c(self.L.pucfem_advection_info(self.h, o))
+        return dict(dye=ADVECTION_NAMES[o[0]], velocity=ADVECTION_NAMES[o[1]], dye_steps=o[2], velocity_steps=o[3],
+                    dye_counts=(o[4], o[5], o[6]), velocity_counts=(o[7], o[8], o[9]), bytes=o[10])
+
+    def advection_probe(self, what, nch=1, iters=10):
+        """Kernel times of the two MacCormack passes (pucfem_advection_probe; tools/maccormack_bench.py)."""
+        o = (ct.c_double * 4)()
+        self._c(self.L.pucfem_advection_probe(self.h, int(what), int(nch), int(iters), o))
+        return dict(pass1_ms=o[0], pass2_ms=o[1], pass1_bytes=o[2], pass2_bytes=o[3])
+
     def flow_info(self, member=None):
         """Flow summaries of the current u, reduced on the device (pucfem_flow_info; one launch, four doubles
         copied): max |vorticity|, the enstrophy 1/2 sum w vorticity^2, the kinetic energy 1/2 sum w |u|^2 and the
@@ -614,7 +647,13 @@ class StokesSimulation:
     or on one rank of a torch.distributed job (dist=(rank, world, unique_id))."""
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
-                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False):
+                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl"):
+        adv = advection_scheme(advection)
+        # (the dye's scheme on color runs, the velocity's too on inertial ones)
+        adv_what = (_lib.ADV_DYE if scheme == "color" else 0) | (_lib.ADV_VELOCITY if inertia else 0)
+        if adv and not adv_what:
+            raise ValueError("advection='maccormack' moves the dye of a 'color' run and the velocity of an inertial "
+                             "one: a 'food' run without inertia has neither")
         self.mesh = mesh
         self.bc = bc or SquirmerBC()
         self.dt = dt
@@ -639,12 +678,14 @@ class StokesSimulation:
             pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
             self.ctx.set_field(_lib.F_TRACERS, pts)
             self.n_tracers = len(pts)
-        if inertia:
-            try:
+        try:
+            if inertia:
                 self.ctx.set_inertia(True)
-            except Exception:
-                self.ctx.close()
-                raise
+            if adv:
+                self.ctx.set_advection(adv_what, adv)
+        except Exception:
+            self.ctx.close()
+            raise
 
     def step(self, n=1):
         st = self.ctx.step(n)
@@ -710,6 +751,31 @@ class StokesSimulation:
         """Context.inertia_info of this run as (on, steps, notfound, bytes)."""
         d = self.ctx.inertia_info()
         return d["on"], d["steps"], d["notfound"], d["bytes"]
+
+    @property
+    def dye_advection(self):
+        """'sl' or 'maccormack': how every step moves c and the dye channels -- the reference's first-order
+        semi-Lagrangian step, or two of them and a clamp (Selle et al.'s limited MacCormack scheme, second order; not
+        conservative).  Setting it takes effect at the next step."""
+        return self.ctx.advection_info()["dye"]
+
+    @dye_advection.setter
+    def dye_advection(self, scheme):
+        self.ctx.set_advection(_lib.ADV_DYE, scheme)
+
+    @property
+    def velocity_advection(self):
+        """'sl' or 'maccormack': how an inertial step forms u_a from u.  It may be set while inertia is off and takes
+        effect when inertia is on."""
+        return self.ctx.advection_info()["velocity"]
+
+    @velocity_advection.setter
+    def velocity_advection(self, scheme):
+        self.ctx.set_advection(_lib.ADV_VELOCITY, scheme)
+
+    def advection_info(self):
+        """Context.advection_info of this run."""
+        return self.ctx.advection_info()
 
     def dye_mixing(self):
         """(K, 3): mixing_index (StokesColor.py:391-403) (I, mu, var) of every dye channel over marker == 0, reduced
@@ -805,6 +871,13 @@ def _ensemble_flags(inertia, M):
     return a.astype(bool)
 
 
+def _ensemble_advection(advection):
+    """Ensembles step the first-order advection alone: advection='maccormack' is refused."""
+    if advection_scheme(advection) != 0:
+        raise ValueError("ensembles step the first-order semi-Lagrangian advection only: advection='maccormack' "
+                         "belongs to StokesSimulation / solve (one squirmer per context)")
+
+
 def ensemble_dirichlet_values(mesh: Mesh, bcs):
     """Dirichlet nodes and per-member values (M, n_dir, 2) of an ensemble: row m is stokes_setup(mesh, bcs[m])'s
     values (the wall values, then the squirmer surface values of makeDirBCU, StokesColor.py:405-427).  Host only."""
@@ -831,7 +904,8 @@ class StokesEnsemble:
     StokesSimulation(..., inertia=True) does, bit for bit (finite Reynolds number); the others step as before."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
-                 tracers=None, inertia=False):
+                 tracers=None, inertia=False, advection="sl"):
+        _ensemble_advection(advection)
         self.bcs = _check_ensemble_bcs(bcs)
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -1035,9 +1109,11 @@ class StokesEnsemble:
 
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
-                   inertia=False):
+                   inertia=False, advection="sl"):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
-    for all members or one per member (StokesEnsemble.inertia)."""
+    for all members or one per member (StokesEnsemble.inertia).  advection: 'sl' only (ensembles have no MacCormack
+    step)."""
+    _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
@@ -1178,7 +1254,7 @@ class Result:
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
-          tol: Tolerances | None = None, log=None, dyes=None, inertia=False):
+          tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl"):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -1186,7 +1262,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     reference's per-step print line (StokesColor.py:586 / StokesFood.py:505).  dyes (scheme 'color'): (K, N) dye
     channels advected beside c (StokesSimulation.dyes); the result's `dyes` holds them after the last step.
     inertia (schemes 'color' and 'food'): every step advects the velocity by itself in front of the viscous solve
-    (StokesSimulation.inertia)."""
+    (StokesSimulation.inertia).  advection 'sl' | 'maccormack' (schemes 'color' and 'food'): the first-order
+    semi-Lagrangian transport of the reference, or the limited MacCormack scheme (second order) for the dye of a
+    'color' run and the velocity of an inertial one (StokesSimulation.dye_advection / velocity_advection)."""
+    if advection_scheme(advection) and scheme not in ("color", "food"):
+        raise ValueError("advection belongs to the Stokes schemes 'color' and 'food'")
     if dyes is not None and scheme != "color":
         raise ValueError("dyes belong to scheme 'color'")
     if inertia and scheme not in ("color", "food"):
@@ -1194,7 +1274,7 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     if scheme in ("color", "food"):
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
-        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia)
+        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection)
         if dyes is not None:
             sim.dyes = dyes
         st = sim.step(steps) if steps else []
