@@ -357,6 +357,45 @@ int pucfem_ens_set_inertia(void* ctx, int32_t member /* -1 = all */, int32_t on)
    last inertial launch (summed on the device; 0 before the first), [3] device bytes the ensemble holds for inertia */
 int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4);
 
+/* ---- Brownian tracers: food that diffuses ---- */
+/* The tracers are deterministic points; in the steady flow a run settles to, a tracer on a streamline outside the
+   capture annulus is never eaten.  With a diffusivity D > 0 every free tracer also takes a random-walk increment per
+   tracer step, reproducible bit for bit from a 64-bit seed.  For tracer k in the 1-based tracer step `stepno` (the
+   count pucfem_tracer_info reports, plus one), every product and sum as written:
+     status[k] == 1 at the start of the step: absorbed food -- nothing is loaded or stored for it, it counts as eaten
+     else  (vx, vy) as without diffusion (NaN outside the mesh)
+           r0..r3 = Philox4x32-10(counter = (k, stepno, 0, 0), key = (seed & 0xffffffff, seed >> 32))
+           U1 = ((r0 >> 5) * 67108864.0 + (r1 >> 6)) * 2^-53, U2 likewise from r2, r3      (in [0, 1), exact)
+           a  = sqrt(6.0 * D * dt)                                                          (host, double)
+           nx = (px + vx * dt) + a * (2.0 * U1 - 1.0),  ny = (py + vy * dt) + a * (2.0 * U2 - 1.0)
+           nx = nx mod 1;  ny < ylo: ny = ylo + (ylo - ny), else ny > yhi: ny = yhi - (ny - yhi)
+           store, then the capture test (sqrt(ddx*ddx + ddy*ddy) <= capture_radius; the capture step on the transition)
+   ylo, yhi: the smallest and largest node y of the mesh (the no-slip walls), from the build.  The increments are
+   uniform on [-a, a], variance 2 D dt per coordinate; NaN stays NaN.  The random stream depends on (seed, k, stepno)
+   only -- not on the kernel form, the grid, the member index or the launch count -- and setting the tracers resets
+   stepno and so restarts it.  D = 0 (the default) is the step without this call, bit for bit and launch for launch:
+   eaten tracers keep moving there; the freeze belongs to D > 0.
+   pucfem_set_tracer_diffusion governs pucfem_step and pucfem_tracer_step (there dt is the call's own) of single-rank
+   PUCFEM_STOKES_COLOR / PUCFEM_STOKES_FOOD contexts after pucfem_build_operators, on every solver path, with or
+   without inertia.  PUCFEM_ESTATE on multi-rank, heat and Poisson contexts and before the build (decided before the
+   device is asked for); PUCFEM_EINVAL for D negative, NaN or infinite; PUCFEM_ENODEV on a host-only context.  A
+   setting made between two steps takes effect at the next step (a small-mesh context captures its step again).
+   pucfem_build_operators and pucfem_ctx_destroy set D back to 0.  The context holds no device memory for it. */
+int pucfem_set_tracer_diffusion(void* ctx, double D, uint64_t seed);
+/* The same per ensemble member (member = -1: every member); the context's setting and the members' stay apart.  Two
+   members with one seed draw the same increments (common random numbers).  A member steps bit for bit as a
+   pucfem_step run with its D and seed; a member with D = 0 takes the plain move.  The step stays one captured chain,
+   captured again only between "no member on" and "some member on".  The members' amplitudes and keys (members each)
+   are allocated when a member is first given D > 0, are counted in pucfem_ens_info's bytes and are freed with the
+   ensemble.  PUCFEM_ESTATE as above and without an ensemble; PUCFEM_EINVAL as above and for a member out of range. */
+int pucfem_ens_set_tracer_diffusion(void* ctx, int32_t member /* -1 = all */, double D, uint64_t seed);
+/* The setting of the context (member = -1) or of ensemble member 0 .. members - 1; D or seed may be null. */
+int pucfem_get_tracer_diffusion(void* ctx, int32_t member /* -1 = the context */, double* D, uint64_t* seed);
+/* Measurement: the tracer launch of pucfem_step (the context's current u, tracers and diffusion setting; time step
+   dt), launched once untimed and then `iters` times back to back between two events; the tracers move.
+   out2[0]: milliseconds per launch; out2[1]: tracers. */
+int pucfem_tracer_probe(void* ctx, double dt, int32_t iters, double* out2);
+
 /* ---- MacCormack advection: second-order transport of the dye and of the velocity ---- */
 /* advect_semilagrange (StokesColor.py:347-389) is first order and its linear interpolation a diffusion of order
    h^2 / dt that no parameter controls.  With the MacCormack scheme of Selle et al. (J. Sci. Comput. 35, 2008) a field

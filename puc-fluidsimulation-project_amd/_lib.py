@@ -117,6 +117,10 @@ SIGNATURES = {
     "pucfem_inertia_probe": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_ens_set_inertia": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_ens_inertia_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_set_tracer_diffusion": ([_P, ct.c_double, ct.c_uint64], ct.c_int),
+    "pucfem_ens_set_tracer_diffusion": ([_P, ct.c_int32, ct.c_double, ct.c_uint64], ct.c_int),
+    "pucfem_get_tracer_diffusion": ([_P, ct.c_int32, _D, ct.POINTER(ct.c_uint64)], ct.c_int),
+    "pucfem_tracer_probe": ([_P, ct.c_double, ct.c_int32, _D], ct.c_int),
     "pucfem_set_advection": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_advection_info": ([_P, _I64], ct.c_int),
     "pucfem_sl_advect_mc": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),

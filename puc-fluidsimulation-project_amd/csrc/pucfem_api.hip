@@ -163,6 +163,15 @@ struct Ens {
   bool adv_stale = true;
   int adv_any = 0;                 // members with their flag on
   bool chain_adv = false;          // the captured graphs hold the inertial launch
+  // Brownian tracers per member (pucfem_ens_set_tracer_diffusion; the BROWN tracer kernels), allocated when a member
+  // is first switched on and kept: the members' amplitudes sqrt(6 D dt) and Philox keys as the kernels read them (M
+  // each); a[m] == 0 is the plain move
+  double* br_a = nullptr;
+  uint2* br_key = nullptr;
+  std::vector<double> br_D;        // the settings (empty: never enabled)
+  std::vector<uint64_t> br_seed;
+  int br_any = 0;                  // members with D > 0
+  bool chain_br = false;           // the captured graphs hold the BROWN tracer launch
   int nb_tr = 1;             // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
@@ -623,6 +632,19 @@ struct Ctx {
   double* part_tr = nullptr;  // the cloud kernels' per-block eaten partials (TRACER_CLOUD_MAXB)
   unsigned long long* trcensus = nullptr;  // pucfem_tracer_info's two counts
   int tr_blocks = 0, tr_threads = 0;       // the last tracer launch
+  // Brownian tracers (pucfem_set_tracer_diffusion, pucfem_brownian.hpp): the context's own setting, host values only
+  // (the kernels take them as arguments: a changed setting drops the captured step graphs).  tr_ylo / tr_yhi: the
+  // reflecting walls, the mesh's smallest and largest node y, from the build.
+  double tr_D = 0.0;
+  uint64_t tr_seed = 0;
+  double tr_ylo = 0.0, tr_yhi = 0.0;
+  // the single-rank Stokes context the tracers' diffusion lives on (decided before the device is asked for)
+  void brownian_ready() const {
+    need_built();
+    if (!(scheme == PUCFEM_STOKES_COLOR || scheme == PUCFEM_STOKES_FOOD))
+      throw Error(PUCFEM_ESTATE, "tracer diffusion needs a Stokes context");
+    if (dist() || world != 1) throw Error(PUCFEM_ESTATE, "tracer diffusion is single-rank");
+  }
   // iteration count of the last solve per `which` slot (the next solve's first host check): 0 viscous,
   // 1 / 2 the two pressure solves of a step, 3 / 4 standalone viscous / pressure solves (pucfem_solve)
   int last_it[6] = {0, 0, 0, 0, 0, 0};
@@ -3589,12 +3611,28 @@ struct Ctx {
       KCHK();
       return;
     }
+    if (tr_D > 0.0) {  // Brownian tracers: the same launch, the BROWN instantiation
+      const Brown br{std::sqrt(6.0 * tr_D * dt), (uint32_t)(tr_seed & 0xffffffffu), (uint32_t)(tr_seed >> 32), tr_ylo,
+                     tr_yhi};
+      if (cloud)
+        hipLaunchKernelGGL(k_tracer_cloud<true>, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx,
+                           fy, ntr, trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius,
+                           part_tr, rt, br);
+      else
+        hipLaunchKernelGGL(k_tracer<true>, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
+                           trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6,
+                           br);
+      KCHK();
+      return;
+    }
     if (cloud)
-      hipLaunchKernelGGL(k_tracer_cloud, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
-                         trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt);
+      hipLaunchKernelGGL(k_tracer_cloud<false>, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx,
+                         fy, ntr, trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius,
+                         part_tr, rt, BrownOff{});
     else
-      hipLaunchKernelGGL(k_tracer, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr, trx,
-                         try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6);
+      hipLaunchKernelGGL(k_tracer<false>, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
+                         trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6,
+                         BrownOff{});
     KCHK();
   }
   // blocks in x of a tracer launch over n tracers: 1 = the one-block kernels, else the cloud kernels' capped grid
@@ -4551,6 +4589,10 @@ void build(Ctx& c) {
   }
   if (literal) build_sell(c.Lit, c.lp, c.sLit);
   c.built = true;
+  c.tr_D = 0.0;  // (pucfem_set_tracer_diffusion: off after every build)
+  c.tr_seed = 0;
+  c.tr_ylo = c.mesh.y.empty() ? 0.0 : *std::min_element(c.mesh.y.begin(), c.mesh.y.end());
+  c.tr_yhi = c.mesh.y.empty() ? 0.0 : *std::max_element(c.mesh.y.begin(), c.mesh.y.end());
   // tooling hook (tools/spmv_lab.hip --real): the pressure operator's SELL image
   if (const char* path = std::getenv("PUCFEM_DUMP_SELL")) {
     if (stokes) {
@@ -5853,16 +5895,25 @@ void ens_enqueue_step(Ctx& c) {
                        (const double*)c.dwmix, (const double*)e.vals, e.part_mx, rm, e.c);
     KCHK();
   } else if (e.ntr > 0) {
-    if (e.nb_tr > 1) {
-      const RedOut rt{e.vals + 6, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
-      hipLaunchKernelGGL(k_ens_tracer_cloud, dim3(e.nb_tr, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T},
-                         c.tgrid, (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep,
-                         c.prm.dt, c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt);
-    } else {
-      hipLaunchKernelGGL(k_ens_tracer, dim3(1, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.tgrid,
-                         (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
-                         c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.vals);
-    }
+    // with at least one member's diffusion on: the BROWN instantiation of the same launch (which members walk, and
+    // with what amplitude and key, the kernel reads from device memory)
+    const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+    const RedOut rt{e.vals + 6, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
+    auto launch = [&](auto brown, auto eb) {
+      constexpr bool B = decltype(brown)::value;
+      if (e.nb_tr > 1)
+        hipLaunchKernelGGL(k_ens_tracer_cloud<B>, dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
+                           (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                           c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt, eb);
+      else
+        hipLaunchKernelGGL(k_ens_tracer<B>, dim3(1, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n, (const double*)e.u,
+                           e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt, c.prm.center_x, c.prm.center_y,
+                           c.prm.capture_radius, e.vals, eb);
+    };
+    if (e.br_any > 0)
+      launch(std::true_type{}, EnsBrown{(const double*)e.br_a, (const uint2*)e.br_key, c.tr_ylo, c.tr_yhi});
+    else
+      launch(std::false_type{}, EnsBrownOff{});
     KCHK();
     e.tr_blocks = e.nb_tr;
     e.tr_threads = BS;
@@ -6167,10 +6218,12 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     };
     // (the chain has the inertial launch iff a member's flag is on: graphs of the other chain are dropped.  Which
     // members are on is read from device memory by the kernels, so it needs no new capture.)
-    if (e.chain_adv != (e.adv_any > 0)) {
+    // (the same for the tracers' diffusion: the BROWN tracer launch iff a member's D is positive)
+    if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0)) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
       e.chain_adv = e.adv_any > 0;
+      e.chain_br = e.br_any > 0;
     }
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
@@ -6816,6 +6869,98 @@ int pucfem_tracer_info(void* ctx, int32_t member, int64_t* out6) {
     out6[3] = steps;
     out6[4] = blocks;
     out6[5] = threads;
+  });
+}
+
+// ---- Brownian tracers (pucfem_brownian.hpp)
+int pucfem_set_tracer_diffusion(void* ctx, double D, uint64_t seed) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.brownian_ready();
+    require(std::isfinite(D) && D >= 0.0, "D must be finite and not negative");
+    c.need_dev();
+    if (D == c.tr_D && seed == c.tr_seed) return;
+    // (the captured small-mesh step holds the amplitude and key as kernel arguments, and the plain or the BROWN
+    // launch: the next pucfem_step captures again)
+    HIPCHK(hipStreamSynchronize(c.st));
+    c.drop_step_graphs();
+    c.tr_D = D;
+    c.tr_seed = seed;
+  });
+}
+
+int pucfem_ens_set_tracer_diffusion(void* ctx, int32_t member, double D, uint64_t seed) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.brownian_ready();
+    if (!c.ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
+    Ens& e = *c.ens;
+    require(std::isfinite(D) && D >= 0.0, "D must be finite and not negative");
+    require(member >= -1 && member < e.M, "member index out of range");
+    const size_t sM = (size_t)e.M;
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
+    if (e.br_D.empty()) {  // (host values only: the device buffers wait for the first D > 0)
+      e.br_D.assign(sM, 0.0);
+      e.br_seed.assign(sM, 0);
+    }
+    bool changed = false;
+    for (size_t m = m0; m < m1; ++m) {
+      if (e.br_D[m] == D && e.br_seed[m] == seed) continue;
+      e.br_D[m] = D;
+      e.br_seed[m] = seed;
+      changed = true;
+    }
+    if (!changed) return;
+    std::vector<double> a(sM);
+    std::vector<uint2> key(sM);
+    int any = 0;
+    for (size_t m = 0; m < sM; ++m) {
+      a[m] = std::sqrt(6.0 * e.br_D[m] * c.prm.dt);
+      key[m] = make_uint2((uint32_t)(e.br_seed[m] & 0xffffffffu), (uint32_t)(e.br_seed[m] >> 32));
+      any += e.br_D[m] > 0.0 ? 1 : 0;
+    }
+    e.br_any = any;
+    if (!e.br_a) {
+      if (any == 0) return;  // (nothing was ever on: nothing is allocated and nothing launched)
+      e.br_a = e.alloc<double>(sM, c.st);
+      e.br_key = e.alloc<uint2>(sM, c.st);
+    }
+    c.h2d(e.br_a, a.data(), sizeof(double) * sM);
+    c.h2d(e.br_key, key.data(), sizeof(uint2) * sM);
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_get_tracer_diffusion(void* ctx, int32_t member, double* D, uint64_t* seed) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.brownian_ready();
+    double d = c.tr_D;
+    uint64_t s = c.tr_seed;
+    if (member != -1) {
+      if (!c.ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
+      require(member >= 0 && member < c.ens->M, "member index out of range");
+      const bool have = !c.ens->br_D.empty();
+      d = have ? c.ens->br_D[(size_t)member] : 0.0;
+      s = have ? c.ens->br_seed[(size_t)member] : 0;
+    }
+    c.need_dev();
+    if (D) *D = d;
+    if (seed) *seed = s;
+  });
+}
+
+int pucfem_tracer_probe(void* ctx, double dt, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.brownian_ready();
+    c.need_dev();
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    require(c.has_tgrid && c.ntr > 0, "tracer_probe needs a STOKES_FOOD context with tracers");
+    auto launch = [&] { c.tracer_advance(dt); };
+    launch();  // (untimed: the first launch)
+    out2[0] = time_launches(c, iters, launch);
+    out2[1] = (double)c.ntr;
   });
 }
 

@@ -432,11 +432,25 @@ __global__ __launch_bounds__(BS) void k_ens_mix2(int64_t n, const double* __rest
   red_finish(R, part, sh);
 }
 
+// member m's setting of the BROWN kernels (block-uniform); a = 0 in the plain instantiation
+template <bool BROWN>
+__device__ __forceinline__ Brown ens_brown(const EnsBrownArg<BROWN>& eb, int32_t m) {
+  if constexpr (BROWN) {
+    const uint2 key = eb.key[m];
+    return Brown{eb.a[m], key.x, key.y, eb.ylo, eb.yhi};
+  } else {
+    return Brown{0.0, 0u, 0u, 0.0, 0.0};
+  }
+}
+
 // k_tracer per member (one block each): the single path's locate / interpolate / move.  tx, ty, status: M x ntr.
+// BROWN (pucfem_brownian.hpp): the member's amplitude and key from device memory; a block-uniform branch, a[m] == 0
+// the plain move.
+template <bool BROWN>
 __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                    int32_t ntr, double* tx, double* ty, double* status,
                                                    int32_t* capstep, int32_t* stepctr, double dt, double cx, double cy,
-                                                   double capture, double* vals) {
+                                                   double capture, double* vals, EnsBrownArg<BROWN> eb) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -446,13 +460,23 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
   double* stm = status + (int64_t)m * ntr;
   int32_t* cpm = capstep + (int64_t)m * ntr;
   const int32_t stepno = stepctr[m] + 1;  // (the member's own count: k_tracer's)
+  const Brown br = ens_brown<BROWN>(eb, m);
   double eaten = 0.0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
+    if (BROWN && br.a != 0.0) {
+      if (stm[k] == 1.0) {
+        eaten += 1.0;
+        continue;
+      }
+    }
     const double px = txm[k], py = tym[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(Mh, G, px, py);
     if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
+    if (BROWN && br.a != 0.0)
+      eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
+    else
+      eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) {
@@ -461,10 +485,12 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
   }
 }
 // k_tracer_cloud per member: grid (blocks, M), the member's partials, ticket and step count (ro.out: vals + 6)
+template <bool BROWN>
 __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                          int32_t ntr, double* tx, double* ty, double* status,
                                                          int32_t* capstep, int32_t* stepctr, double dt, double cx,
-                                                         double cy, double capture, double* part, RedOut ro) {
+                                                         double cy, double capture, double* part, RedOut ro,
+                                                         EnsBrownArg<BROWN> eb) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -475,14 +501,24 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
   int32_t* cpm = capstep + (int64_t)m * ntr;
   const RedOut R = ens_red(ro, m, part);
   const int32_t stepno = stepctr[m] + 1;
+  const Brown br = ens_brown<BROWN>(eb, m);
   double eaten = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
     const int32_t k = (int32_t)i;
+    if (BROWN && br.a != 0.0) {
+      if (stm[k] == 1.0) {  // (this lane's iteration only: red_finish's barrier and ticket are behind the loop)
+        eaten += 1.0;
+        continue;
+      }
+    }
     const double px = txm[k], py = tym[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(Mh, G, px, py);
     if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
+    if (BROWN && br.a != 0.0)
+      eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
+    else
+      eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) red_part(R, part, 0, t);

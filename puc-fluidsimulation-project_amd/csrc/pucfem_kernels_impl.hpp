@@ -5,6 +5,7 @@
 
 #include "pucfem_kernels.hpp"
 #include "pucfem_locate.hpp"
+#include "pucfem_brownian.hpp"
 
 namespace pucfem {
 namespace dev {
@@ -2668,18 +2669,30 @@ constexpr int TRACER_CLOUD_MAXB = 2048;  // the cloud kernels' grid cap in x (me
 
 // stepctr: the set's tracer steps so far, in device memory (a captured step's arguments are fixed); the step being
 // taken is *stepctr + 1.  Every thread reads it before the block's barrier, thread 0 stores the new count after it.
+// BROWN (pucfem_brownian.hpp): the move with the random increment of setting br; false is the plain step.  An
+// absorbed tracer leaves its loop iteration only: every thread reaches the barriers behind the loop.
+template <bool BROWN>
 __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, const double* __restrict__ uy,
                          int32_t ntr, double* tx, double* ty, double* status, int32_t* capstep, int32_t* stepctr,
-                         double dt, double cx, double cy, double capture, double* eaten_out) {
+                         double dt, double cx, double cy, double capture, double* eaten_out, BrownArg<BROWN> br) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
+    if constexpr (BROWN) {
+      if (status[k] == 1.0) {
+        eaten += 1.0;
+        continue;
+      }
+    }
     const double px = tx[k], py = ty[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(M, G, px, py);
     if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
+    if constexpr (BROWN)
+      eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
+    else
+      eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) {
@@ -2690,21 +2703,31 @@ __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, co
 // k_tracer on a grid: one tracer per thread, grid-stride past the capped grid; the eaten count from per-block
 // partials (red_finish; ro.out is never null here).  The block that finishes the reduction stores the new step
 // count: every block read the old one before it drew its ticket.
+template <bool BROWN>
 __global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const double* __restrict__ ux,
                                                      const double* __restrict__ uy, int32_t ntr, double* tx,
                                                      double* ty, double* status, int32_t* capstep, int32_t* stepctr,
                                                      double dt, double cx, double cy, double capture, double* part,
-                                                     RedOut ro) {
+                                                     RedOut ro, BrownArg<BROWN> br) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
   for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
     const int32_t k = (int32_t)i;
+    if constexpr (BROWN) {
+      if (status[k] == 1.0) {  // (absorbed: this lane's iteration only; the block's barrier and ticket are behind the loop)
+        eaten += 1.0;
+        continue;
+      }
+    }
     const double px = tx[k], py = ty[k];
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(M, G, px, py);
     if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
-    eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
+    if constexpr (BROWN)
+      eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
+    else
+      eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) red_part(ro, part, 0, t);

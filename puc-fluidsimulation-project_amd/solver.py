@@ -523,6 +523,24 @@ class Context:
         self._c(self.L.pucfem_inertia_info(self.h, o))
         return dict(on=bool(o[0]), steps=o[1], notfound=o[2], bytes=o[3])
 
+    def set_tracer_diffusion(self, D, seed=0):
+        """Brownian tracers (pucfem_set_tracer_diffusion): every free tracer also takes a random-walk increment of
+        diffusivity D per tracer step, reproducible from the 64-bit seed; D = 0 is the plain step."""
+        self._c(self.L.pucfem_set_tracer_diffusion(self.h, float(D), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def tracer_diffusion(self, member=-1):
+        """(D, seed) of the context (member = -1) or of an ensemble member (pucfem_get_tracer_diffusion)."""
+        d, s = ct.c_double(0.0), ct.c_uint64(0)
+        self._c(self.L.pucfem_get_tracer_diffusion(self.h, int(member), ct.byref(d), ct.byref(s)))
+        return d.value, int(s.value)
+
+    def tracer_probe(self, dt, iters=20):
+        """Kernel time of one tracer launch on the current u, tracers and diffusion setting (pucfem_tracer_probe;
+        tools/brownian_bench.py).  The tracers move."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_tracer_probe(self.h, float(dt), int(iters), o))
+        return dict(kernel_ms=o[0], tracers=int(o[1]))
+
     def inertia_probe(self, iters=10):
         """Kernel time of one inertial launch on the current u (pucfem_inertia_probe; tools/inertia_bench.py)."""
         o = (ct.c_double * 2)()
@@ -647,7 +665,8 @@ class StokesSimulation:
     or on one rank of a torch.distributed job (dist=(rank, world, unique_id))."""
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
-                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl"):
+                 tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl",
+                 tracer_diffusivity=0.0, tracer_seed=0):
         adv = advection_scheme(advection)
         # (the dye's scheme on color runs, the velocity's too on inertial ones)
         adv_what = (_lib.ADV_DYE if scheme == "color" else 0) | (_lib.ADV_VELOCITY if inertia else 0)
@@ -683,9 +702,32 @@ class StokesSimulation:
                 self.ctx.set_inertia(True)
             if adv:
                 self.ctx.set_advection(adv_what, adv)
+            if tracer_diffusivity != 0.0 or tracer_seed != 0:
+                self.ctx.set_tracer_diffusion(tracer_diffusivity, tracer_seed)
         except Exception:
             self.ctx.close()
             raise
+
+    @property
+    def tracer_diffusivity(self):
+        """The tracers' diffusivity D (Brownian food): with D > 0 every free tracer takes, per step, a random-walk
+        increment uniform on [-a, a], a = sqrt(6 D dt), on top of its move (variance 2 D dt per coordinate), is
+        reflected at the walls and, once eaten, stays where it was absorbed.  0 (the default): the reference's
+        deterministic tracers.  Setting it takes effect at the next step."""
+        return self.ctx.tracer_diffusion()[0]
+
+    @tracer_diffusivity.setter
+    def tracer_diffusivity(self, D):
+        self.ctx.set_tracer_diffusion(D, self.ctx.tracer_diffusion()[1])
+
+    @property
+    def tracer_seed(self):
+        """The 64-bit seed of the tracers' random walk: the increments depend on (seed, tracer, tracer step) alone."""
+        return self.ctx.tracer_diffusion()[1]
+
+    @tracer_seed.setter
+    def tracer_seed(self, seed):
+        self.ctx.set_tracer_diffusion(self.ctx.tracer_diffusion()[0], seed)
 
     def step(self, n=1):
         st = self.ctx.step(n)
@@ -871,6 +913,19 @@ def _ensemble_flags(inertia, M):
     return a.astype(bool)
 
 
+def _ensemble_diffusion(tracer_diffusivity, tracer_seed, M):
+    """The tracer_diffusivity= and tracer_seed= arguments of an ensemble of M members as an (M,) float64 and an (M,)
+    uint64 array: one value for all, or M of them."""
+    d = np.asarray(tracer_diffusivity, dtype=np.float64)
+    if d.ndim != 0 and d.shape != (M,):
+        raise ValueError(f"tracer_diffusivity must be one value or one per member: {M} members, got shape {d.shape}")
+    s = np.asarray(tracer_seed, dtype=object)  # (Python ints: all 64 bits)
+    if s.ndim != 0 and s.shape != (M,):
+        raise ValueError(f"tracer_seed must be one value or one per member: {M} members, got shape {s.shape}")
+    seeds = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in np.broadcast_to(s, (M,)).tolist()], dtype=np.uint64)
+    return np.broadcast_to(d, (M,)).copy(), seeds
+
+
 def _ensemble_advection(advection):
     """Ensembles step the first-order advection alone: advection='maccormack' is refused."""
     if advection_scheme(advection) != 0:
@@ -904,12 +959,13 @@ class StokesEnsemble:
     StokesSimulation(..., inertia=True) does, bit for bit (finite Reynolds number); the others step as before."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
-                 tracers=None, inertia=False, advection="sl"):
+                 tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0):
         _ensemble_advection(advection)
         self.bcs = _check_ensemble_bcs(bcs)
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
         flags = _ensemble_flags(inertia, len(self.bcs))
+        diff, seeds = _ensemble_diffusion(tracer_diffusivity, tracer_seed, len(self.bcs))
         nodes, vals = ensemble_dirichlet_values(mesh, self.bcs)
         self.mesh = mesh
         self.dt = dt
@@ -935,6 +991,8 @@ class StokesEnsemble:
             self.ctx._c(self.ctx.L.pucfem_ens_create(self.ctx.h, self.M, _lib.dptr(vals)))
             if flags.any():
                 self.inertia = flags
+            if diff.any() or seeds.any():
+                self.set_tracer_diffusion(diff, seeds)
         except Exception:
             self.ctx.close()
             raise
@@ -1020,6 +1078,32 @@ class StokesEnsemble:
         else:
             for m, f in enumerate(flags):
                 self.set_inertia(bool(f), m)
+
+    # ---- Brownian tracers per member (pucfem_ens_set_tracer_diffusion)
+    def set_tracer_diffusion(self, D, seed=0, member=None):
+        """The tracers' diffusivity and random seed of one member, or (member=None) of all: one value each, or one per
+        member.  A member steps as StokesSimulation(..., tracer_diffusivity=D, tracer_seed=seed) does, bit for bit;
+        members with one seed draw the same increments.  It takes effect at the next step."""
+        L, h = self.ctx.L, self.ctx.h
+        if member is not None:
+            self.ctx._c(L.pucfem_ens_set_tracer_diffusion(h, int(member), float(D), int(seed) & 0xFFFFFFFFFFFFFFFF))
+            return
+        d, s = _ensemble_diffusion(D, seed, self.M)
+        if (d == d[0]).all() and (s == s[0]).all():
+            self.ctx._c(L.pucfem_ens_set_tracer_diffusion(h, -1, float(d[0]), int(s[0])))
+        else:
+            for m in range(self.M):
+                self.ctx._c(L.pucfem_ens_set_tracer_diffusion(h, m, float(d[m]), int(s[m])))
+
+    @property
+    def tracer_diffusivity(self):
+        """(M,) the members' tracer diffusivities (StokesSimulation.tracer_diffusivity per member)."""
+        return np.array([self.ctx.tracer_diffusion(m)[0] for m in range(self.M)])
+
+    @property
+    def tracer_seed(self):
+        """(M,) uint64: the members' random seeds."""
+        return np.array([self.ctx.tracer_diffusion(m)[1] for m in range(self.M)], dtype=np.uint64)
 
     @property
     def u_advected(self):
@@ -1109,15 +1193,17 @@ class StokesEnsemble:
 
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
-                   inertia=False, advection="sl"):
+                   inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  advection: 'sl' only (ensembles have no MacCormack
-    step)."""
+    step).  tracer_diffusivity, tracer_seed: one value for all members or one per member
+    (StokesEnsemble.set_tracer_diffusion)."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
-    ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia)
+    ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia, tracer_diffusivity=tracer_diffusivity,
+                         tracer_seed=tracer_seed)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
@@ -1254,7 +1340,8 @@ class Result:
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
-          tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl"):
+          tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
+          tracer_seed=0):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -1264,7 +1351,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     inertia (schemes 'color' and 'food'): every step advects the velocity by itself in front of the viscous solve
     (StokesSimulation.inertia).  advection 'sl' | 'maccormack' (schemes 'color' and 'food'): the first-order
     semi-Lagrangian transport of the reference, or the limited MacCormack scheme (second order) for the dye of a
-    'color' run and the velocity of an inertial one (StokesSimulation.dye_advection / velocity_advection)."""
+    'color' run and the velocity of an inertial one (StokesSimulation.dye_advection / velocity_advection).
+    tracer_diffusivity, tracer_seed (schemes 'color' and 'food'): Brownian tracers, a random walk of that diffusivity
+    per tracer and step on top of the move, reproducible from the seed (StokesSimulation.tracer_diffusivity)."""
+    if (tracer_diffusivity != 0.0 or tracer_seed != 0) and scheme not in ("color", "food"):
+        raise ValueError("tracer_diffusivity belongs to the Stokes schemes 'color' and 'food'")
     if advection_scheme(advection) and scheme not in ("color", "food"):
         raise ValueError("advection belongs to the Stokes schemes 'color' and 'food'")
     if dyes is not None and scheme != "color":
@@ -1274,7 +1365,8 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     if scheme in ("color", "food"):
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
-        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection)
+        sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection,
+                               tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed)
         if dyes is not None:
             sim.dyes = dyes
         st = sim.step(steps) if steps else []
