@@ -148,6 +148,15 @@ enum pucfem_field {
   /* u_a (N,2) of the last inertial step, read only (setting it is PUCFEM_EINVAL): the velocity the viscous solve
      took as its right-hand side, see "inertia" below.  PUCFEM_ESTATE before the first inertial step. */
   PUCFEM_F_U_ADV = 14,
+  /* the total body force f (N,2) of the current state, read only (setting it is PUCFEM_EINVAL): formed on the device
+     when read, as the vorticity is, see "body forces" below; zeros with no force set.  On a partitioned context
+     pucfem_get_field serves the rank's owned rows.  (This and the next enumerator count on from PUCFEM_F_U_ADV:
+     15 and 16.) */
+  PUCFEM_F_FORCE,
+  /* r (N,2) of the last forced step, read only (setting it is PUCFEM_EINVAL): what its viscous solve took as its
+     right-hand side, see "body forces" below.  PUCFEM_ESTATE before the first forced step.  Owned rows on a
+     partitioned context. */
+  PUCFEM_F_U_RHS,
   /* channel k is field PUCFEM_F_DYE0 + k (N values, k < K) */
   PUCFEM_F_DYE0 = 64
 };
@@ -356,6 +365,80 @@ int pucfem_ens_set_inertia(void* ctx, int32_t member /* -1 = all */, int32_t on)
 /* member 0 .. members - 1: out[0] on, [1] inertial steps since the member was switched on, [2] not-found rows of its
    last inertial launch (summed on the device; 0 before the first), [3] device bytes the ensemble holds for inertia */
 int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4);
+
+/* ---- body forces: driven channel flow and buoyant dye ---- */
+/* The reference forms the viscous right-hand side as u + DT * b_force (StokesColor.py:485-486, 540-541,
+   StokesFood.py:405-406, 444-445) and its experiments set b_force[:, 0] = 0.1, a mean pressure gradient in the
+   x-periodic channel.  With a force set, every pucfem_step forms, for owned row i, every product and sum as written
+   (base: what the viscous solve takes without a force -- u^n, or u_a with inertia on):
+     f = (0, 0)
+     constant F given:      f = F
+     nodal field fn given:  f = f + fn[i]                       (per component; if no F was given, f = fn[i])
+     buoyancy given:        b = beta_0 * (s_0[i] - ref_0)
+                            for t = 1 .. nterms - 1:  b = b + beta_t * (s_t[i] - ref_t)
+                            f = (f.x + g.x * b, f.y + g.y * b)
+     r[i] = (base[i].x + dt * f.x,  base[i].y + dt * f.y)
+   Terms that are not given are skipped, not added as zeros.  s_t is c or a dye channel as it stands at the start of
+   the step (c^n: Boussinesq buoyancy, the dye pushes back).  r replaces base wherever the viscous solve reads it: as
+   its right-hand side and as the base of its start and of its increments.  Nothing else in the step changes: the
+   boundary rows of u* are overwritten as before, so a force at a Dirichlet node has no effect.  On the direct-solve
+   paths a forced step holds, bit for bit, what an unforced step computes after
+   pucfem_set_field(PUCFEM_F_U, pucfem_force_apply(u, dt)); PUCFEM_F_U_ADV still holds u_a without the force.
+   PUCFEM_STOKES_COLOR (either dye scheme) and PUCFEM_STOKES_FOOD contexts after pucfem_build_operators, on every
+   solver path, with or without inertia, dye channels, MacCormack advection and Brownian tracers.  The uniform and
+   the nodal force are element-wise on the rows a rank owns and also run on partitioned contexts (every rank sets the
+   same force; the field is N x 2 on every rank).  Buoyancy reads the dye the previous step's tail wrote: such steps
+   wait for that tail in front of the viscous solve instead of overlapping it, and a partitioned context, whose tail
+   runs behind the next viscous solve, refuses buoyancy.
+   pucfem_set_force with both pointers NULL, or F = (0, 0) and no field, switches that part off; with every part off
+   the step is the one without these calls, launch for launch.  The buffers (r, the nodal field; owned rows x 2) are
+   allocated when first needed; pucfem_build_operators and pucfem_ctx_destroy free them and switch every force off.
+   Setting or clearing a force resets the viscous solve's extrapolation history, as setting u does.  A small-mesh
+   context steps from its captured graph only while no force is set; with one it runs the same launches uncaptured
+   behind k_force_rhs.  The context's setting is for pucfem_step alone; ensembles carry their own settings, one per
+   member (pucfem_ens_set_force / pucfem_ens_set_buoyancy below), and the two stay apart.
+   PUCFEM_EINVAL: a non-finite value.  PUCFEM_ESTATE: before the build; heat and Poisson contexts.  PUCFEM_ENODEV on
+   a host-only context. */
+int pucfem_set_force(void* ctx, const double* F2 /* or NULL */, const double* field /* N x 2, caller numbering, or NULL */);
+/* fields[t]: PUCFEM_F_C or PUCFEM_F_DYE0 + k; nterms = 0: off (the other arguments may then be NULL).
+   PUCFEM_EINVAL: nterms outside 0 .. 17, a non-finite g, beta or ref, an unknown or repeated field.  PUCFEM_ESTATE:
+   before the build, heat and Poisson contexts, PUCFEM_STOKES_FOOD (it has no dye), partitioned contexts, a channel
+   k >= K.  Removing or redefining the channels (PUCFEM_F_DYES) while a term names one switches buoyancy off. */
+int pucfem_set_buoyancy(void* ctx, const double* g2, int32_t nterms, const int32_t* fields, const double* beta,
+                        const double* ref);
+/* Body forces per ensemble member: a sweep over the background flow's strength against the neutral swimmer, the pusher
+   and the puller, or a buoyant dye per member, in one launch chain.  A forced member steps r = base + dt * f (base:
+   its u, or its u_a when its inertia flag is on) and then the ensemble's step with r as the viscous product's input:
+   bit for bit a pucfem_step run with the same setting and the member's boundary values.  A member with no force
+   steps as without these calls.  Settings may differ between members; one set between two pucfem_ens_step calls takes
+   effect at the next step and starts the member's count again.  F2 NULL or (0, 0) and field NULL switch those parts
+   off; field is one N x 2 array (caller numbering) given to every requested member.  Members have c only: their
+   buoyancy is one term, f += g * beta * (c - ref); g2 NULL switches it off.  The step stays one captured chain,
+   with k_ens_force_rhs in front of the viscous product while at least one member is forced; it is captured again only
+   when that changes and when the nodal planes are first allocated (which members are forced, and how, the kernel
+   reads from device memory).  The members' r (members x N x 2), masks and parameters (members x 8 doubles) are
+   allocated when a member is first forced, the nodal planes (members x N x 2) when one is first given a field; they
+   are counted in pucfem_ens_info's bytes and freed with the ensemble.
+   member = -1: every member.  PUCFEM_ESTATE without an ensemble (and for buoyancy on PUCFEM_STOKES_FOOD);
+   PUCFEM_EINVAL for a member out of range and for a non-finite value.
+   pucfem_ens_get_field serves PUCFEM_F_FORCE (every member's f of the current state, zeros for an unforced member)
+   and PUCFEM_F_U_RHS (PUCFEM_ESTATE when a requested member has taken no forced step since its setting last
+   changed). */
+int pucfem_ens_set_force(void* ctx, int32_t member /* -1 = all */, const double* F2, const double* field /* N x 2 or NULL */);
+int pucfem_ens_set_buoyancy(void* ctx, int32_t member, const double* g2, double beta, double ref);
+/* member = -1, the context: out[0] bit mask of the terms present (1 uniform, 2 nodal, 4 buoyancy), [1] forced steps
+   since the setting last changed, [2] buoyancy terms, [3] device bytes held.  member 0 .. members - 1: the same of an
+   ensemble member ([3]: the bytes the ensemble holds for forces); PUCFEM_ESTATE without an ensemble, PUCFEM_EINVAL for
+   a member out of range. */
+int pucfem_force_info(void* ctx, int32_t member, int64_t* out4);
+/* Unit operation: out = r from the context's current setting and current dye fields and the caller's base (N x 2)
+   and dt, through the step's kernel on scratch buffers; the step's state is not touched.  With no force set out is
+   base + dt * 0. */
+int pucfem_force_apply(void* ctx, const double* base, double dt, double* out);
+/* Measurement: the step's launch (base = the context's current u, its dt, a scratch output), launched once untimed and
+   then `iters` times back to back between two events.  out2[0]: milliseconds per launch; out2[1]: algorithmic bytes
+   per launch (32 per row, 16 more with a nodal field, 8 more per buoyancy term). */
+int pucfem_force_probe(void* ctx, int32_t iters, double* out2);
 
 /* ---- Brownian tracers: food that diffuses ---- */
 /* The tracers are deterministic points; in the steady flow a run settles to, a tracer on a streamline outside the

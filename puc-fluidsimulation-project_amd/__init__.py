@@ -11,11 +11,11 @@ The directory name contains hyphens, so import it with
 from ._lib import PucfemError, device_count, lib as _load_library  # noqa: F401
 from .mesh import (Mesh, boundary_sets, filter_wall_pairs, find_boundary_pairs, load_mesh, readEle,  # noqa: F401
                    readNode, readPoly, writeEle, writeNode, writePoly)
-from .ops import (advect_maccormack, advect_maccormack_vector, advect_semilagrange, advect_semilagrange_multi, advect_semilagrange_vector, buildLumpedMassMatrix,  # noqa: F401
+from .ops import (advect_maccormack, advect_maccormack_vector, advect_semilagrange, advect_semilagrange_multi, advect_semilagrange_vector, apply_body_force, buildLumpedMassMatrix,  # noqa: F401
                   buildStiffnessMatrix, calculate_divergence, build_mass_and_convection_mass, calculate_gradiant,
                   calculate_vorticity, dye_implicit_step,
                   makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous)
-from .solver import (SAMPLE_FIELDS, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
+from .solver import (SAMPLE_FIELDS, Buoyancy, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
                      StokesSimulation, Streamlines, Tolerances, dye_patterns, ensemble_dirichlet_values,
                      pixel_centres, poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401

@@ -11,7 +11,7 @@ SRC = ["csrc/pucfem_api.hip", "csrc/pucfem_host.cpp"]
 DEPS = SRC + ["csrc/pucfem_host.hpp", "csrc/pucfem_kernels.hpp", "csrc/pucfem_kernels_impl.hpp",
               "csrc/pucfem_comm.hpp", "csrc/pucfem_lattice.hpp", "csrc/pucfem_locate.hpp", "csrc/pucfem_ensemble.hpp",
               "csrc/pucfem_sample.hpp", "csrc/pucfem_streamline.hpp",
-              "csrc/pucfem_dye_channels.hpp", "csrc/pucfem_inertia.hpp",
+              "csrc/pucfem_dye_channels.hpp", "csrc/pucfem_inertia.hpp", "csrc/pucfem_force.hpp",
               "csrc/pucfem_maccormack.hpp", "csrc/pucfem_brownian.hpp"]
 
 

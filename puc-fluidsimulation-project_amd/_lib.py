@@ -22,6 +22,9 @@ F_VORTICITY = 12
 F_DYES = 13  # all dye channels (K, N); channel k is field F_DYE0 + k
 F_DYE0 = 64
 F_U_ADV = 14  # u_a (N, 2) of the last inertial step, read only
+F_FORCE = 15  # the total body force f (N, 2) of the current state, read only
+F_U_RHS = 16  # r (N, 2) of the last forced step, read only
+FORCE_UNIFORM, FORCE_NODAL, FORCE_BUOYANCY = 1, 2, 4  # pucfem_force_info: the terms present (a mask)
 MAX_DYES = 16
 ADV_DYE, ADV_VELOCITY = 1, 2  # pucfem_set_advection: what (a mask)
 ADV_SL, ADV_MACCORMACK = 0, 1  # ... and the scheme
@@ -117,6 +120,13 @@ SIGNATURES = {
     "pucfem_inertia_probe": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_ens_set_inertia": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_ens_inertia_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_set_force": ([_P, _D, _D], ct.c_int),
+    "pucfem_set_buoyancy": ([_P, _D, ct.c_int32, _I32, _D, _D], ct.c_int),
+    "pucfem_ens_set_force": ([_P, ct.c_int32, _D, _D], ct.c_int),
+    "pucfem_ens_set_buoyancy": ([_P, ct.c_int32, _D, ct.c_double, ct.c_double], ct.c_int),
+    "pucfem_force_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_force_apply": ([_P, _D, ct.c_double, _D], ct.c_int),
+    "pucfem_force_probe": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_set_tracer_diffusion": ([_P, ct.c_double, ct.c_uint64], ct.c_int),
     "pucfem_ens_set_tracer_diffusion": ([_P, ct.c_int32, ct.c_double, ct.c_uint64], ct.c_int),
     "pucfem_get_tracer_diffusion": ([_P, ct.c_int32, _D, ct.POINTER(ct.c_uint64)], ct.c_int),

@@ -31,6 +31,7 @@
 #include "pucfem_streamline.hpp"
 #include "pucfem_dye_channels.hpp"
 #include "pucfem_inertia.hpp"
+#include "pucfem_force.hpp"
 #include "pucfem_maccormack.hpp"
 
 using namespace pucfem;
@@ -163,6 +164,18 @@ struct Ens {
   bool adv_stale = true;
   int adv_any = 0;                 // members with their flag on
   bool chain_adv = false;          // the captured graphs hold the inertial launch
+  // body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy; k_ens_force_rhs), allocated when a member
+  // is first forced and kept: the members' r (M x 2n), their term masks (M) and parameters (M x ENS_FORCE_PARM) as
+  // the kernel reads them; the nodal planes (M x 2n) when a member is first given a field
+  double *frhs = nullptr, *fparm = nullptr, *fnod = nullptr;
+  int32_t* fmask_dev = nullptr;
+  size_t force_bytes = 0;
+  std::vector<int32_t> fmask;      // the masks (empty: never forced)
+  std::vector<double> fpar;        // the parameters
+  std::vector<int64_t> fsteps;     // per member: forced steps since its setting last changed
+  int force_any = 0;               // members with a force
+  bool chain_force = false;        // the captured graphs hold the force launch ...
+  bool chain_fnod = false;         // ... with the nodal planes' pointer
   // Brownian tracers per member (pucfem_ens_set_tracer_diffusion; the BROWN tracer kernels), allocated when a member
   // is first switched on and kept: the members' amplitudes sqrt(6 D dt) and Philox keys as the kernels read them (M
   // each); a[m] == 0 is the plain move
@@ -834,6 +847,7 @@ struct Ctx {
       for (void* a : allocs) (void)hipFree(a);
       drop_dyes();
       drop_inertia();
+      drop_force();
       drop_advection();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
@@ -1176,6 +1190,11 @@ struct Ctx {
   // K channels from buf (K x N, the caller's numbering); K = 0 removes them
   void set_dyes(int K, const double* buf) {
     const i64 N = mesh.N;
+    for (int t = 0; t < b_n; ++t)
+      if (b_field[t] != PUCFEM_F_C) {  // (a buoyancy term names a channel being removed or redefined: buoyancy off)
+        b_n = 0;
+        force_changed();
+      }
     if (K != ndye) {
       drop_dyes();
       if (K > 0) {
@@ -1285,6 +1304,122 @@ struct Ctx {
   }
   size_t inertia_dev_bytes() const {
     return u_adv ? sizeof(double) * 2 * (size_t)mesh.N + sizeof(int32_t) * SLB : 0;
+  }
+
+  // ------------------------------------------------------------------ body forces (pucfem_force.hpp)
+  // With a force set, stokes_step forms r = base + dt * f (base: u^n, or u_a with inertia on) behind inertia_step and
+  // in front of the viscous solve, which then reads r wherever it read base.  u_rhs is one interleaved buffer over the
+  // owned rows, allocated when a force is first set and freed by drop_force (it is not in `allocs`), as the nodal
+  // field is: a context that never sets a force holds no new memory and launches nothing new.
+  bool f_uni = false;
+  double f_F[2] = {0.0, 0.0};
+  double* f_nodal = nullptr;  // the nodal field's pairs, owned rows in the internal numbering (null: none)
+  int b_n = 0;                // buoyancy terms (0: off)
+  int32_t b_field[FORCE_MAX_TERMS] = {};
+  double b_beta[FORCE_MAX_TERMS] = {}, b_ref[FORCE_MAX_TERMS] = {}, b_g[2] = {0.0, 0.0};
+  double* u_rhs = nullptr;
+  bool rhs_valid = false;  // u_rhs holds the r of a forced step
+  i64 force_steps = 0;     // forced steps since the setting last changed
+  int force_mask() const { return (f_uni ? 1 : 0) | (f_nodal ? 2 : 0) | (b_n ? 4 : 0); }
+  bool forced() const { return force_mask() != 0; }
+  // a built Stokes context (checked before the device is asked for)
+  void force_ready() const {
+    need_built();
+    if (scheme != PUCFEM_STOKES_COLOR && scheme != PUCFEM_STOKES_FOOD)
+      throw Error(PUCFEM_ESTATE, "body forces need a Stokes context");
+  }
+  // buoyancy reads the dye at the start of the step: a single-rank STOKES_COLOR context (a partitioned one finishes
+  // step n's dye behind step n + 1's viscous solve, dye_tail_dist)
+  void buoyancy_ready() const {
+    force_ready();
+    if (scheme != PUCFEM_STOKES_COLOR) throw Error(PUCFEM_ESTATE, "buoyancy needs a STOKES_COLOR context: STOKES_FOOD has no dye");
+    if (dist() || world != 1)
+      throw Error(PUCFEM_ESTATE, "buoyancy is single-rank (a partitioned step's dye is finished after the next viscous solve)");
+  }
+  double force_launch_bytes(int mask, int nterms, i64 n) const {
+    return (32.0 + ((mask & 2) ? 16.0 : 0.0) + ((mask & 4) ? 8.0 * nterms : 0.0)) * (double)n;
+  }
+  // the current setting as the kernel takes it (the dye pointers as they stand now: call after sl_join)
+  ForceTerms force_terms() const {
+    ForceTerms T{};
+    T.fx = f_F[0];
+    T.fy = f_F[1];
+    T.gx = b_g[0];
+    T.gy = b_g[1];
+    T.nterms = b_n;
+    for (int t = 0; t < b_n; ++t) {
+      T.s[t] = b_field[t] == PUCFEM_F_C ? c_full + lp.r0 : dye_cur + (size_t)(b_field[t] - PUCFEM_F_DYE0) * (size_t)mesh.N;
+      T.beta[t] = b_beta[t];
+      T.ref[t] = b_ref[t];
+    }
+    return T;
+  }
+  // k_force_rhs over the owned rows on the current stream: out = base + dt * f (RHS), or f itself
+  template <bool RHS>
+  void force_launch(const double* base2, double dt, double* out2) {
+    const i64 n = lp.n_own;
+    const int mask = force_mask();
+    const ForceTerms T = force_terms();
+    const dbl2* base = reinterpret_cast<const dbl2*>(base2);
+    const dbl2* fn = reinterpret_cast<const dbl2*>(f_nodal);
+    dbl2* out = reinterpret_cast<dbl2*>(out2);
+    const double bytes = force_launch_bytes(mask, b_n, n) - (RHS ? 0.0 : 16.0 * (double)n);
+    auto go = [&](auto uni, auto nod, auto buo) {
+      klaunch(-1, bytes, k_force_rhs<decltype(uni)::value, decltype(nod)::value, decltype(buo)::value, RHS>,
+              dim3(grid_ew(n)), dim3(BS), (int64_t)n, base, dt, fn, T, out);
+    };
+    using Y = std::true_type;
+    using N = std::false_type;
+    switch (mask) {
+      case 0: go(N{}, N{}, N{}); break;  // (f = 0: PUCFEM_F_FORCE and pucfem_force_apply with nothing set)
+      case 1: go(Y{}, N{}, N{}); break;
+      case 2: go(N{}, Y{}, N{}); break;
+      case 3: go(Y{}, Y{}, N{}); break;
+      case 4: go(N{}, N{}, Y{}); break;
+      case 5: go(Y{}, N{}, Y{}); break;
+      case 6: go(N{}, Y{}, Y{}); break;
+      default: go(Y{}, Y{}, Y{}); break;
+    }
+    KCHK();
+  }
+  // the forced part of a step, on the main stream behind inertia_step.  Buoyancy reads c^n, which the previous step's
+  // overlapped dye tail writes on the side stream: the main stream joins it first (and c_full is read after the join:
+  // the tail swapped c_full / c_new when it was queued)
+  void force_step() {
+    if (!forced()) return;
+    if (b_n) sl_join();
+    force_launch<true>(inertia ? u_adv : ux, prm.dt, u_rhs);
+    ++force_steps;
+    rhs_valid = true;
+  }
+  void force_alloc() {
+    if (u_rhs) return;
+    const size_t bytes = sizeof(double) * 2 * (size_t)std::max<i64>(1, lp.n_own);
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&u_rhs), bytes));
+    HIPCHK(hipMemsetAsync(u_rhs, 0, bytes, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  // a setting changed: the counts start again and the viscous solve's right-hand side changes its meaning
+  void force_changed() {
+    force_steps = 0;
+    have_vinc = 0;
+    if (forced()) force_alloc();
+  }
+  void drop_force() {
+    f_uni = false;
+    f_F[0] = f_F[1] = 0.0;
+    b_n = 0;
+    force_steps = 0;
+    rhs_valid = false;
+    if (!u_rhs && !f_nodal) return;
+    if (st) (void)hipStreamSynchronize(st);
+    for (void* q : {(void*)u_rhs, (void*)f_nodal})
+      if (q) (void)hipFree(q);
+    u_rhs = f_nodal = nullptr;
+  }
+  size_t force_dev_bytes() const {
+    const size_t plane = sizeof(double) * 2 * (size_t)std::max<i64>(1, lp.n_own);
+    return (u_rhs ? plane : 0) + (f_nodal ? plane : 0);
   }
 
   // ------------------------------------------------------------------ MacCormack advection (pucfem_maccormack.hpp)
@@ -2703,8 +2838,8 @@ struct Ctx {
   int viscous(int& iters) {  // StokesColor.py:540-547
     const i64 n = lp.n_own;
     // the right-hand side and the base of the start and of the increments: u^n, or with inertia on the advected u_a
-    // (inertia_step ran in front)
-    const double *rx = inertia ? u_adv : ux, *ry = rx + 1;
+    // (inertia_step ran in front); with a body force r = that + dt * f (force_step ran behind it)
+    const double *rx = forced() ? u_rhs : inertia ? u_adv : ux, *ry = rx + 1;
     if (dense) {  // u* = A_visc^-1 (u + DT * 0)
       if (dbcsrc && dir_ncomp == 2) {  // (velocity BCs: both components copied / set)
         hipLaunchKernelGGL(k_dense_mv2_bc, dim3((int)std::min<i64>(2048, (n + 3) / 4)), dim3(BS), 0, st, n, dVinv, rx,
@@ -3331,6 +3466,7 @@ struct Ctx {
     int itv = 0;
     ring_in_mix = false;
     inertia_step();  // (reads u, as the previous step's dye tail on the side stream does: no join)
+    force_step();    // (buoyancy reads c^n: it joins the tail)
     viscous(itv);
     dye_tail_dist();  // (W > 1: the previous step's dye tail)
     // max |div u*| -> vals[0]; the div u* field itself is computed when read (pucfem_get_field): nothing in the
@@ -5506,6 +5642,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     c.drop_step_graphs();
     if (!c.host_only) c.drop_dyes();
     if (!c.host_only) c.drop_inertia();
+    if (!c.host_only) c.drop_force();
     if (!c.host_only) c.drop_advection();
     build(c);
   });
@@ -5636,6 +5773,21 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
         require(count == 2 * N, "field is (N, 2)");
         c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)c.u_adv, (const double*)nullptr, false);
         break;
+      case PUCFEM_F_FORCE: {  // (the total f of the current state, formed when read; the owned rows)
+        c.force_ready();
+        require(count == 2 * N, "field is (N, 2)");
+        double* s = c.smp_scratch<double>(15, 2 * (size_t)no);
+        c.sl_join();
+        c.force_launch<false>(nullptr, 0.0, s);
+        c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)s, (const double*)nullptr, false);
+        break;
+      }
+      case PUCFEM_F_U_RHS:  // (the r of the last forced step)
+        c.force_ready();
+        if (!c.rhs_valid) throw Error(PUCFEM_ESTATE, "no forced step has been taken: u_rhs holds nothing");
+        require(count == 2 * N, "field is (N, 2)");
+        c.get(c.ord, c.lp.r0, no, 2, 1, buf, (const double*)c.u_rhs, (const double*)nullptr, false);
+        break;
       case PUCFEM_F_C:
         require(count == N, "c is (N,)");
         c.allgather_full(c.c_full);  // multi-rank: collective (every rank reads c), the full field
@@ -5672,8 +5824,9 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       std::vector<int32_t> its(3 * (size_t)nsteps);
       // (a context with dye channels steps uncaptured: the channels' buffers swap every step; so does one with
       // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step; so does one
-      // whose dye moves by MacCormack steps)
-      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye) {
+      // whose dye moves by MacCormack steps, and one with a body force: the same launches behind k_force_rhs, whose
+      // by-value terms and dye pointers change between steps)
+      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced()) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -5843,11 +5996,24 @@ void ens_enqueue_step(Ctx& c) {
                        e.part_adv, ra);
     KCHK();
   }
+  // with at least one member forced: r = base + dt * f of those members behind it (Ctx::force_step), and the viscous
+  // product stages r for them.  c holds c^n: k_ens_mix2 of the previous step wrote it earlier in this chain
+  const bool forced = e.force_any > 0;
+  if (forced) {
+    hipLaunchKernelGGL(k_ens_force_rhs<true>, dim3(Ctx::grid_ew(n), M), dim3(BS), 0, st, (int64_t)n,
+                       (const int32_t*)e.fmask_dev, (const double*)e.fparm, reinterpret_cast<const dbl2*>(e.fnod),
+                       reinterpret_cast<const dbl2*>(e.u), reinterpret_cast<const dbl2*>(e.ua),
+                       adv ? (const int32_t*)e.adv_on_dev : (const int32_t*)nullptr, (const double*)e.c, c.prm.dt,
+                       reinterpret_cast<dbl2*>(e.frhs));
+    KCHK();
+  }
   hipLaunchKernelGGL(k_ens_mv2_bc<ENS_TM>, dim3(e.gx_dense, tiles), dim3(BS), e.lds_mv, st, (int64_t)n, M,
                      (const double*)c.dVinv, (const double*)e.u, e.us, (const int32_t*)c.dbcsrc,
                      (const int32_t*)c.dbcdir, (const double*)e.dval, (int64_t)e.dstride,
                      adv ? (const double*)e.ua : (const double*)nullptr,
-                     adv ? (const int32_t*)e.adv_on_dev : (const int32_t*)nullptr);
+                     adv ? (const int32_t*)e.adv_on_dev : (const int32_t*)nullptr,
+                     forced ? (const double*)e.frhs : (const double*)nullptr,
+                     forced ? (const int32_t*)e.fmask_dev : (const int32_t*)nullptr);
   KCHK();
   // max |div| into vals slot `slot`; with rhs the pressure right-hand side and its sum (slot 9)
   auto div = [&](const double* u, int slot, bool rhs) {
@@ -5962,12 +6128,18 @@ EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
     case PUCFEM_F_U_ADV:  // (read only: the members' u_a of their last inertial step)
       if (!e.ua) throw Error(PUCFEM_ESTATE, "no member has taken an inertial step: u_adv holds nothing");
       return {e.ua, 2 * e.n, 2};
+    case PUCFEM_F_U_RHS:  // (read only: the members' r of their last forced step)
+      if (!e.frhs) throw Error(PUCFEM_ESTATE, "no member has taken a forced step: u_rhs holds nothing");
+      return {e.frhs, 2 * e.n, 2};
+    case PUCFEM_F_FORCE:  // (read only, formed when read into the context's scratch: pucfem_ens_get_field)
+      return {c.smp_scratch<double>(15, 2 * (size_t)e.n * (size_t)e.M), 2 * e.n, 2};
     case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
     case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
     case PUCFEM_F_CAPTURE_STEP: return {nullptr, (i64)e.ntr, 0};
     default:
       throw Error(PUCFEM_EINVAL,
-                  "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, U_ADV, TRACERS, STATUS, CAPTURE_STEP)");
+                  "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, U_ADV, FORCE, U_RHS, TRACERS, STATUS, "
+                  "CAPTURE_STEP)");
   }
 }
 }  // namespace
@@ -6150,6 +6322,83 @@ int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4) {
   });
 }
 
+// ---- body forces per member (k_ens_force_rhs, pucfem_force.hpp)
+namespace {
+// the members' force buffers, allocated when a member is first forced; the nodal planes when first needed
+void ens_force_bufs(Ctx& c, Ens& e, bool nodal) {
+  const size_t sM = (size_t)e.M, before = e.bytes;
+  if (e.fmask.empty()) {
+    e.frhs = e.alloc<double>(sM * 2 * e.n, c.st);
+    e.fparm = e.alloc<double>(sM * ENS_FORCE_PARM, c.st);
+    e.fmask_dev = e.alloc<int32_t>(sM, c.st);
+    e.fmask.assign(sM, 0);
+    e.fpar.assign(sM * ENS_FORCE_PARM, 0.0);
+    e.fsteps.assign(sM, 0);
+  }
+  if (nodal && !e.fnod) e.fnod = e.alloc<double>(sM * 2 * e.n, c.st);
+  e.force_bytes += e.bytes - before;
+}
+// the members' settings to the device (the stream is idle between two pucfem_ens_step calls)
+void ens_force_upload(Ctx& c, Ens& e) {
+  e.force_any = (int)std::count_if(e.fmask.begin(), e.fmask.end(), [](int32_t k) { return k != 0; });
+  c.h2d(e.fmask_dev, e.fmask.data(), sizeof(int32_t) * e.fmask.size());
+  c.h2d(e.fparm, e.fpar.data(), sizeof(double) * e.fpar.size());
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+}  // namespace
+
+int pucfem_ens_set_force(void* ctx, int32_t member, const double* F2, const double* field) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    if (F2) require(std::isfinite(F2[0]) && std::isfinite(F2[1]), "the force must be finite");
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const i64 N = c.mesh.N;
+    if (field) {
+      bool ok = true;
+      for (i64 k = 0; k < 2 * N && ok; ++k) ok = std::isfinite(field[k]);
+      require(ok, "the force field must be finite");
+    }
+    const bool uni = F2 && (F2[0] != 0.0 || F2[1] != 0.0);
+    if (e.fmask.empty() && !uni && !field) return;  // (nothing was ever set: nothing to switch off)
+    ens_force_bufs(c, e, field != nullptr);
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? (size_t)e.M : m0 + 1;
+    for (size_t m = m0; m < m1; ++m) {
+      e.fmask[m] = (e.fmask[m] & 4) | (uni ? 1 : 0) | (field ? 2 : 0);
+      e.fpar[m * ENS_FORCE_PARM + 0] = uni ? F2[0] : 0.0;
+      e.fpar[m * ENS_FORCE_PARM + 1] = uni ? F2[1] : 0.0;
+      e.fsteps[m] = 0;
+      if (field) c.put_all(2, 1, field, e.fnod + m * 2 * (size_t)e.n);  // (one N x 2 field, every requested member)
+    }
+    ens_force_upload(c, e);
+  });
+}
+
+int pucfem_ens_set_buoyancy(void* ctx, int32_t member, const double* g2, double beta, double ref) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    if (g2) require(std::isfinite(g2[0]) && std::isfinite(g2[1]) && std::isfinite(beta) && std::isfinite(ref),
+                    "g, beta and ref must be finite");
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    if (g2 && c.scheme != PUCFEM_STOKES_COLOR)
+      throw Error(PUCFEM_ESTATE, "buoyancy needs a STOKES_COLOR context: STOKES_FOOD has no dye");
+    if (e.fmask.empty() && !g2) return;
+    ens_force_bufs(c, e, false);
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? (size_t)e.M : m0 + 1;
+    for (size_t m = m0; m < m1; ++m) {
+      e.fmask[m] = (e.fmask[m] & 3) | (g2 ? 4 : 0);
+      double* q = e.fpar.data() + m * ENS_FORCE_PARM;
+      q[2] = g2 ? g2[0] : 0.0;
+      q[3] = g2 ? g2[1] : 0.0;
+      q[4] = g2 ? beta : 0.0;
+      q[5] = g2 ? ref : 0.0;
+      e.fsteps[m] = 0;
+    }
+    ens_force_upload(c, e);
+  });
+}
+
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
@@ -6158,6 +6407,7 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     require(field != PUCFEM_F_CAPTURE_STEP, "capture steps cannot be set");
     require(field != PUCFEM_F_VORTICITY, "the vorticity cannot be set");
     require(field != PUCFEM_F_U_ADV, "u_adv cannot be set: it is the inertial step's own output");
+    require(field != PUCFEM_F_FORCE && field != PUCFEM_F_U_RHS, "the force and u_rhs cannot be set: they are formed");
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
@@ -6184,6 +6434,21 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
       for (i64 m = m0; m < m0 + nm; ++m)
         if (e.adv_steps[(size_t)m] == 0)
           throw Error(PUCFEM_ESTATE, "a requested member has taken no inertial step since it was switched on");
+    if (field == PUCFEM_F_U_RHS)  // (every requested member's plane must hold the r of a step of its own)
+      for (i64 m = m0; m < m0 + nm; ++m)
+        if (e.fsteps[(size_t)m] == 0)
+          throw Error(PUCFEM_ESTATE, "a requested member has taken no forced step since its setting last changed");
+    if (field == PUCFEM_F_FORCE) {  // (the members' f of the current state, every member's plane: zeros if unforced)
+      if (e.fmask.empty()) {
+        HIPCHK(hipMemsetAsync(f.a, 0, sizeof(double) * (size_t)(e.M * f.per), c.st));
+      } else {
+        hipLaunchKernelGGL(k_ens_force_rhs<false>, dim3(Ctx::grid_ew(e.n), e.M), dim3(BS), 0, c.st, (int64_t)e.n,
+                           (const int32_t*)e.fmask_dev, (const double*)e.fparm, reinterpret_cast<const dbl2*>(e.fnod),
+                           (const dbl2*)nullptr, (const dbl2*)nullptr, (const int32_t*)nullptr, (const double*)e.c,
+                           0.0, reinterpret_cast<dbl2*>(f.a));
+        KCHK();
+      }
+    }
     if (f.per == 0) return;
     if (field == PUCFEM_F_CAPTURE_STEP) return capture_steps_get(c, e.trcap, m0 * e.ntr, nm * e.ntr, buf);
     if (field == PUCFEM_F_TRACERS) return tracers_get(c, e.trx, e.try_, m0 * e.ntr, nm * e.ntr, buf);
@@ -6219,11 +6484,15 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     // (the chain has the inertial launch iff a member's flag is on: graphs of the other chain are dropped.  Which
     // members are on is read from device memory by the kernels, so it needs no new capture.)
     // (the same for the tracers' diffusion: the BROWN tracer launch iff a member's D is positive)
-    if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0)) {
+    // (and for the body forces: the force launch iff a member is forced, with the nodal planes once they exist)
+    if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0) || e.chain_force != (e.force_any > 0) ||
+        e.chain_fnod != (e.fnod != nullptr)) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
       e.chain_adv = e.adv_any > 0;
       e.chain_br = e.br_any > 0;
+      e.chain_force = e.force_any > 0;
+      e.chain_fnod = e.fnod != nullptr;
     }
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
@@ -6254,6 +6523,8 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
         if (e.adv_on[m]) e.adv_steps[m] += nsteps;
       e.adv_stale = true;
     }
+    for (size_t m = 0; m < sM && e.force_any > 0; ++m)
+      if (e.fmask[m]) e.fsteps[m] += nsteps;
     if (stats)
       for (size_t k = 0; k < (size_t)nsteps * sM; ++k) {
         pucfem_step_stats& o = stats[k];
@@ -7135,6 +7406,133 @@ int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2) {
     launch();  // (untimed: the first launch)
     out2[0] = time_launches(c, iters, launch);
     out2[1] = c.vel_launch_bytes(N);
+  });
+}
+
+// ---- body forces (pucfem_force.hpp)
+static_assert(PUCFEM_F_FORCE == 15 && PUCFEM_F_U_RHS == 16, "the fields' numbers are part of the ABI");
+namespace {
+bool finite2(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]); }
+}  // namespace
+
+int pucfem_set_force(void* ctx, const double* F2, const double* field) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    if (F2) require(finite2(F2), "the force must be finite");
+    c.force_ready();
+    const i64 N = c.mesh.N, no = c.lp.n_own;
+    if (field) {
+      bool ok = true;
+      for (i64 k = 0; k < 2 * N && ok; ++k) ok = std::isfinite(field[k]);
+      require(ok, "the force field must be finite");
+    }
+    c.need_dev();
+    const bool uni = F2 && (F2[0] != 0.0 || F2[1] != 0.0);
+    if (!uni && !field && !c.f_uni && !c.f_nodal) return;  // (off stays off: the step's state is not touched)
+    c.f_uni = uni;
+    c.f_F[0] = c.f_uni ? F2[0] : 0.0;
+    c.f_F[1] = c.f_uni ? F2[1] : 0.0;
+    if (field) {  // (the owned rows' pairs, in the internal numbering)
+      if (!c.f_nodal) HIPCHK(hipMalloc(reinterpret_cast<void**>(&c.f_nodal), sizeof(double) * 2 * (size_t)std::max<i64>(1, no)));
+      HIPCHK(hipStreamSynchronize(c.st));  // (a step still reading the old field)
+      c.put(c.ord, c.lp.r0, no, 2, 1, field, c.f_nodal);
+      HIPCHK(hipStreamSynchronize(c.st));
+    } else if (c.f_nodal) {
+      HIPCHK(hipStreamSynchronize(c.st));
+      (void)hipFree(c.f_nodal);
+      c.f_nodal = nullptr;
+    }
+    c.force_changed();
+  });
+}
+
+int pucfem_set_buoyancy(void* ctx, const double* g2, int32_t nterms, const int32_t* fields, const double* beta,
+                        const double* ref) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(nterms >= 0 && nterms <= FORCE_MAX_TERMS, "nterms must be in 0 .. 17 (c and PUCFEM_MAX_DYES channels)");
+    if (nterms > 0) {
+      require(g2 != nullptr && fields != nullptr && beta != nullptr && ref != nullptr, "null buoyancy arguments");
+      require(finite2(g2), "g must be finite");
+      for (int t = 0; t < nterms; ++t) {
+        require(std::isfinite(beta[t]) && std::isfinite(ref[t]), "beta and ref must be finite");
+        require(fields[t] == PUCFEM_F_C || (fields[t] >= PUCFEM_F_DYE0 && fields[t] < PUCFEM_F_DYE0 + DYE_MAX),
+                "a buoyancy field is PUCFEM_F_C or PUCFEM_F_DYE0 + k");
+        for (int q = 0; q < t; ++q) require(fields[q] != fields[t], "a buoyancy field is named twice");
+      }
+    }
+    c.buoyancy_ready();
+    for (int t = 0; t < nterms; ++t)
+      if (fields[t] != PUCFEM_F_C && fields[t] - PUCFEM_F_DYE0 >= c.ndye)
+        throw Error(PUCFEM_ESTATE, "a buoyancy term names a dye channel the context does not have");
+    c.need_dev();
+    if (nterms == 0 && c.b_n == 0) return;  // (off stays off)
+    c.b_n = nterms;
+    for (int t = 0; t < nterms; ++t) {
+      c.b_field[t] = fields[t];
+      c.b_beta[t] = beta[t];
+      c.b_ref[t] = ref[t];
+    }
+    c.b_g[0] = nterms ? g2[0] : 0.0;
+    c.b_g[1] = nterms ? g2[1] : 0.0;
+    c.force_changed();
+  });
+}
+
+int pucfem_force_info(void* ctx, int32_t member, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out4 != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.force_ready();
+    if (member >= 0) {  // (an ensemble member's own setting)
+      require(c.ens == nullptr || member < c.ens->M, "member index out of range");
+      Ens& e = *ens_of(c);
+      const bool have = !e.fmask.empty();
+      out4[0] = have ? e.fmask[(size_t)member] : 0;
+      out4[1] = have ? e.fsteps[(size_t)member] : 0;
+      out4[2] = have && (e.fmask[(size_t)member] & 4) ? 1 : 0;
+      out4[3] = (int64_t)e.force_bytes;
+      return;
+    }
+    c.need_dev();
+    out4[0] = c.force_mask();
+    out4[1] = c.force_steps;
+    out4[2] = c.b_n;
+    out4[3] = (int64_t)c.force_dev_bytes();
+  });
+}
+
+int pucfem_force_apply(void* ctx, const double* base, double dt, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(base != nullptr && out != nullptr, "null fields");
+    require(std::isfinite(dt), "dt must be finite");
+    c.force_ready();
+    c.need_dev();
+    const i64 no = c.lp.n_own;
+    double* din = c.smp_scratch<double>(14, 2 * (size_t)no);
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)no);
+    c.put(c.ord, c.lp.r0, no, 2, 1, base, din);
+    c.sl_join();
+    c.force_launch<true>(din, dt, dout);
+    c.get(c.ord, c.lp.r0, no, 2, 1, out, (const double*)dout);
+  });
+}
+
+int pucfem_force_probe(void* ctx, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    c.force_ready();
+    c.need_dev();
+    const i64 no = c.lp.n_own;
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)no);
+    c.sl_join();
+    auto launch = [&] { c.force_launch<true>(c.ux, c.prm.dt, dout); };
+    launch();  // (untimed: the first launch)
+    out2[0] = time_launches(c, iters, launch);
+    out2[1] = c.force_launch_bytes(c.force_mask(), c.b_n, no);
   });
 }
 

@@ -43,19 +43,23 @@ __device__ __forceinline__ RedOut ens_red(const RedOut& ro, int32_t m, double*& 
 // (component-major per member: consecutive lanes read consecutive doubles).  A ragged last tile computes its
 // missing members as copies of the last member and does not store them.  With inertia (advon non-null: the members'
 // flags) a member whose flag is set stages its plane of ua (M x 2n, k_ens_sl_vel's output) instead of its u: the
-// single path's viscous product takes u_a as its input.  The rows' accumulation is the same either way.
+// single path's viscous product takes u_a as its input.  With body forces (fmask non-null: the members' term masks)
+// a member whose mask is not 0 stages its plane of r (M x 2n, k_ens_force_rhs's output) instead.  The rows'
+// accumulation is the same either way.
 template <int TM>
 __global__ __launch_bounds__(BS) void k_ens_mv2_bc(int64_t n, int32_t M, const double* __restrict__ Ainv,
                                                    const double* __restrict__ u, double* __restrict__ us,
                                                    const int32_t* __restrict__ bsrc, const int32_t* __restrict__ bdir,
                                                    const double* __restrict__ dval, int64_t dstride,
-                                                   const double* __restrict__ ua, const int32_t* __restrict__ advon) {
+                                                   const double* __restrict__ ua, const int32_t* __restrict__ advon,
+                                                   const double* __restrict__ fr, const int32_t* __restrict__ fmask) {
   extern __shared__ __align__(16) double ens_xl[];
   const int32_t m0 = (int32_t)blockIdx.y * TM;
 #pragma unroll
   for (int t = 0; t < TM; ++t) {
     const int32_t mt = m0 + t < M ? m0 + t : M - 1;
-    const dbl2* x = reinterpret_cast<const dbl2*>(advon && advon[mt] ? ua : u) + (int64_t)mt * n;
+    const dbl2* x =
+        reinterpret_cast<const dbl2*>(fmask && fmask[mt] ? fr : advon && advon[mt] ? ua : u) + (int64_t)mt * n;
     for (int64_t j = threadIdx.x; j < n; j += BS) {
       const dbl2 q = x[j];
       ens_xl[(2 * t) * n + j] = q.x;

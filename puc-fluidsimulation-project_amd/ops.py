@@ -204,6 +204,47 @@ def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None):
     return nf.astype(bool)
 
 
+def apply_body_force(u, dt, nodes=None, triangles=None, force=None, buoyancy=None, c=None, dyes=None):
+    """The forced step's right-hand side r = u + dt * f (N, 2) (pucfem_force_apply, the step's kernel): force a pair,
+    an (N, 2) field or a (pair, field) tuple; buoyancy a Buoyancy whose terms read c (N,) and dyes (K, N).  The
+    products and sums in the order include/pucfem.h states, absent terms skipped.  Returns r; u is left alone."""
+    from .solver import Buoyancy, _force_args
+
+    if nodes is None or triangles is None:
+        m = _mesh_or_global(None)
+        nodes, triangles = m.coords, m.triangles
+    N = len(nodes)
+    base = np.ascontiguousarray(u, dtype=np.float64)
+    if base.shape != (N, 2):
+        raise ValueError(f"apply_body_force: u must have shape ({N}, 2)")
+    if isinstance(force, tuple) and len(force) == 2 and np.shape(force[1]) == (N, 2):
+        F, fn = force
+    else:
+        F, fn = _force_args(force, N)
+    if buoyancy is not None and not isinstance(buoyancy, Buoyancy):
+        raise ValueError("apply_body_force: buoyancy must be a Buoyancy or None")
+    ctx = context_for(nodes, triangles)
+    try:
+        if buoyancy is not None:
+            names = list(buoyancy.terms)
+            if "c" in names:
+                if c is None:
+                    raise ValueError("apply_body_force: the buoyancy reads c")
+                ctx.set_field(_lib.F_C, np.ascontiguousarray(c, dtype=np.float64).reshape(N))
+            if any(n != "c" for n in names):
+                if dyes is None:
+                    raise ValueError("apply_body_force: the buoyancy reads dye channels: give dyes (K, N)")
+                ctx.set_field(_lib.F_DYES, np.ascontiguousarray(dyes, dtype=np.float64).reshape(-1, N))
+        ctx.set_force(F, fn)
+        ctx.set_buoyancy(buoyancy)
+        return ctx.force_apply(base, dt)
+    finally:  # (the cached context serves the other operators: it keeps no force and no channels)
+        ctx.set_buoyancy(None)
+        ctx.set_force(None, None)
+        if dyes is not None:
+            ctx._c(ctx.L.pucfem_set_field(ctx.h, _lib.F_DYES, None, 0))
+
+
 def advect_maccormack(c, u, DT, nodes=None, triangles=None, tri=None):
     """One limited MacCormack step (pucfem_sl_advect_mc; Selle et al. 2008) of the field c (N,) or of the K fields
     c (K, N), K = 1 .. 16, from one point location per pass and node: ch = SL(c; u, DT), cb = SL(ch; u, -DT),

@@ -47,6 +47,50 @@ def dye_field(name):
     return _lib.F_DYE0 + int(k)
 
 
+class Buoyancy:
+    """Boussinesq buoyancy of the dye: f = g * sum_t beta_t * (s_t - ref_t), with s_t the dye c ("c") or a dye
+    channel ("dye0" .. "dye15") at the start of the step.  terms: {name: (beta, ref)}, summed in the order given."""
+
+    def __init__(self, g=(0.0, -1.0), terms=None):
+        self.g = tuple(float(v) for v in np.asarray(g, dtype=np.float64).reshape(-1))
+        if len(self.g) != 2:
+            raise ValueError("buoyancy: g is a pair")
+        terms = {"c": (1.0, 0.0)} if terms is None else dict(terms)
+        if not 1 <= len(terms) <= 1 + _lib.MAX_DYES:
+            raise ValueError(f"buoyancy: 1 .. {1 + _lib.MAX_DYES} terms, got {len(terms)}")
+        self.terms = {}
+        for name, br in terms.items():
+            if name != "c" and dye_field(name) is None:
+                raise ValueError(f"buoyancy: unknown field {name!r}: 'c' or 'dye0' .. 'dye{_lib.MAX_DYES - 1}'")
+            beta, ref = br
+            self.terms[name] = (float(beta), float(ref))
+        vals = list(self.g) + [v for br in self.terms.values() for v in br]
+        if not np.all(np.isfinite(vals)):
+            raise ValueError("buoyancy: g, beta and ref must be finite")
+
+    def arrays(self):
+        """(g (2,), fields int32, beta, ref) as pucfem_set_buoyancy takes them."""
+        fields = np.array([_lib.F_C if n == "c" else dye_field(n) for n in self.terms], dtype=np.int32)
+        beta = np.array([b for b, _ in self.terms.values()], dtype=np.float64)
+        ref = np.array([r for _, r in self.terms.values()], dtype=np.float64)
+        return np.array(self.g, dtype=np.float64), fields, beta, ref
+
+    def __repr__(self):
+        return f"Buoyancy(g={self.g}, terms={self.terms})"
+
+
+def _force_args(force, N):
+    """force= as (constant, field): None, a pair, or an (N, 2) array."""
+    if force is None:
+        return None, None
+    a = np.asarray(force, dtype=np.float64)
+    if a.shape == (2,):
+        return a, None
+    if a.shape == (N, 2):
+        return None, a
+    raise ValueError(f"force must be a pair, an ({N}, 2) array or None, got shape {a.shape}")
+
+
 def _sample_spec(fields):
     """(names, enum array, components) of a field list given by name ("u", "c", "dye3", ...) or pucfem_field
     value."""
@@ -547,6 +591,52 @@ class Context:
         self._c(self.L.pucfem_inertia_probe(self.h, int(iters), o))
         return dict(kernel_ms=o[0], algo_bytes=o[1])
 
+    # ---- body forces (pucfem_set_force, pucfem_set_buoyancy)
+    def set_force(self, constant=None, field=None):
+        """The uniform force (a pair or None) and the nodal force field ((N, 2) or None) of the steps' right-hand
+        side r = base + dt * f (pucfem_set_force); both None switches that part off."""
+        F = None if constant is None else np.ascontiguousarray(constant, dtype=np.float64)
+        if F is not None and F.shape != (2,):
+            raise ValueError(f"force: the uniform force is a pair, got shape {F.shape}")
+        fn = None if field is None else np.ascontiguousarray(field, dtype=np.float64)
+        self._c(self.L.pucfem_set_force(self.h, None if F is None else _lib.dptr(F),
+                                        None if fn is None else _lib.dptr(fn)))
+
+    def set_buoyancy(self, buoyancy=None):
+        """Boussinesq buoyancy of the dye (pucfem_set_buoyancy): a Buoyancy, or None for off."""
+        if buoyancy is None:
+            self._c(self.L.pucfem_set_buoyancy(self.h, None, 0, None, None, None))
+            return
+        if not isinstance(buoyancy, Buoyancy):
+            raise ValueError("buoyancy must be a Buoyancy or None")
+        g, fields, beta, ref = buoyancy.arrays()
+        self._c(self.L.pucfem_set_buoyancy(self.h, _lib.dptr(g), len(fields), _lib.iptr(fields), _lib.dptr(beta),
+                                           _lib.dptr(ref)))
+
+    def force_info(self):
+        """The context's body force (pucfem_force_info): which terms are present, the forced steps since the setting
+        last changed, the buoyancy terms and the device bytes held."""
+        o = (ct.c_int64 * 4)()
+        self._c(self.L.pucfem_force_info(self.h, -1, o))
+        return dict(mask=int(o[0]), uniform=bool(o[0] & _lib.FORCE_UNIFORM), nodal=bool(o[0] & _lib.FORCE_NODAL),
+                    buoyancy=bool(o[0] & _lib.FORCE_BUOYANCY), steps=o[1], terms=o[2], bytes=o[3])
+
+    def force_apply(self, base, dt):
+        """r = base + dt * f (N, 2) from the context's current force setting and dye fields, through the step's
+        kernel on scratch buffers (pucfem_force_apply); the step's state is not touched."""
+        b = np.ascontiguousarray(base, dtype=np.float64)
+        if b.shape != (self.N, 2):
+            raise ValueError(f"force_apply: base must be ({self.N}, 2), got {b.shape}")
+        out = np.zeros_like(b)
+        self._c(self.L.pucfem_force_apply(self.h, _lib.dptr(b), float(dt), _lib.dptr(out)))
+        return out
+
+    def force_probe(self, iters=10):
+        """Kernel time of one k_force_rhs launch with the current setting (pucfem_force_probe; tools/force_bench.py)."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_force_probe(self.h, int(iters), o))
+        return dict(kernel_ms=o[0], algo_bytes=o[1])
+
     def set_advection(self, what, scheme):
         """The advection scheme (pucfem_set_advection) of the dye (what = ADV_DYE), of the inertial step's velocity
         (ADV_VELOCITY) or of both (their sum): 'sl' the reference's first-order step, 'maccormack' two of them and
@@ -666,8 +756,13 @@ class StokesSimulation:
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
                  tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl",
-                 tracer_diffusivity=0.0, tracer_seed=0):
+                 tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None):
         adv = advection_scheme(advection)
+        f_const, f_field = _force_args(force, mesh.N)
+        if buoyancy is not None and not isinstance(buoyancy, Buoyancy):
+            raise ValueError("buoyancy must be a Buoyancy or None")
+        if buoyancy is not None and scheme != "color":
+            raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
         # (the dye's scheme on color runs, the velocity's too on inertial ones)
         adv_what = (_lib.ADV_DYE if scheme == "color" else 0) | (_lib.ADV_VELOCITY if inertia else 0)
         if adv and not adv_what:
@@ -704,9 +799,66 @@ class StokesSimulation:
                 self.ctx.set_advection(adv_what, adv)
             if tracer_diffusivity != 0.0 or tracer_seed != 0:
                 self.ctx.set_tracer_diffusion(tracer_diffusivity, tracer_seed)
+            self._force = (None, None)
+            self._buoyancy = None
+            if force is not None:
+                self.set_force(f_const, f_field)
+            if buoyancy is not None:
+                self.buoyancy = buoyancy
         except Exception:
             self.ctx.close()
             raise
+
+    # ---- body forces: r = base + dt * f in front of the viscous solve
+    def set_force(self, constant=None, field=None):
+        """The uniform force (a pair) and the nodal force field ((N, 2)) at once; None for a part that is absent.
+        It takes effect at the next step."""
+        if field is not None and np.shape(field) != (self.mesh.N, 2):
+            raise ValueError(f"force: the nodal field must be ({self.mesh.N}, 2), got {np.shape(field)}")
+        self.ctx.set_force(constant, field)
+        self._force = (None if constant is None else np.array(constant, dtype=np.float64),
+                       None if field is None else np.array(field, dtype=np.float64))
+
+    @property
+    def force(self):
+        """The body force of the steps: a pair (uniform: a mean pressure gradient in the x-periodic channel), an (N, 2)
+        nodal field, or None.  The viscous solve takes r = base + dt * f where it took base (u, or u_a with
+        inertia on).  set_force gives both parts at once; the getter returns (constant, field) when both are set."""
+        F, fn = self._force
+        return F if fn is None else fn if F is None else (F, fn)
+
+    @force.setter
+    def force(self, force):
+        self.set_force(*_force_args(force, self.mesh.N))
+
+    @property
+    def buoyancy(self):
+        """The Buoyancy of the dye (scheme 'color'), or None: f = g * sum_t beta_t * (s_t - ref_t) on top of the
+        force, read from the dye at the start of each step.  Such steps wait for the previous step's dye in front
+        of the viscous solve instead of overlapping it.  Removing or redefining the dye channels while a term names
+        one switches it off."""
+        return self._buoyancy if self.ctx.force_info()["buoyancy"] else None
+
+    @buoyancy.setter
+    def buoyancy(self, b):
+        if b is None and self.scheme != "color":  # (a 'food' run has none to switch off)
+            return
+        self.ctx.set_buoyancy(b)
+        self._buoyancy = b
+
+    @property
+    def force_field(self):
+        """(N, 2) the total force f of the current state (PUCFEM_F_FORCE), formed on the device when read."""
+        return self.ctx.get_field(_lib.F_FORCE, (self.mesh.N, 2))
+
+    @property
+    def u_rhs(self):
+        """(N, 2) the r of the last forced step (PUCFEM_F_U_RHS): what its viscous solve took as right-hand side."""
+        return self.ctx.get_field(_lib.F_U_RHS, (self.mesh.N, 2))
+
+    def force_info(self):
+        """Context.force_info of this run."""
+        return self.ctx.force_info()
 
     @property
     def tracer_diffusivity(self):
@@ -956,11 +1108,18 @@ class StokesEnsemble:
     fields and tracers; each member's fields are bit-identical to a StokesSimulation with its SquirmerBC.
     Small meshes only (the dense path: N <= 1500), scheme 'color' (semi-Lagrangian dye) or 'food'.
     inertia: a bool for all members or one bool per member -- a member with it on steps as
-    StokesSimulation(..., inertia=True) does, bit for bit (finite Reynolds number); the others step as before."""
+    StokesSimulation(..., inertia=True) does, bit for bit (finite Reynolds number); the others step as before.
+    force: one pair (a tuple or array) or (N, 2) field for all members, or a list with one entry per member, each a
+    pair, an (N, 2) field or None; buoyancy: one (g, beta, ref) for all members or a list of them (None: off) -- a
+    forced member steps as StokesSimulation(..., force=, buoyancy=Buoyancy(g, {"c": (beta, ref)})) does, bit for
+    bit (set_force, set_buoyancy)."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
-                 tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0):
+                 tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
+                 buoyancy=None):
         _ensemble_advection(advection)
+        if buoyancy is not None and scheme != "color":
+            raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
         self.bcs = _check_ensemble_bcs(bcs)
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -993,6 +1152,10 @@ class StokesEnsemble:
                 self.inertia = flags
             if diff.any() or seeds.any():
                 self.set_tracer_diffusion(diff, seeds)
+            if force is not None:
+                self.set_force(force)
+            if buoyancy is not None:
+                self.set_buoyancy(buoyancy)
         except Exception:
             self.ctx.close()
             raise
@@ -1078,6 +1241,87 @@ class StokesEnsemble:
         else:
             for m, f in enumerate(flags):
                 self.set_inertia(bool(f), m)
+
+    # ---- body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy)
+    def set_force(self, force, member=None):
+        """The body force of one member, or (member=None) of all: a pair, an (N, 2) field, a (pair, field) tuple or
+        None -- or, member=None, a list with one such entry per member.  A forced member steps as
+        StokesSimulation(..., force=...) does, bit for bit.  It takes effect at the next step."""
+        L, h, N = self.ctx.L, self.ctx.h, self.mesh.N
+
+        def one(f, m):
+            if isinstance(f, tuple) and len(f) == 2 and np.shape(f[1]) == (N, 2):
+                F, fn = np.asarray(f[0], dtype=np.float64), np.asarray(f[1], dtype=np.float64)
+            else:
+                F, fn = _force_args(f, N)
+            F = None if F is None else np.ascontiguousarray(F, dtype=np.float64)
+            fn = None if fn is None else np.ascontiguousarray(fn, dtype=np.float64)
+            self.ctx._c(L.pucfem_ens_set_force(h, m, None if F is None else _lib.dptr(F),
+                                               None if fn is None else _lib.dptr(fn)))
+
+        if member is not None:
+            return one(force, int(member))
+        if isinstance(force, list):
+            if len(force) != self.M:
+                raise ValueError(f"force: one entry per member: {self.M} members, got {len(force)}")
+            for m, f in enumerate(force):
+                one(f, m)
+        else:
+            one(force, -1)
+
+    def set_buoyancy(self, buoyancy, member=None):
+        """The buoyancy of one member's dye c, or (member=None) of all: (g, beta, ref) -- f += g * beta * (c - ref) --
+        or None for off; or, member=None, a list with one such entry per member."""
+        L, h = self.ctx.L, self.ctx.h
+
+        def one(b, m):
+            if b is None:
+                self.ctx._c(L.pucfem_ens_set_buoyancy(h, m, None, 0.0, 0.0))
+                return
+            try:
+                g, beta, ref = b
+                g = np.ascontiguousarray(g, dtype=np.float64)
+                ok = g.shape == (2,)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError("buoyancy: a member's entry is (g, beta, ref) with g a pair, or None")
+            self.ctx._c(L.pucfem_ens_set_buoyancy(h, m, _lib.dptr(g), float(beta), float(ref)))
+
+        if member is not None:
+            return one(buoyancy, int(member))
+        if isinstance(buoyancy, list):
+            if len(buoyancy) != self.M:
+                raise ValueError(f"buoyancy: one entry per member: {self.M} members, got {len(buoyancy)}")
+            for m, b in enumerate(buoyancy):
+                one(b, m)
+        else:
+            one(buoyancy, -1)
+
+    def force_info(self, member=None):
+        """pucfem_force_info per member: the mask of its terms, the forced steps since its setting last changed, its
+        buoyancy terms and the device bytes the ensemble holds for forces -- one member's dict, or (member=None) a
+        dict of (M,) arrays."""
+        def one(m):
+            o = (ct.c_int64 * 4)()
+            self.ctx._c(self.ctx.L.pucfem_force_info(self.ctx.h, int(m), o))
+            return dict(mask=int(o[0]), steps=int(o[1]), terms=int(o[2]), bytes=int(o[3]))
+
+        if member is not None:
+            return one(member)
+        rows = [one(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in ("mask", "steps", "terms", "bytes")}
+
+    @property
+    def force_field(self):
+        """(M, N, 2) every member's total force f of the current state (PUCFEM_F_FORCE); zeros for an unforced one."""
+        return self.get(_lib.F_FORCE, 2)
+
+    @property
+    def u_rhs(self):
+        """(M, N, 2) every member's r of its last forced step (PUCFEM_F_U_RHS); members that have taken none since
+        their setting last changed make this an error: read one member with get(F_U_RHS, 2, member)."""
+        return self.get(_lib.F_U_RHS, 2)
 
     # ---- Brownian tracers per member (pucfem_ens_set_tracer_diffusion)
     def set_tracer_diffusion(self, D, seed=0, member=None):
@@ -1193,17 +1437,18 @@ class StokesEnsemble:
 
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
-                   inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0):
+                   inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  advection: 'sl' only (ensembles have no MacCormack
     step).  tracer_diffusivity, tracer_seed: one value for all members or one per member
-    (StokesEnsemble.set_tracer_diffusion)."""
+    (StokesEnsemble.set_tracer_diffusion).  force, buoyancy: one setting for all members or a list with one per
+    member (StokesEnsemble.set_force / set_buoyancy)."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
     ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia, tracer_diffusivity=tracer_diffusivity,
-                         tracer_seed=tracer_seed)
+                         tracer_seed=tracer_seed, force=force, buoyancy=buoyancy)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
@@ -1341,7 +1586,7 @@ class Result:
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
           tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
-          tracer_seed=0):
+          tracer_seed=0, force=None, buoyancy=None):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -1353,7 +1598,13 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     semi-Lagrangian transport of the reference, or the limited MacCormack scheme (second order) for the dye of a
     'color' run and the velocity of an inertial one (StokesSimulation.dye_advection / velocity_advection).
     tracer_diffusivity, tracer_seed (schemes 'color' and 'food'): Brownian tracers, a random walk of that diffusivity
-    per tracer and step on top of the move, reproducible from the seed (StokesSimulation.tracer_diffusivity)."""
+    per tracer and step on top of the move, reproducible from the seed (StokesSimulation.tracer_diffusivity).
+    force, buoyancy (schemes 'color' and 'food'; buoyancy 'color'): the body force of the steps, a pair, an (N, 2)
+    field or None, and the Buoyancy of the dye (StokesSimulation.force / buoyancy; its terms may name the dyes=)."""
+    if force is not None and scheme not in ("color", "food"):
+        raise ValueError("force belongs to the Stokes schemes 'color' and 'food'")
+    if buoyancy is not None and scheme != "color":
+        raise ValueError("buoyancy belongs to scheme 'color'")
     if (tracer_diffusivity != 0.0 or tracer_seed != 0) and scheme not in ("color", "food"):
         raise ValueError("tracer_diffusivity belongs to the Stokes schemes 'color' and 'food'")
     if advection_scheme(advection) and scheme not in ("color", "food"):
@@ -1366,9 +1617,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
         sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection,
-                               tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed)
+                               tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed, force=force)
         if dyes is not None:
             sim.dyes = dyes
+        if buoyancy is not None:  # (behind the channels its terms may name)
+            sim.buoyancy = buoyancy
         st = sim.step(steps) if steps else []
         res = Result(scheme, steps, u=sim.u, p=sim.field(_lib.F_P), stats=st)
         if dyes is not None:
