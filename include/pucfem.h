@@ -514,6 +514,33 @@ int pucfem_advection_info(void* ctx, int64_t* out11);
    zero fields; PUCFEM_ADV_VELOCITY: f = u (nch ignored) -- each launched once untimed and then `iters` times back to
    back between two events.  out4: milliseconds per launch of pass 1, of pass 2, algorithmic bytes of each. */
 int pucfem_advection_probe(void* ctx, int32_t what, int32_t nch, int32_t iters, double* out4);
+/* MacCormack advection per ensemble member: the comparison of swimmers with a dye whose mixing index is the flow's,
+   not the interpolation's, in one launch chain.  Each member has a dye scheme and a velocity scheme (both
+   PUCFEM_ADV_SL at first), apart from the context's own, which keeps governing pucfem_step alone (and
+   pucfem_set_advection beside an ensemble, and pucfem_ens_create with a scheme set, stay PUCFEM_ESTATE).  A member
+   whose dye scheme is on moves its c by the two passes above with the step's final u: bit for bit the c, the mixing
+   record and sl_notfound (pass 1's count) of a pucfem_step run with PUCFEM_ADV_DYE set and the member's boundary
+   values.  A member whose velocity scheme is on steps u_a = MC(u^n; u^n, dt) while its inertia flag is on
+   (pucfem_ens_set_inertia; the scheme may be set at any time and waits for the flag); PUCFEM_F_U_ADV, the forces and
+   the viscous product read that u_a.  A member with both schemes PUCFEM_ADV_SL steps as without this call.  Schemes
+   may differ between members; one set between two pucfem_ens_step calls takes effect at the next step, and switching
+   a scheme on starts that member's counts again.  The step stays one captured chain -- three launches more behind
+   the first-order dye launch while a member's dye scheme is on, two more behind the first-order inertial launch
+   while an inertial member's velocity scheme is on -- captured again only when that changes; which members run
+   which, the kernels read from device memory.  Per set, allocated when a scheme is first switched on: the members'
+   intermediate field (members x N doubles for the dye, members x N x 2 for the velocity), 16 bytes per node and
+   member for T1, the launches' partials and ticket counters; they are counted in pucfem_ens_info's bytes and freed
+   with the ensemble.
+   member = -1: every member.  PUCFEM_ESTATE without an ensemble and for PUCFEM_ADV_DYE on a PUCFEM_STOKES_FOOD
+   ensemble; PUCFEM_EINVAL for a member out of range, an unknown mask or scheme; PUCFEM_ENODEV on a host-only
+   context. */
+int pucfem_ens_set_advection(void* ctx, int32_t member /* -1 = all */, int32_t what /* bit mask */, int32_t scheme);
+/* member 0 .. members - 1, pucfem_advection_info's layout: out[0] the member's dye scheme, [1] its velocity scheme,
+   [2] MacCormack dye steps since that scheme was switched on, [3] velocity steps (those taken with inertia on),
+   [4..6] of the member's last dye launch: rows without T1, rows without T2, clamped values, [7..9] the same of its
+   last velocity launch (both components count) -- summed on the device; 0 before the first launch and while the
+   scheme (for the velocity: or the inertia flag) is off -- [10] device bytes the ensemble holds for MacCormack */
+int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11);
 
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,

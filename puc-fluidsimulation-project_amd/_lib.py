@@ -136,6 +136,8 @@ SIGNATURES = {
     "pucfem_sl_advect_mc": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
     "pucfem_sl_advect_vel_mc": ([_P, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
     "pucfem_advection_probe": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, _D], ct.c_int),
+    "pucfem_ens_set_advection": ([_P, ct.c_int32, ct.c_int32, ct.c_int32], ct.c_int),
+    "pucfem_ens_advection_info": ([_P, ct.c_int32, _I64], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_dye_step": ([_P, _D, _D, _D, _I32], ct.c_int),
     "pucfem_comm_info": ([_P, ct.POINTER(ct.c_int64)], ct.c_int),

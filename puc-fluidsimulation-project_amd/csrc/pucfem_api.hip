@@ -164,6 +164,23 @@ struct Ens {
   bool adv_stale = true;
   int adv_any = 0;                 // members with their flag on
   bool chain_adv = false;          // the captured graphs hold the inertial launch
+  // MacCormack advection per member (pucfem_ens_set_advection; k_ens_mc_fwd / k_ens_mc_bwd / k_ens_wsum), one set of
+  // buffers for the dye and one for the velocity, each allocated when its scheme is first switched on and kept: the
+  // members' ch (M x n doubles / M x 2n), pass 1's records (M x n int4), the partials of the set's launches and their
+  // ticket counters.  The dye's flags as the kernels read them are mc_on_dev (M); the velocity's are the value
+  // ENS_ADV_MC of adv_on_dev.  A member's counts are slots 4, 11, 12 (dye) and 10, 13, 14 (velocity) of its vals.
+  double *mc_ch = nullptr, *mc_part = nullptr, *mc_part_ws = nullptr;
+  double *mcv_ch = nullptr, *mcv_part = nullptr;
+  int4 *mc_rec = nullptr, *mcv_rec = nullptr;
+  int32_t* mc_on_dev = nullptr;
+  unsigned *mc_cnt = nullptr, *mcv_cnt = nullptr;  // 3 M (pass 1, pass 2, sums) / 2 M
+  size_t mc_bytes = 0;
+  std::vector<int32_t> mc_dye, mc_vel;       // the schemes (empty: never switched on)
+  std::vector<int64_t> mc_steps, mcv_steps;  // per member: MacCormack steps since the scheme was switched on
+  int mc_dye_any = 0;                        // members whose dye moves by MacCormack
+  int mc_vel_any = 0;                        // members with inertia on whose velocity does
+  bool chain_mcd = false, chain_mcv = false; // the captured graphs hold the dye's / the velocity's MacCormack launches
+  int nb_ws = 1;                             // blocks in x of k_ens_wsum: the single path's k_wsum grid
   // body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy; k_ens_force_rhs), allocated when a member
   // is first forced and kept: the members' r (M x 2n), their term masks (M) and parameters (M x ENS_FORCE_PARM) as
   // the kernel reads them; the nodal planes (M x 2n) when a member is first given a field
@@ -5995,6 +6012,24 @@ void ens_enqueue_step(Ctx& c) {
                        c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, e.ua,
                        e.part_adv, ra);
     KCHK();
+    // with at least one inertial member's velocity scheme on: u_a = MC(u^n; u^n, dt) of those members (flag ENS_ADV_MC,
+    // which k_ens_sl_vel skips) into their planes of ua -- Ctx::inertia_step's mc_vel_launch
+    if (e.mc_vel_any > 0) {
+      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+      const dbl2* f = reinterpret_cast<const dbl2*>(e.u);
+      const size_t sM = (size_t)M;
+      const RedOut r1{e.vals + 10, nullptr, e.mcv_cnt, 1, 0, 0u};
+      hipLaunchKernelGGL(k_ens_mc_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                         (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC, f,
+                         reinterpret_cast<dbl2*>(e.mcv_ch), e.mcv_rec, e.mcv_part, r1);
+      KCHK();
+      const RedOut r2{e.vals + 13, nullptr, e.mcv_cnt + sM, 2, 0, 0u};
+      hipLaunchKernelGGL(k_ens_mc_bwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                         (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC, f,
+                         reinterpret_cast<const dbl2*>(e.mcv_ch), reinterpret_cast<dbl2*>(e.ua),
+                         (const int4*)e.mcv_rec, e.mcv_part + sM * e.nb_sl, r2);
+      KCHK();
+    }
   }
   // with at least one member forced: r = base + dt * f of those members behind it (Ctx::force_step), and the viscous
   // product stages r for them.  c holds c^n: k_ens_mix2 of the previous step wrote it earlier in this chain
@@ -6054,8 +6089,30 @@ void ens_enqueue_step(Ctx& c) {
     const RedOut rs{e.vals + 2, nullptr, e.cnt + M, 3, 0, 0u};
     hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
                        c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
-                       (const double*)c.dwmix, e.part_sl, rs);
+                       (const double*)c.dwmix, e.part_sl, rs,
+                       e.mc_dye_any > 0 ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
     KCHK();
+    // with at least one member's dye scheme on: cn = MC(c; u, dt) of those members (which k_ens_sl skipped), pass 1's
+    // not-found count into slot 4 and the single path's k_wsum sums into slots 2 and 3 -- Ctx::mc_dye_step /
+    // mc_dye_reduce
+    if (e.mc_dye_any > 0) {
+      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+      const size_t sM = (size_t)M;
+      const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
+      hipLaunchKernelGGL(k_ens_mc_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                         (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c, e.mc_ch,
+                         e.mc_rec, e.mc_part, r1);
+      KCHK();
+      const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
+      hipLaunchKernelGGL(k_ens_mc_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                         (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c,
+                         (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2);
+      KCHK();
+      const RedOut rw{e.vals + 2, nullptr, e.mc_cnt + 2 * sM, 2, 0, 0u};
+      hipLaunchKernelGGL(k_ens_wsum, dim3(e.nb_ws, M), dim3(BS), 0, st, (int64_t)n, (const int32_t*)e.mc_on_dev,
+                         (const double*)e.cn, (const double*)c.dwmix, e.mc_part_ws, rw);
+      KCHK();
+    }
     const RedOut rm{e.vals + 5, nullptr, e.cnt + 2 * (size_t)M, 1, 0, 0u};
     hipLaunchKernelGGL(k_ens_mix2, dim3(e.nb_mix, M), dim3(BS), 0, st, (int64_t)n, (const double*)e.cn,
                        (const double*)c.dwmix, (const double*)e.vals, e.part_mx, rm, e.c);
@@ -6192,6 +6249,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     e.nb_div = c.div_grid();
     e.nb_sl = c.nb_sl(n);
     e.nb_mix = c.nb_rows(n);
+    e.nb_ws = Ctx::nb_dye(n);
     e.lds_mv = sizeof(double) * 2 * (size_t)n * ENS_TM;
     e.lds_pres = sizeof(double) * (size_t)n * ENS_TM;
     HIPCHK(hipFuncSetAttribute((const void*)k_ens_mv2_bc<ENS_TM>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -6264,6 +6322,25 @@ int pucfem_ens_info(void* ctx, int64_t* out4) {
 }
 
 // ---- inertia per member (k_ens_sl_vel, pucfem_ensemble.hpp)
+namespace {
+// the members' inertia flags as the kernels read them: ENS_ADV_MC where the member's velocity scheme is MacCormack
+void ens_adv_upload(Ctx& c, Ens& e) {
+  const size_t sM = (size_t)e.M;
+  e.adv_any = (int)std::count(e.adv_on.begin(), e.adv_on.end(), 1);
+  e.mc_vel_any = 0;
+  if (!e.adv_on_dev) return;
+  std::vector<int32_t> f(sM, ENS_ADV_OFF);
+  for (size_t m = 0; m < sM; ++m)
+    if (e.adv_on[m]) {
+      const bool mc = !e.mc_vel.empty() && e.mc_vel[m] != PUCFEM_ADV_SL;
+      f[m] = mc ? ENS_ADV_MC : ENS_ADV_SL;
+      e.mc_vel_any += mc ? 1 : 0;
+    }
+  c.h2d(e.adv_on_dev, f.data(), sizeof(int32_t) * sM);
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+}  // namespace
+
 int pucfem_ens_set_inertia(void* ctx, int32_t member, int32_t on) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
@@ -6296,9 +6373,7 @@ int pucfem_ens_set_inertia(void* ctx, int32_t member, int32_t on) {
       }
     }
     if (!changed) return;
-    e.adv_any = (int)std::count(e.adv_on.begin(), e.adv_on.end(), 1);
-    c.h2d(e.adv_on_dev, e.adv_on.data(), sizeof(int32_t) * sM);
-    HIPCHK(hipStreamSynchronize(c.st));
+    ens_adv_upload(c, e);
   });
 }
 
@@ -6319,6 +6394,107 @@ int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4) {
     out4[1] = have ? e.adv_steps[m] : 0;
     out4[2] = have ? (int64_t)std::llround(e.adv_vals[ENS_VALS * m + 10]) : 0;
     out4[3] = (int64_t)e.adv_bytes;
+  });
+}
+
+// ---- MacCormack advection per member (k_ens_mc_fwd / k_ens_mc_bwd / k_ens_wsum, pucfem_ensemble.hpp)
+int pucfem_ens_set_advection(void* ctx, int32_t member, int32_t what, int32_t scheme) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    if (what & ~(PUCFEM_ADV_DYE | PUCFEM_ADV_VELOCITY) || what == 0)
+      throw Error(PUCFEM_EINVAL, "what is a mask of PUCFEM_ADV_DYE and PUCFEM_ADV_VELOCITY");
+    if (scheme != PUCFEM_ADV_SL && scheme != PUCFEM_ADV_MACCORMACK)
+      throw Error(PUCFEM_EINVAL, "unknown advection scheme");
+    if ((what & PUCFEM_ADV_DYE) && c.scheme != PUCFEM_STOKES_COLOR)
+      throw Error(PUCFEM_ESTATE, "the dye's scheme needs a STOKES_COLOR ensemble: STOKES_FOOD has no dye");
+    const size_t sM = (size_t)e.M, sn = (size_t)e.n;
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
+    const size_t before = e.bytes;
+    bool up_dye = false, up_vel = false;
+    if (what & PUCFEM_ADV_DYE) {
+      if (e.mc_dye.empty() && scheme) {  // (nothing was ever on: nothing is allocated until now)
+        e.mc_ch = e.alloc<double>(sM * sn, c.st);
+        e.mc_rec = e.alloc<int4>(sM * sn, c.st);
+        e.mc_part = e.alloc<double>(sM * 3 * e.nb_sl, c.st);
+        e.mc_part_ws = e.alloc<double>(sM * 2 * e.nb_ws, c.st);
+        e.mc_on_dev = e.alloc<int32_t>(sM, c.st);
+        e.mc_cnt = e.alloc<unsigned>(3 * sM, c.st);
+        e.mc_dye.assign(sM, 0);
+        e.mc_steps.assign(sM, 0);
+      }
+      for (size_t m = m0; m < m1 && !e.mc_dye.empty(); ++m) {
+        if (e.mc_dye[m] == scheme) continue;
+        e.mc_dye[m] = scheme;
+        up_dye = true;
+        if (scheme) {  // (switched on: its counts start again, as pucfem_set_advection's do)
+          e.mc_steps[m] = 0;
+          HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 11, 0, 2 * sizeof(double), c.st));
+        }
+      }
+    }
+    if (what & PUCFEM_ADV_VELOCITY) {
+      if (e.mc_vel.empty() && scheme) {
+        e.mcv_ch = e.alloc<double>(sM * 2 * sn, c.st);
+        e.mcv_rec = e.alloc<int4>(sM * sn, c.st);
+        e.mcv_part = e.alloc<double>(sM * 3 * e.nb_sl, c.st);
+        e.mcv_cnt = e.alloc<unsigned>(2 * sM, c.st);
+        e.mc_vel.assign(sM, 0);
+        e.mcv_steps.assign(sM, 0);
+      }
+      for (size_t m = m0; m < m1 && !e.mc_vel.empty(); ++m) {
+        if (e.mc_vel[m] == scheme) continue;
+        e.mc_vel[m] = scheme;
+        up_vel = true;
+        if (scheme) {
+          e.mcv_steps[m] = 0;
+          HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 13, 0, 2 * sizeof(double), c.st));
+        }
+      }
+    }
+    e.mc_bytes += e.bytes - before;
+    if (up_dye) {
+      e.mc_dye_any = (int)std::count(e.mc_dye.begin(), e.mc_dye.end(), (int32_t)PUCFEM_ADV_MACCORMACK);
+      c.h2d(e.mc_on_dev, e.mc_dye.data(), sizeof(int32_t) * sM);
+    }
+    if (up_vel) ens_adv_upload(c, e);  // (takes effect while the member's inertia flag is on)
+    e.adv_stale = true;
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= 0 && member < e.M, "member index out of range");
+    require(out11 != nullptr, "null output");
+    const size_t m = (size_t)member;
+    const bool dye = !e.mc_dye.empty(), vel = !e.mc_vel.empty();
+    if ((dye || vel) && (e.adv_stale || e.adv_vals.empty())) {  // (one copy serves every member until the next step)
+      e.adv_vals.resize((size_t)e.M * ENS_VALS);
+      c.d2h(e.adv_vals.data(), e.vals, sizeof(double) * e.adv_vals.size());
+      e.adv_stale = false;
+    }
+    auto val = [&](int slot) { return (int64_t)std::llround(e.adv_vals[ENS_VALS * m + slot]); };
+    for (int k = 0; k < 11; ++k) out11[k] = 0;
+    out11[0] = dye ? e.mc_dye[m] : PUCFEM_ADV_SL;
+    out11[1] = vel ? e.mc_vel[m] : PUCFEM_ADV_SL;
+    out11[2] = dye ? e.mc_steps[m] : 0;
+    out11[3] = vel ? e.mcv_steps[m] : 0;
+    // (the counts of the member's last MacCormack launch while its scheme is on; 0 before the first and once it is off)
+    if (out11[0] && out11[2] > 0) {
+      out11[4] = val(4);
+      out11[5] = val(11);
+      out11[6] = val(12);
+    }
+    if (out11[1] && out11[3] > 0 && !e.adv_on.empty() && e.adv_on[m]) {
+      out11[7] = val(10);
+      out11[8] = val(13);
+      out11[9] = val(14);
+    }
+    out11[10] = (int64_t)e.mc_bytes;
   });
 }
 
@@ -6485,14 +6661,19 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     // members are on is read from device memory by the kernels, so it needs no new capture.)
     // (the same for the tracers' diffusion: the BROWN tracer launch iff a member's D is positive)
     // (and for the body forces: the force launch iff a member is forced, with the nodal planes once they exist)
+    // (and for MacCormack: the dye's three launches iff a member's dye scheme is on, the velocity's two iff an
+    // inertial member's velocity scheme is)
     if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0) || e.chain_force != (e.force_any > 0) ||
-        e.chain_fnod != (e.fnod != nullptr)) {
+        e.chain_fnod != (e.fnod != nullptr) || e.chain_mcd != (e.mc_dye_any > 0) ||
+        e.chain_mcv != (e.mc_vel_any > 0)) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
       e.chain_adv = e.adv_any > 0;
       e.chain_br = e.br_any > 0;
       e.chain_force = e.force_any > 0;
       e.chain_fnod = e.fnod != nullptr;
+      e.chain_mcd = e.mc_dye_any > 0;
+      e.chain_mcv = e.mc_vel_any > 0;
     }
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
@@ -6523,6 +6704,11 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
         if (e.adv_on[m]) e.adv_steps[m] += nsteps;
       e.adv_stale = true;
     }
+    for (size_t m = 0; m < sM && e.mc_dye_any > 0; ++m)
+      if (e.mc_dye[m]) e.mc_steps[m] += nsteps;
+    for (size_t m = 0; m < sM && e.mc_vel_any > 0; ++m)
+      if (e.mc_vel[m] && e.adv_on[m]) e.mcv_steps[m] += nsteps;
+    if (e.mc_dye_any > 0 || e.mc_vel_any > 0) e.adv_stale = true;
     for (size_t m = 0; m < sM && e.force_any > 0; ++m)
       if (e.fmask[m]) e.fsteps[m] += nsteps;
     if (stats)

@@ -16,14 +16,19 @@
 #pragma once
 #include "pucfem_kernels.hpp"
 #include "pucfem_kernels_impl.hpp"
+#include "pucfem_maccormack.hpp"
 
 namespace pucfem {
 namespace dev {
 
 constexpr int ENS_TM = 4;     // members per block of the dense products
 // per-member value slots (k_stats' layout in 0..6; 8: scratch maximum, 9: sum(braw), 10: not-found rows of the
-// member's last inertial launch)
+// member's last inertial launch; 11 / 12: rows without T2 and clamped values of its last MacCormack dye launch,
+// 13 / 14: the same of its last MacCormack velocity launch; 15 is free)
 constexpr int ENS_VALS = 16;
+// a member's flag as the inertial kernels read it (Ens::adv_on_dev): off, first order (k_ens_sl_vel), MacCormack
+// (k_ens_mc_fwd / k_ens_mc_bwd); the consumers of ua (k_ens_force_rhs, k_ens_mv2_bc) read any non-zero value as on
+constexpr int32_t ENS_ADV_OFF = 0, ENS_ADV_SL = 1, ENS_ADV_MC = 2;
 
 // the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
 // (NP partial arrays of gridDim.x blocks per member)
@@ -333,13 +338,17 @@ __global__ __launch_bounds__(BS) void k_ens_grad_proj1(SellDev A, const double* 
 }
 
 // k_sl_rec_wave per member (row0 = 0: one rank): one wave per row, the single path's sl_row_wave (pucfem_locate.hpp).
-// u: M x 2n, c / cout: M x n, part: M x 3 gridDim.x.
+// u: M x 2n, c / cout: M x n, part: M x 3 gridDim.x.  mc (M, or null: no member's dye moves by MacCormack): a member
+// whose flag is set leaves at once, as in k_ens_sl_vel -- k_ens_mc_fwd / k_ens_mc_bwd / k_ens_wsum write its cout and
+// its sums.
 __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, int64_t n, const double* __restrict__ u,
                                                double dt, const double* __restrict__ c, double* __restrict__ cout,
-                                               const double* __restrict__ wmix, double* part, RedOut ro) {
+                                               const double* __restrict__ wmix, double* part, RedOut ro,
+                                               const int32_t* __restrict__ mc) {
   __shared__ double sw_[3][BS / 64];
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
+  if (mc && mc[m]) return;
   const double* ux = u + (int64_t)m * 2 * n;
   const double* uy = ux + 1;
   const double* cm = c + (int64_t)m * n;
@@ -377,8 +386,8 @@ __global__ __launch_bounds__(BS) void k_ens_sl(MeshDev Mh, LocDev L, GridDev G, 
 // velocity, in front of k_ens_mv2_bc.  k_ens_sl's sl_row_wave on k_ens_sl's grid in x (one wave per row), with
 // k_sl_vel's field (pucfem_inertia.hpp): sl_value's pair form, so a member's ua holds the bits of the single path's
 // u_adv.  Three 16-byte gathers from the member's u, one 16-byte store into its plane of ua; a row that is not found
-// keeps its own pair.  A member whose flag is off leaves at once (a block-uniform exit in front of every barrier: its
-// ticket is not drawn).  The not-found rows of each member: per-block partials, summed by red_finish in block order.
+// keeps its own pair.  A member whose flag is not ENS_ADV_SL (off, or MacCormack: k_ens_mc_* form its ua) leaves at
+// once (a block-uniform exit in front of every barrier: its ticket is not drawn).  The not-found rows of each member: per-block partials, summed by red_finish in block order.
 // u, ua: M x 2n (ua must not alias u: rows of other blocks still gather from u); on: M; part: M x gridDim.x.
 __global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev G, int64_t n,
                                                    const double* __restrict__ u, double dt,
@@ -387,7 +396,7 @@ __global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev
   __shared__ double sw_[BS / 64];
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
-  if (!on[m]) return;
+  if (on[m] != ENS_ADV_SL) return;
   const dbl2* f = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
   dbl2* out = reinterpret_cast<dbl2*>(ua) + (int64_t)m * n;
   const RedOut R = ens_red<1>(ro, m, part);
@@ -406,6 +415,132 @@ __global__ __launch_bounds__(BS) void k_ens_sl_vel(MeshDev Mh, LocDev L, GridDev
     double a = 0.0;
     for (int k = 0; k < BS / 64; ++k) a += sw_[k];
     red_part(R, part, 0, a);
+  }
+  red_finish(R, part, sh);
+}
+
+// MacCormack advection per member (pucfem_ens_set_advection; pucfem_maccormack.hpp): the two passes of k_mc_fwd /
+// k_mc_bwd (F = double: the dye) and of k_mc_fwd_vel / k_mc_bwd_vel (F = dbl2: the velocity's interleaved pairs), one
+// wave per row on k_ens_sl's grid in x, with the locate members already run (sl_point, sl_locate_wave, sl_value: the
+// triangle of the single path's lane-per-row locate, pucfem_locate.hpp), so ch, the record and the result hold the bits
+// of the single path's.  A member whose flag on[m] is not `want` leaves at once: a block-uniform exit in front of every
+// barrier and of the ticket, as in k_ens_sl_vel.  u: M x 2n (the velocity that traces), f / ch / out: M x n values of
+// F, rec: M x n.
+//
+// Pass 1: ch = SL(f; u, +dt) and the row's T1 (a, b, d, id; id = -1: none, and ch keeps f).  The member's rows
+// without T1: per-block partials, summed by red_finish in block order.  part: M x gridDim.x.
+template <class F>
+__global__ __launch_bounds__(BS) void k_ens_mc_fwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                   const double* __restrict__ u, double dt,
+                                                   const int32_t* __restrict__ on, int32_t want, const F* f,
+                                                   F* __restrict__ ch, int4* __restrict__ rec, double* part, RedOut ro) {
+  __shared__ double sw_[BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (on[m] != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  const F* fm = f + (int64_t)m * n;
+  F* chm = ch + (int64_t)m * n;
+  int4* rm = rec + (int64_t)m * n;
+  const RedOut R = ens_red<1>(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nnf = 0.0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double xb, yb;
+    sl_point(Mh, i, v.x, v.y, dt, xb, yb);
+    SlTri r{};
+    const bool ok = sl_locate_wave(L, G, xb, yb, r);
+    if (!ok) nnf = 1.0;
+    const F o = ok ? sl_value(r, xb, yb, fm) : fm[i];
+    if (lane == 0) {
+      chm[i] = o;
+      rm[i] = ok ? make_int4(r.a, r.b, r.d, r.id) : make_int4(0, 0, 0, -1);
+    }
+  }
+  if (lane == 0) sw_[wv] = nnf;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double a = 0.0;
+    for (int k = 0; k < BS / 64; ++k) a += sw_[k];
+    red_part(R, part, 0, a);
+  }
+  red_finish(R, part, sh);
+}
+// Pass 2, its own launch (it gathers ch at the vertices of other rows' triangles): the trace with -dt, pass 1's record
+// and mc_row / mc_limit (pucfem_maccormack.hpp) on (f, ch).  out aliases neither f nor ch.  The member's rows without
+// T2 and its clamped values (both components of a pair count): per-block partials, summed by red_finish in block
+// order.  part: M x 2 gridDim.x.
+template <class F>
+__global__ __launch_bounds__(BS) void k_ens_mc_bwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                   const double* __restrict__ u, double dt,
+                                                   const int32_t* __restrict__ on, int32_t want, const F* f,
+                                                   const F* ch, F* __restrict__ out, const int4* __restrict__ rec,
+                                                   double* part, RedOut ro) {
+  __shared__ double sw_[2][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (on[m] != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  const F* fm = f + (int64_t)m * n;
+  const F* chm = ch + (int64_t)m * n;
+  F* om = out + (int64_t)m * n;
+  const int4* rm = rec + (int64_t)m * n;
+  const RedOut R = ens_red<2>(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nb2 = 0.0;
+  int32_t ncl = 0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double xb, yb;
+    sl_point(Mh, i, v.x, v.y, -dt, xb, yb);
+    SlTri r{};
+    const bool ok2 = sl_locate_wave(L, G, xb, yb, r);
+    if (!ok2) nb2 = 1.0;
+    const F o = mc_row(rm[i], ok2, r, xb, yb, i, fm, chm, ncl);
+    if (lane == 0) om[i] = o;
+  }
+  if (lane == 0) {
+    sw_[0][wv] = nb2;
+    sw_[1][wv] = (double)ncl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  red_finish(R, part, sh);
+}
+// k_wsum per member, for the members whose dye moved by MacCormack (on[m] set; the others leave at once): sum w c and
+// sum w of the new dye cn in the single path's grouping -- its grid in x (Ctx::nb_dye), block_rows, the lanes' strided
+// accumulation, block_sum -- and red_finish, whose order over these few blocks is k_reduce's.  cn: M x n,
+// part: M x 2 gridDim.x.
+__global__ __launch_bounds__(BS) void k_ens_wsum(int64_t n, const int32_t* __restrict__ on,
+                                                 const double* __restrict__ cn, const double* __restrict__ wmix,
+                                                 double* part, RedOut ro) {
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (!on[m]) return;
+  const double* c = cn + (int64_t)m * n;
+  const RedOut R = ens_red<2>(ro, m, part);
+  double swc = 0.0, sw = 0.0;
+  int64_t r0, r1;
+  block_rows(n, r0, r1);
+  for (int64_t i = r0 + threadIdx.x; i < r1; i += BS) {
+    const double w = wmix[i];
+    swc += w * c[i];
+    sw += w;
+  }
+  const double a = block_sum(swc, sh), b = block_sum(sw, sh);
+  if (threadIdx.x == 0) {
+    red_part(R, part, 0, a);
+    red_part(R, part, 1, b);
   }
   red_finish(R, part, sh);
 }

@@ -93,6 +93,29 @@ __device__ __forceinline__ double mc_row(const int4 t, bool ok2, const SlTri& r,
   return v;
 }
 
+// ... of a field of interleaved pairs: the two components limited separately (each in the plain form's expression
+// order: component k holds the bits of the plain form on that component); every clamped component counts
+__device__ __forceinline__ dbl2 mc_row(const int4 t, bool ok2, const SlTri& r, double xb, double yb, int64_t g,
+                                       const dbl2* f, const dbl2* ch, int32_t& nclamp) {
+  dbl2 o = f[g];
+  if (t.w >= 0) {
+    const dbl2 chg = ch[g];
+    if (!ok2) {
+      o = chg;
+    } else {
+      const dbl2 cb = sl_value(r, xb, yb, ch);
+      const dbl2 fa = f[t.x], fb = f[t.y], fd = f[t.z];
+      bool hx, hy;
+      const double ex = chg.x + 0.5 * (o.x - cb.x), ey = chg.y + 0.5 * (o.y - cb.y);
+      o.x = mc_limit(ex, fa.x, fb.x, fd.x, hx);
+      o.y = mc_limit(ey, fa.y, fb.y, fd.y, hy);
+      if (hx) ++nclamp;
+      if (hy) ++nclamp;
+    }
+  }
+  return o;
+}
+
 // pass 2, plain fields: out0 / cout from (c0, ch0) / (cin, ch) and pass 1's rec; marks, tri (n each, or null): the
 // row's MC_* bits and T1's mesh triangle id (-1); cnt[3 * block + (0, 1, 2)]: the block's rows without T1, rows
 // without T2, clamped values (every field counts)
@@ -183,23 +206,7 @@ __global__ __launch_bounds__(BS) void k_mc_bwd_vel(MeshDev M, LOC L, GridDev G, 
     if (!ok2) ++nb2;
     if (marks) marks[i] = (t.w < 0 ? MC_NO_BACK : 0) | (ok2 ? 0 : MC_NO_FWD);
     if (tri) tri[i] = t.w;
-    dbl2 o = f[g];
-    if (t.w >= 0) {
-      const dbl2 chg = ch[g];
-      if (!ok2) {
-        o = chg;
-      } else {
-        const dbl2 cb = sl_value(r, xb, yb, ch);
-        const dbl2 fa = f[t.x], fb = f[t.y], fd = f[t.z];
-        bool hx, hy;
-        const double ex = chg.x + 0.5 * (o.x - cb.x), ey = chg.y + 0.5 * (o.y - cb.y);
-        o.x = mc_limit(ex, fa.x, fb.x, fd.x, hx);
-        o.y = mc_limit(ey, fa.y, fb.y, fd.y, hy);
-        if (hx) ++ncl;
-        if (hy) ++ncl;
-      }
-    }
-    stnt(out + g, o);
+    stnt(out + g, mc_row(t, ok2, r, xb, yb, g, f, ch, ncl));
   }
   const double a = block_sum((double)nb1, sh), b = block_sum((double)nb2, sh), d = block_sum((double)ncl, sh);
   if (threadIdx.x == 0) {

@@ -1079,10 +1079,22 @@ def _ensemble_diffusion(tracer_diffusivity, tracer_seed, M):
 
 
 def _ensemble_advection(advection):
-    """Ensembles step the first-order advection alone: advection='maccormack' is refused."""
+    """The advection= keyword of ensembles takes 'sl' alone: members carry a dye scheme and a velocity scheme each."""
     if advection_scheme(advection) != 0:
-        raise ValueError("ensembles step the first-order semi-Lagrangian advection only: advection='maccormack' "
-                         "belongs to StokesSimulation / solve (one squirmer per context)")
+        raise ValueError("ensembles take dye_advection= and velocity_advection= (one name for all members or one per "
+                         "member), not advection='maccormack': that keyword belongs to StokesSimulation / solve (one "
+                         "squirmer per context)")
+
+
+def _ensemble_schemes(scheme, M, name):
+    """The dye_advection= / velocity_advection= argument of an ensemble of M members as an (M,) array of
+    PUCFEM_ADV_* values: one name for all, or M of them."""
+    if isinstance(scheme, (str, int, np.integer)):
+        return np.full(M, advection_scheme(scheme), dtype=np.int32)
+    names = list(scheme)
+    if len(names) != M:
+        raise ValueError(f"{name} must be one name or one per member: {M} members, got {len(names)}")
+    return np.array([advection_scheme(v) for v in names], dtype=np.int32)
 
 
 def ensemble_dirichlet_values(mesh: Mesh, bcs):
@@ -1112,11 +1124,14 @@ class StokesEnsemble:
     force: one pair (a tuple or array) or (N, 2) field for all members, or a list with one entry per member, each a
     pair, an (N, 2) field or None; buoyancy: one (g, beta, ref) for all members or a list of them (None: off) -- a
     forced member steps as StokesSimulation(..., force=, buoyancy=Buoyancy(g, {"c": (beta, ref)})) does, bit for
-    bit (set_force, set_buoyancy)."""
+    bit (set_force, set_buoyancy).
+    dye_advection, velocity_advection: 'sl' or 'maccormack', one name for all members or one per member -- a member
+    whose dye scheme is 'maccormack' moves its c as StokesSimulation(..., advection="maccormack") does, one whose
+    velocity scheme is forms its u_a that way while its inertia is on, bit for bit (set_advection)."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
                  tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
-                 buoyancy=None):
+                 buoyancy=None, dye_advection="sl", velocity_advection="sl"):
         _ensemble_advection(advection)
         if buoyancy is not None and scheme != "color":
             raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
@@ -1124,6 +1139,10 @@ class StokesEnsemble:
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
         flags = _ensemble_flags(inertia, len(self.bcs))
+        adv_dye = _ensemble_schemes(dye_advection, len(self.bcs), "dye_advection")
+        adv_vel = _ensemble_schemes(velocity_advection, len(self.bcs), "velocity_advection")
+        if adv_dye.any() and scheme != "color":
+            raise ValueError("dye_advection='maccormack' belongs to scheme 'color': a 'food' run has no dye")
         diff, seeds = _ensemble_diffusion(tracer_diffusivity, tracer_seed, len(self.bcs))
         nodes, vals = ensemble_dirichlet_values(mesh, self.bcs)
         self.mesh = mesh
@@ -1150,6 +1169,10 @@ class StokesEnsemble:
             self.ctx._c(self.ctx.L.pucfem_ens_create(self.ctx.h, self.M, _lib.dptr(vals)))
             if flags.any():
                 self.inertia = flags
+            if adv_dye.any():
+                self.dye_advection = adv_dye
+            if adv_vel.any():
+                self.velocity_advection = adv_vel
             if diff.any() or seeds.any():
                 self.set_tracer_diffusion(diff, seeds)
             if force is not None:
@@ -1241,6 +1264,60 @@ class StokesEnsemble:
         else:
             for m, f in enumerate(flags):
                 self.set_inertia(bool(f), m)
+
+    # ---- MacCormack advection per member (pucfem_ens_set_advection)
+    def set_advection(self, what, scheme, member=None):
+        """The advection scheme of one member (or, member=None, of all): of its dye (what = ADV_DYE), of its inertial
+        step's velocity (ADV_VELOCITY) or of both (their sum); 'sl' or 'maccormack'.  It takes effect at the next
+        step (the velocity's while the member's inertia is on); switching a scheme on starts the member's counts
+        (advection_info) again."""
+        self.ctx._c(self.ctx.L.pucfem_ens_set_advection(self.ctx.h, -1 if member is None else int(member), int(what),
+                                                        advection_scheme(scheme)))
+
+    def advection_info(self, member=None):
+        """pucfem_ens_advection_info, with Context.advection_info's keys: the member's two schemes, the MacCormack
+        steps since each was switched on, the counts of its last launch of each (rows without T1, rows without T2,
+        clamped values) and the device bytes the ensemble holds for MacCormack -- one member's dict, or
+        (member=None) a dict of (M,) arrays ((M, 3) for the counts)."""
+        def one(m):
+            o = (ct.c_int64 * 11)()
+            self.ctx._c(self.ctx.L.pucfem_ens_advection_info(self.ctx.h, int(m), o))
+            return dict(dye=ADVECTION_NAMES[o[0]], velocity=ADVECTION_NAMES[o[1]], dye_steps=o[2],
+                        velocity_steps=o[3], dye_counts=(o[4], o[5], o[6]), velocity_counts=(o[7], o[8], o[9]),
+                        bytes=o[10])
+
+        if member is not None:
+            return one(member)
+        rows = [one(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in rows[0]}
+
+    def _set_schemes(self, what, scheme, name):
+        v = _ensemble_schemes(scheme, self.M, name)
+        if (v == v[0]).all():
+            self.set_advection(what, int(v[0]))
+        else:
+            for m, k in enumerate(v):
+                self.set_advection(what, int(k), m)
+
+    @property
+    def dye_advection(self):
+        """One name per member, 'sl' or 'maccormack': how each member's step moves its c
+        (StokesSimulation.dye_advection per member).  Set it with one name for all or one per member."""
+        return list(self.advection_info()["dye"])
+
+    @dye_advection.setter
+    def dye_advection(self, scheme):
+        self._set_schemes(_lib.ADV_DYE, scheme, "dye_advection")
+
+    @property
+    def velocity_advection(self):
+        """One name per member: how each member's inertial step forms u_a from u.  It may be set while the member's
+        inertia is off and takes effect when it is on."""
+        return list(self.advection_info()["velocity"])
+
+    @velocity_advection.setter
+    def velocity_advection(self, scheme):
+        self._set_schemes(_lib.ADV_VELOCITY, scheme, "velocity_advection")
 
     # ---- body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy)
     def set_force(self, force, member=None):
@@ -1437,10 +1514,12 @@ class StokesEnsemble:
 
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
-                   inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None):
+                   inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
+                   dye_advection="sl", velocity_advection="sl"):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
-    for all members or one per member (StokesEnsemble.inertia).  advection: 'sl' only (ensembles have no MacCormack
-    step).  tracer_diffusivity, tracer_seed: one value for all members or one per member
+    for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
+    'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
+    would not say which of the two).  tracer_diffusivity, tracer_seed: one value for all members or one per member
     (StokesEnsemble.set_tracer_diffusion).  force, buoyancy: one setting for all members or a list with one per
     member (StokesEnsemble.set_force / set_buoyancy)."""
     _ensemble_advection(advection)
@@ -1448,7 +1527,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
     ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia, tracer_diffusivity=tracer_diffusivity,
-                         tracer_seed=tracer_seed, force=force, buoyancy=buoyancy)
+                         tracer_seed=tracer_seed, force=force, buoyancy=buoyancy, dye_advection=dye_advection,
+                         velocity_advection=velocity_advection)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
