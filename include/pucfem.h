@@ -440,6 +440,61 @@ int pucfem_force_apply(void* ctx, const double* base, double dt, double* out);
    per launch (32 per row, 16 more with a nodal field, 8 more per buoyancy term). */
 int pucfem_force_probe(void* ctx, int32_t iters, double* out2);
 
+/* ---- time-dependent strokes: boundary values that vary per step ---- */
+/* The Dirichlet values of pucfem_set_dirichlet are fixed for a run: every swimmer is steady, and a steady
+   two-dimensional flow stretches dye along its streamlines without mixing it.  A stroke makes the values of `n` driven
+   Dirichlet nodes periodic in time: K modes (1 .. 8), a table amp[P][K] (1 <= P <= 65536), a start row, and per driven
+   node q a shape[q][K] and a direction dir[q] (a pair).  With s the steps taken since the stroke was set (a counter in
+   device memory, advanced on the device), the step being taken imposes, every product and sum as written,
+
+     row    = (start + s) mod P
+     vt     = amp[row][0] * shape[q][0]
+     vt     = vt + amp[row][j] * shape[q][j]      j = 1 .. K - 1, in this order
+     val[q] = (vt * dir[q].x, vt * dir[q].y)
+
+   written into the context's Dirichlet value array in front of the step's first launch (k_stroke_bc, one block) and
+   held for every boundary-condition application of that step.  Dirichlet nodes the stroke does not drive (the walls)
+   keep their values.  With shape = (sin th, sin 2 th, ...) and dir = (-sin th, cos th) a table whose rows are all
+   (B1, B2) gives the bits of the static squirmer values.  The reference zeroes the Dirichlet rows and columns of the
+   viscous matrix, so the values enter a step only through that array: a stroked step is, bit for bit on the
+   direct-solve paths, the step of a context built with the row's values, taken from the same fields.
+   Setting a stroke does not touch u; it resets s to 0 and the viscous solve's extrapolation history, as a force change
+   does.  K = 0 clears the stroke and restores the values the build uploaded (off stays off: nothing is touched).
+   pucfem_build_operators and pucfem_ctx_destroy clear it.  Off is the default, and with the stroke off a step is
+   launch for launch what it was.  A small-mesh context steps from its captured graph only while no stroke is set; with
+   one it runs the same launches uncaptured behind k_stroke_bc (the graph is kept: clearing the stroke returns to it).
+   PUCFEM_ESTATE: a heat or Poisson context, a multi-rank context, a context that has an ensemble (its members carry
+   their own strokes), pucfem_ens_create on a context whose stroke is on.  PUCFEM_EINVAL: K or P out of range,
+   start < 0, a non-finite table, shape or direction, a driven node that is not in the Dirichlet list or is listed
+   twice.  `nodes` are in the caller's numbering. */
+int pucfem_set_stroke(void* ctx, int32_t K, int32_t P, const double* amp, int32_t n, const int32_t* nodes,
+                      const double* shape /* n x K */, const double* dir /* n x 2 */, int64_t start);
+/* The same per ensemble member: each member has its own table, period, start row and counter (k_ens_stroke_bc, one
+   block per member, in front of the chain while at least one member has a stroke; the step stays one captured graph,
+   captured again only when "any member stroked" changes or the tables or shapes are reallocated).  The shapes,
+   directions and nodes are shared: those of the first call stand for all members, and a later call whose n, K, nodes,
+   shapes or directions differ is PUCFEM_EINVAL unless every member's stroke is off.  A member without a stroke is
+   skipped: its values and counter are left alone.  K = 0 clears the member's stroke and restores the values
+   pucfem_ens_create gave it.  A stroked member steps bit for bit as a pucfem_step run with the same stroke. */
+int pucfem_ens_set_stroke(void* ctx, int32_t member /* -1 = all */, int32_t K, int32_t P, const double* amp, int32_t n,
+                          const int32_t* nodes, const double* shape, const double* dir, int64_t start);
+/* member = -1, the context; 0 .. members - 1: an ensemble member.  out[0] K (0: off), [1] P, [2] start (mod P),
+   [3] steps taken since the stroke was set (read from the device), [4] the row the next step imposes, [5] driven
+   nodes. */
+int pucfem_stroke_info(void* ctx, int32_t member, int64_t* out6);
+/* The Dirichlet values the device holds now (the context's, or an ensemble member's), ndirlist x ncomp in the order of
+   the list given to pucfem_set_dirichlet; a node listed more than once reports its kept (last) value in every place.
+   Single-rank contexts. */
+int pucfem_get_dirichlet(void* ctx, int32_t member, double* out);
+/* Unit operation: row `row` of the stroke (the context's, or a member's) evaluated by the step's kernel into a scratch
+   copy of the Dirichlet values, returned as pucfem_get_dirichlet returns them.  The step's state, the values and the
+   counter are not touched.  PUCFEM_ESTATE with no stroke set. */
+int pucfem_stroke_apply(void* ctx, int32_t member, int64_t row, double* out);
+/* Measurement: the context's step launch (counter read, barrier, counter store) on a scratch copy of the values and a
+   scratch counter, launched once untimed and then `iters` times back to back between two events.  out2[0]:
+   milliseconds per launch; out2[1]: algorithmic bytes per launch (32 + 8 K per driven node). */
+int pucfem_stroke_probe(void* ctx, int32_t iters, double* out2);
+
 /* ---- Brownian tracers: food that diffuses ---- */
 /* The tracers are deterministic points; in the steady flow a run settles to, a tracer on a streamline outside the
    capture annulus is never eaten.  With a diffusivity D > 0 every free tracer also takes a random-walk increment per

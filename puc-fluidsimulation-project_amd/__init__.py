@@ -16,8 +16,9 @@ from .ops import (advect_maccormack, advect_maccormack_vector, advect_semilagran
                   calculate_vorticity, dye_implicit_step,
                   makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous)
 from .solver import (SAMPLE_FIELDS, Buoyancy, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
-                     StokesSimulation, Streamlines, Tolerances, dye_patterns, ensemble_dirichlet_values,
-                     pixel_centres, poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments)
+                     StokesSimulation, Streamlines, Stroke, Tolerances, dye_patterns, ensemble_dirichlet_values,
+                     pixel_centres, poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments,
+                     stroke_geometry)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401
 from .tracers import capture_map, tracer_init  # noqa: F401
 

@@ -26,6 +26,7 @@ F_FORCE = 15  # the total body force f (N, 2) of the current state, read only
 F_U_RHS = 16  # r (N, 2) of the last forced step, read only
 FORCE_UNIFORM, FORCE_NODAL, FORCE_BUOYANCY = 1, 2, 4  # pucfem_force_info: the terms present (a mask)
 MAX_DYES = 16
+STROKE_MAX_MODES, STROKE_MAX_PERIOD = 8, 65536  # pucfem_set_stroke: K and P at the most
 ADV_DYE, ADV_VELOCITY = 1, 2  # pucfem_set_advection: what (a mask)
 ADV_SL, ADV_MACCORMACK = 0, 1  # ... and the scheme
 MC_NO_BACK, MC_NO_FWD = 1, 2  # marks of pucfem_sl_advect_mc
@@ -127,7 +128,14 @@ SIGNATURES = {
     "pucfem_force_info": ([_P, ct.c_int32, _I64], ct.c_int),
     "pucfem_force_apply": ([_P, _D, ct.c_double, _D], ct.c_int),
     "pucfem_force_probe": ([_P, ct.c_int32, _D], ct.c_int),
-    "pucfem_set_tracer_diffusion": ([_P, ct.c_double, ct.c_uint64], ct.c_int),
+    "pucfem_set_stroke": ([_P, ct.c_int32, ct.c_int32, _D, ct.c_int32, _I32, _D, _D, ct.c_int64], ct.c_int),
+    "pucfem_ens_set_stroke": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, _D, ct.c_int32, _I32, _D, _D, ct.c_int64],
+                              ct.c_int),
+    "pucfem_stroke_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_get_dirichlet": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_stroke_apply": ([_P, ct.c_int32, ct.c_int64, _D], ct.c_int),
+    "pucfem_stroke_probe": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_set_tracer_diffusion":([_P, ct.c_double, ct.c_uint64], ct.c_int),
     "pucfem_ens_set_tracer_diffusion": ([_P, ct.c_int32, ct.c_double, ct.c_uint64], ct.c_int),
     "pucfem_get_tracer_diffusion": ([_P, ct.c_int32, _D, ct.POINTER(ct.c_uint64)], ct.c_int),
     "pucfem_tracer_probe": ([_P, ct.c_double, ct.c_int32, _D], ct.c_int),

@@ -33,6 +33,7 @@
 #include "pucfem_inertia.hpp"
 #include "pucfem_force.hpp"
 #include "pucfem_maccormack.hpp"
+#include "pucfem_stroke.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -202,6 +203,22 @@ struct Ens {
   std::vector<uint64_t> br_seed;
   int br_any = 0;                  // members with D > 0
   bool chain_br = false;           // the captured graphs hold the BROWN tracer launch
+  // time-dependent strokes per member (pucfem_ens_set_stroke; k_ens_stroke_bc), allocated when a member is first given
+  // one and kept: the members' parameters (M x ENS_STROKE_PARM) and step counters (M) as the kernel reads them, their
+  // tables one behind the other (sk_cap doubles, grown by reallocation), and the shared shapes, directions and value
+  // positions of the driven entries.  dval0: the values pucfem_ens_create uploaded, which clearing a stroke restores.
+  int64_t *sk_parm = nullptr, *sk_ctr = nullptr;
+  double *sk_tab = nullptr, *sk_shape = nullptr, *sk_dir = nullptr;
+  int32_t* sk_q = nullptr;
+  size_t sk_cap = 0, stroke_bytes = 0;
+  int32_t sk_n = 0;                          // driven entries (shared)
+  int sk_K = 0;                              // modes of the shared shapes
+  std::vector<int64_t> sk_par;               // the parameters (empty: never stroked)
+  std::vector<std::vector<double>> sk_amp;   // the members' tables
+  std::vector<int32_t> sk_nodes;             // the shared driven nodes (caller numbering), shapes and directions
+  std::vector<double> sk_shape_h, sk_dir_h, dval0;
+  int stroke_any = 0;                        // members with a stroke
+  bool chain_stroke = false;                 // the captured graphs hold the stroke launch
   int nb_tr = 1;             // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
@@ -634,7 +651,9 @@ struct Ctx {
   // pucfem_inertia_probe (pucfem_inertia.hpp): the fields in, the fields out, the blocks' not-found counts
   // Slots 17..21: pucfem_sl_advect_mc / pucfem_sl_advect_vel_mc / pucfem_advection_probe (pucfem_maccormack.hpp): the
   // intermediate fields, the records, the marks, the triangle ids, pass 2's counts
-  static constexpr int SMP_SLOTS = 22;
+  // Slot 22: pucfem_stroke_apply / pucfem_stroke_probe (pucfem_stroke.hpp): a copy of the Dirichlet values and, behind
+  // it, the probe's counter
+  static constexpr int SMP_SLOTS = 23;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -865,6 +884,7 @@ struct Ctx {
       drop_dyes();
       drop_inertia();
       drop_force();
+      drop_stroke(false);
       drop_advection();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
@@ -1437,6 +1457,82 @@ struct Ctx {
   size_t force_dev_bytes() const {
     const size_t plane = sizeof(double) * 2 * (size_t)std::max<i64>(1, lp.n_own);
     return (u_rhs ? plane : 0) + (f_nodal ? plane : 0);
+  }
+
+  // ------------------------------------------------------------------ time-dependent strokes (pucfem_stroke.hpp)
+  // With a stroke set, stokes_step rewrites the driven entries of ddval in front of everything else from row
+  // (start + s) mod P of the table; s is sk_ctr, in device memory.  The buffers are allocated when a stroke is set and
+  // freed by drop_stroke (they are not in `allocs`): a context that never sets one holds no new memory and launches
+  // nothing new.  dval_build: the values build uploaded, which clearing the stroke restores.
+  int sk_K = 0;  // modes (0: off)
+  i64 sk_P = 0, sk_start = 0;
+  int32_t sk_n = 0;  // driven entries
+  double *sk_amp = nullptr, *sk_shape = nullptr, *sk_dir = nullptr;
+  int32_t* sk_q = nullptr;
+  i64* sk_ctr = nullptr;
+  std::vector<double> dval_build;
+  bool stroked() const { return sk_K > 0; }
+  // a built single-rank Stokes context (checked before the device is asked for)
+  void stroke_ready() const {
+    need_built();
+    if (scheme != PUCFEM_STOKES_COLOR && scheme != PUCFEM_STOKES_FOOD)
+      throw Error(PUCFEM_ESTATE, "strokes need a Stokes context");
+    if (dist() || world != 1) throw Error(PUCFEM_ESTATE, "strokes are single-rank");
+    need_dev();
+    if (dir_ncomp != 2) throw Error(PUCFEM_ESTATE, "strokes need two-component Dirichlet values");
+  }
+  // the position in ddval of every caller node's kept Dirichlet entry (-1: not a Dirichlet node), as build orders them
+  std::vector<i32> dir_positions() const {
+    std::vector<i32> pos((size_t)mesh.N, -1);
+    std::vector<i64> last((size_t)mesh.N, -1);
+    for (size_t k = 0; k < dir_nodes.size(); ++k) last[dir_nodes[k]] = (i64)k;
+    i32 q = 0;
+    for (size_t k = 0; k < dir_nodes.size(); ++k)
+      if (last[dir_nodes[k]] == (i64)k) pos[dir_nodes[k]] = q++;
+    if (q != ndir) throw Error(PUCFEM_ESTATE, "Dirichlet list changed since the build");
+    return pos;
+  }
+  double stroke_launch_bytes() const { return (32.0 + 8.0 * sk_K) * (double)sk_n; }
+  // k_stroke_bc on the current stream: the row of counter ctr, which is advanced (the step's launch: sk_ctr into
+  // ddval), or with ctr null row `row`, into val
+  void stroke_launch(i64* ctr, i64 row, double* val) {
+    klaunch(-1, stroke_launch_bytes(), k_stroke_bc, dim3(1), dim3(BS), sk_K, (int64_t)sk_P, (int64_t)sk_start,
+            (int64_t*)ctr, (int64_t)row, (const double*)sk_amp, sk_n,
+            (const int32_t*)sk_q, (const double*)sk_shape, reinterpret_cast<const dbl2*>(sk_dir),
+            reinterpret_cast<dbl2*>(val));
+    KCHK();
+  }
+  // the stroke's part of a step, on the main stream in front of inertia_step: nothing on the side stream reads ddval
+  void stroke_step() {
+    if (stroked()) stroke_launch(sk_ctr, 0, ddval);
+  }
+  // off: the buffers freed and, with `restore`, build's values back in ddval
+  void drop_stroke(bool restore) {
+    const bool was = stroked();
+    sk_K = 0;
+    sk_P = sk_start = 0;
+    sk_n = 0;
+    if (!sk_ctr && !was) return;
+    if (st) (void)hipStreamSynchronize(st);
+    for (void* q : {(void*)sk_amp, (void*)sk_shape, (void*)sk_dir, (void*)sk_q, (void*)sk_ctr})
+      if (q) (void)hipFree(q);
+    sk_amp = sk_shape = sk_dir = nullptr;
+    sk_q = nullptr;
+    sk_ctr = nullptr;
+    if (restore && was && ddval && !dval_build.empty()) {
+      h2d(ddval, dval_build.data(), sizeof(double) * dval_build.size());
+      HIPCHK(hipStreamSynchronize(st));
+      have_vinc = 0;  // (as a force change: the boundary data of the viscous solve changed)
+    }
+  }
+  // a stroke buffer of its own (freed by drop_stroke): a copy of src, or zeros
+  template <class T>
+  T* stroke_buf(const T* src, size_t count) {
+    T* p = nullptr;
+    HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * std::max<size_t>(1, count)));
+    if (src) h2d(p, src, sizeof(T) * count);
+    else HIPCHK(hipMemsetAsync(p, 0, sizeof(T) * std::max<size_t>(1, count), st));
+    return p;
   }
 
   // ------------------------------------------------------------------ MacCormack advection (pucfem_maccormack.hpp)
@@ -3482,6 +3578,7 @@ struct Ctx {
   void stokes_step(double* rec, int32_t* its) {
     int itv = 0;
     ring_in_mix = false;
+    stroke_step();   // (the step's boundary values, in front of everything that reads ddval)
     inertia_step();  // (reads u, as the previous step's dye tail on the side stream does: no join)
     force_step();    // (buoyancy reads c^n: it joins the tail)
     viscous(itv);
@@ -5149,6 +5246,7 @@ void build(Ctx& c) {
     c.dcsrc = c.upload(cs);
     c.ddnode = c.upload(dn);
     c.ddval = c.upload(dv);
+    c.dval_build = dv;  // (what clearing a stroke restores)
     c.dbctmp = c.dalloc<double>(2 * std::max(1, c.ncopy));
     c.dspos = nullptr;  // (k_grad_proj_bc's position map follows the operators: rebuilt at the next step call)
     c.dbcsrc = c.dbcdir = nullptr;
@@ -5660,6 +5758,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     if (!c.host_only) c.drop_dyes();
     if (!c.host_only) c.drop_inertia();
     if (!c.host_only) c.drop_force();
+    if (!c.host_only) c.drop_stroke(false);
     if (!c.host_only) c.drop_advection();
     build(c);
   });
@@ -5842,8 +5941,10 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       // (a context with dye channels steps uncaptured: the channels' buffers swap every step; so does one with
       // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step; so does one
       // whose dye moves by MacCormack steps, and one with a body force: the same launches behind k_force_rhs, whose
-      // by-value terms and dye pointers change between steps)
-      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced()) {
+      // by-value terms and dye pointers change between steps; and one with a stroke: the same launches behind
+      // k_stroke_bc, so that the captured graphs stay the unstroked step's, launch for launch)
+      if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced() &&
+          !c.stroked()) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -6006,6 +6107,14 @@ void ens_enqueue_step(Ctx& c) {
   // with at least one member's inertia on: u_a = SL(u^n; u^n, dt) of those members in front, and the viscous product
   // takes it as their input (Ctx::inertia_step / Ctx::viscous of the single path)
   const bool adv = e.adv_any > 0;
+  // with at least one member stroked: those members' boundary values of this step in front of everything
+  // (Ctx::stroke_step), one block per member; the rows come from the members' counters in device memory
+  if (e.stroke_any > 0) {
+    hipLaunchKernelGGL(k_ens_stroke_bc, dim3(M), dim3(BS), 0, st, 0, (const int64_t*)e.sk_parm, e.sk_ctr, (int64_t)-1,
+                       (const double*)e.sk_tab, e.sk_n, (const int32_t*)e.sk_q, (const double*)e.sk_shape,
+                       reinterpret_cast<const dbl2*>(e.sk_dir), e.dval, (int64_t)e.dstride);
+    KCHK();
+  }
   if (adv) {
     const RedOut ra{e.vals + 10, nullptr, e.cnt_adv, 1, 0, 0u};
     hipLaunchKernelGGL(k_ens_sl_vel, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
@@ -6224,6 +6333,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     state(!c.inertia, "ensembles step without inertia: switch it off first (pucfem_set_inertia)");
     state(!c.adv_dye && !c.adv_vel,
           "ensembles step the first-order advection: switch MacCormack off first (pucfem_set_advection)");
+    state(!c.stroked(), "the context's stroke is on: clear it first (members carry their own: pucfem_ens_set_stroke)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
               c.sl_rec_wave(c.lp.n_own) && (c.scheme != PUCFEM_STOKES_FOOD || c.has_tgrid),
@@ -6299,6 +6409,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
       for (i64 g = 0; g < n; ++g) c0[m * n + g] = c.mesh.x[c.ord.new2old[g]] < 0.5 ? 1.0 : 0.0;
     }
     c.h2d(e.dval, dv.data(), sizeof(double) * dv.size());
+    e.dval0 = dv;  // (what clearing a member's stroke restores)
     c.h2d(e.u, u0.data(), sizeof(double) * u0.size());
     c.h2d(e.c, c0.data(), sizeof(double) * c0.size());
     for (size_t m = 0; m < sM && e.ntr > 0; ++m) {
@@ -6663,11 +6774,14 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     // (and for the body forces: the force launch iff a member is forced, with the nodal planes once they exist)
     // (and for MacCormack: the dye's three launches iff a member's dye scheme is on, the velocity's two iff an
     // inertial member's velocity scheme is)
+    // (and for the strokes: the stroke launch iff a member has one; pucfem_ens_set_stroke drops the graphs itself when
+    // it reallocates the tables or the shared shapes)
     if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0) || e.chain_force != (e.force_any > 0) ||
         e.chain_fnod != (e.fnod != nullptr) || e.chain_mcd != (e.mc_dye_any > 0) ||
-        e.chain_mcv != (e.mc_vel_any > 0)) {
+        e.chain_mcv != (e.mc_vel_any > 0) || e.chain_stroke != (e.stroke_any > 0)) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
+      e.chain_stroke = e.stroke_any > 0;
       e.chain_adv = e.adv_any > 0;
       e.chain_br = e.br_any > 0;
       e.chain_force = e.force_any > 0;
@@ -7719,6 +7833,281 @@ int pucfem_force_probe(void* ctx, int32_t iters, double* out2) {
     launch();  // (untimed: the first launch)
     out2[0] = time_launches(c, iters, launch);
     out2[1] = c.force_launch_bytes(c.force_mask(), c.b_n, no);
+  });
+}
+
+// ---- time-dependent strokes (pucfem_stroke.hpp)
+namespace {
+// a stroke's arguments (PUCFEM_EINVAL): the positions in the Dirichlet value array of its driven nodes
+void stroke_check(const Ctx& c, int32_t K, int32_t P, const double* amp, int32_t n, const int32_t* nodes,
+                  const double* shape, const double* dir, int64_t start, std::vector<i32>& q) {
+  require(K >= 1 && K <= STROKE_MAX_MODES, "K must be in 0 .. 8 (0 clears the stroke)");
+  require(P >= 1 && P <= STROKE_MAX_PERIOD, "P must be in 1 .. 65536");
+  require(start >= 0, "start < 0");
+  require(amp != nullptr && nodes != nullptr && shape != nullptr && dir != nullptr, "null stroke arguments");
+  require(n >= 1 && (int64_t)n <= c.mesh.N, "the count of driven nodes must be in 1 .. N");
+  auto finite = [](const double* v, size_t k) {
+    for (size_t i = 0; i < k; ++i)
+      if (!std::isfinite(v[i])) return false;
+    return true;
+  };
+  require(finite(amp, (size_t)P * K), "the table must be finite");
+  require(finite(shape, (size_t)n * K) && finite(dir, 2 * (size_t)n), "the shapes and directions must be finite");
+  const std::vector<i32> pos = c.dir_positions();
+  std::vector<char> seen((size_t)c.mesh.N, 0);
+  q.assign((size_t)n, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    require(nodes[i] >= 0 && (int64_t)nodes[i] < c.mesh.N, "a driven node is out of range");
+    require(pos[nodes[i]] >= 0, "a driven node is not in the Dirichlet list");
+    require(!seen[nodes[i]], "a driven node is listed twice");
+    seen[nodes[i]] = 1;
+    q[i] = pos[nodes[i]];
+  }
+}
+// the values of the device array val (positions) in the caller's list order: a duplicate entry gets the kept value
+void dirichlet_out(Ctx& c, const double* val, double* out) {
+  const int nc = c.dir_ncomp;
+  std::vector<double> h((size_t)nc * std::max(1, c.ndir));
+  c.d2h(h.data(), val, sizeof(double) * (size_t)nc * c.ndir);
+  const std::vector<i32> pos = c.dir_positions();
+  for (size_t k = 0; k < c.dir_nodes.size(); ++k)
+    for (int q = 0; q < nc; ++q) out[nc * k + q] = h[(size_t)nc * pos[c.dir_nodes[k]] + q];
+}
+// the members' parameters and tables as k_ens_stroke_bc reads them (members given one table share its copy); the
+// tables' buffer grows by reallocation, which drops the captured graphs
+void ens_stroke_upload(Ctx& c, Ens& e) {
+  const size_t sM = (size_t)e.M;
+  std::vector<double> tab;
+  for (size_t m = 0; m < sM; ++m) {
+    int64_t* p = e.sk_par.data() + m * ENS_STROKE_PARM;
+    p[3] = 0;
+    if (p[0] == 0) continue;
+    const std::vector<double>& t = e.sk_amp[m];
+    size_t k = 0;  // (an earlier member with an equal table: member = -1 gives every member the same one)
+    while (k < m && !(e.sk_par[k * ENS_STROKE_PARM] != 0 && e.sk_amp[k] == t)) ++k;
+    if (k < m) {
+      p[3] = e.sk_par[k * ENS_STROKE_PARM + 3];
+      continue;
+    }
+    p[3] = (int64_t)tab.size();
+    tab.insert(tab.end(), t.begin(), t.end());
+  }
+  e.stroke_any = 0;
+  for (size_t m = 0; m < sM; ++m) e.stroke_any += e.sk_par[m * ENS_STROKE_PARM] != 0 ? 1 : 0;
+  HIPCHK(hipStreamSynchronize(c.st));
+  if (tab.size() > e.sk_cap) {
+    if (e.sk_tab) {
+      (void)hipFree(e.sk_tab);
+      e.allocs.erase(std::find(e.allocs.begin(), e.allocs.end(), (void*)e.sk_tab));
+      e.bytes -= sizeof(double) * e.sk_cap;
+      e.stroke_bytes -= sizeof(double) * e.sk_cap;
+    }
+    e.sk_cap = std::max<size_t>({tab.size(), 2 * e.sk_cap, 4096});  // (room for small tables: no new capture per set)
+    e.sk_tab = e.alloc<double>(e.sk_cap, c.st);
+    e.stroke_bytes += sizeof(double) * e.sk_cap;
+    e.drop_graphs();
+  }
+  if (!tab.empty()) c.h2d(e.sk_tab, tab.data(), sizeof(double) * tab.size());
+  c.h2d(e.sk_parm, e.sk_par.data(), sizeof(int64_t) * e.sk_par.size());
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+}  // namespace
+
+int pucfem_set_stroke(void* ctx, int32_t K, int32_t P, const double* amp, int32_t n, const int32_t* nodes,
+                      const double* shape, const double* dir, int64_t start) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.stroke_ready();
+    if (K == 0) {  // (off stays off: the step's state is not touched)
+      c.drop_stroke(true);
+      return;
+    }
+    if (c.ens) throw Error(PUCFEM_ESTATE, "the context has an ensemble: its members carry their own strokes (pucfem_ens_set_stroke)");
+    std::vector<i32> q;
+    stroke_check(c, K, P, amp, n, nodes, shape, dir, start, q);
+    c.drop_stroke(true);  // (entries the new stroke does not drive hold build's values)
+    c.sk_amp = c.stroke_buf(amp, (size_t)P * K);
+    c.sk_shape = c.stroke_buf(shape, (size_t)n * K);
+    c.sk_dir = c.stroke_buf(dir, 2 * (size_t)n);
+    c.sk_q = c.stroke_buf<i32>(q.data(), (size_t)n);
+    c.sk_ctr = c.stroke_buf<i64>(nullptr, 1);
+    HIPCHK(hipStreamSynchronize(c.st));  // (the arguments are the caller's)
+    c.sk_K = K;
+    c.sk_P = P;
+    c.sk_start = start % P;
+    c.sk_n = n;
+    c.have_vinc = 0;  // (as a force change: the boundary data of the viscous solve change)
+  });
+}
+
+int pucfem_ens_set_stroke(void* ctx, int32_t member, int32_t K, int32_t P, const double* amp, int32_t n,
+                          const int32_t* nodes, const double* shape, const double* dir, int64_t start) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.stroke_ready();
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    const size_t sM = (size_t)e.M, m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : (size_t)member + 1;
+    if (K == 0) {  // off: the member's values as pucfem_ens_create uploaded them, its counter at 0
+      if (e.sk_par.empty()) return;
+      bool any = false;
+      for (size_t m = m0; m < m1; ++m) {
+        if (e.sk_par[m * ENS_STROKE_PARM] == 0) continue;
+        any = true;
+        std::fill_n(e.sk_par.begin() + m * ENS_STROKE_PARM, ENS_STROKE_PARM, (int64_t)0);
+        e.sk_amp[m].clear();
+        c.h2d(e.dval + m * e.dstride, e.dval0.data() + m * e.dstride, sizeof(double) * (size_t)e.dstride);
+        HIPCHK(hipMemsetAsync(e.sk_ctr + m, 0, sizeof(int64_t), c.st));
+      }
+      if (any) ens_stroke_upload(c, e);
+      return;
+    }
+    std::vector<i32> q;
+    stroke_check(c, K, P, amp, n, nodes, shape, dir, start, q);
+    const bool same = e.sk_n == n && e.sk_K == K && std::equal(nodes, nodes + n, e.sk_nodes.begin()) &&
+                      std::equal(shape, shape + (size_t)n * K, e.sk_shape_h.begin()) &&
+                      std::equal(dir, dir + 2 * (size_t)n, e.sk_dir_h.begin());
+    if (!same) {  // the shared shapes: those of the first call, replaced only while no member has a stroke
+      require(e.stroke_any == 0, "the shapes differ from the ensemble's: clear every member's stroke first");
+      HIPCHK(hipStreamSynchronize(c.st));
+      for (void** p : {(void**)&e.sk_shape, (void**)&e.sk_dir, (void**)&e.sk_q})
+        if (*p) {
+          (void)hipFree(*p);
+          e.allocs.erase(std::find(e.allocs.begin(), e.allocs.end(), *p));
+          *p = nullptr;
+        }
+      const size_t old = e.sk_n > 0 ? (sizeof(double) * (e.sk_K + 2) + sizeof(int32_t)) * (size_t)e.sk_n : 0;
+      e.bytes -= old;
+      e.stroke_bytes -= old;
+      const size_t before = e.bytes;
+      e.sk_shape = e.alloc<double>((size_t)n * K, c.st);
+      e.sk_dir = e.alloc<double>(2 * (size_t)n, c.st);
+      e.sk_q = e.alloc<int32_t>((size_t)n, c.st);
+      if (!e.sk_parm) {
+        e.sk_parm = e.alloc<int64_t>(sM * ENS_STROKE_PARM, c.st);
+        e.sk_ctr = e.alloc<int64_t>(sM, c.st);
+        e.sk_par.assign(sM * ENS_STROKE_PARM, 0);
+        e.sk_amp.assign(sM, {});
+      }
+      e.stroke_bytes += e.bytes - before;
+      e.sk_n = n;
+      e.sk_K = K;
+      e.sk_nodes.assign(nodes, nodes + n);
+      e.sk_shape_h.assign(shape, shape + (size_t)n * K);
+      e.sk_dir_h.assign(dir, dir + 2 * (size_t)n);
+      c.h2d(e.sk_shape, shape, sizeof(double) * (size_t)n * K);
+      c.h2d(e.sk_dir, dir, sizeof(double) * 2 * (size_t)n);
+      c.h2d(e.sk_q, q.data(), sizeof(int32_t) * (size_t)n);
+      HIPCHK(hipStreamSynchronize(c.st));
+      e.drop_graphs();  // (they hold the old arrays as kernel arguments)
+    }
+    const std::vector<double> table(amp, amp + (size_t)P * K);
+    for (size_t m = m0; m < m1; ++m) {
+      int64_t* p = e.sk_par.data() + m * ENS_STROKE_PARM;
+      p[0] = K;
+      p[1] = P;
+      p[2] = start % P;
+      e.sk_amp[m] = table;
+      HIPCHK(hipMemsetAsync(e.sk_ctr + m, 0, sizeof(int64_t), c.st));
+    }
+    ens_stroke_upload(c, e);
+  });
+}
+
+int pucfem_stroke_info(void* ctx, int32_t member, int64_t* out6) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out6 != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.stroke_ready();
+    int64_t K = c.sk_K, P = c.sk_P, start = c.sk_start, s = 0, n = c.sk_n;
+    if (member >= 0) {  // (an ensemble member's own stroke)
+      require(c.ens == nullptr || member < c.ens->M, "member index out of range");
+      Ens& e = *ens_of(c);
+      const int64_t* p = e.sk_par.empty() ? nullptr : e.sk_par.data() + (size_t)member * ENS_STROKE_PARM;
+      K = p ? p[0] : 0;
+      P = p ? p[1] : 0;
+      start = p ? p[2] : 0;
+      n = K ? e.sk_n : 0;
+      if (K) c.d2h(&s, e.sk_ctr + member, sizeof(int64_t));
+    } else if (K) {
+      c.d2h(&s, c.sk_ctr, sizeof(int64_t));
+    }
+    out6[0] = K;
+    out6[1] = P;
+    out6[2] = start;
+    out6[3] = s;
+    out6[4] = K ? (start + s) % P : 0;
+    out6[5] = n;
+  });
+}
+
+int pucfem_get_dirichlet(void* ctx, int32_t member, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.need_built();
+    if (c.dist() || c.world != 1) throw Error(PUCFEM_ESTATE, "the Dirichlet values are read on single-rank contexts");
+    c.need_dev();
+    if (member < 0) {
+      dirichlet_out(c, c.ddval, out);
+      return;
+    }
+    require(c.ens == nullptr || member < c.ens->M, "member index out of range");
+    Ens& e = *ens_of(c);
+    dirichlet_out(c, e.dval + (size_t)member * e.dstride, out);
+  });
+}
+
+int pucfem_stroke_apply(void* ctx, int32_t member, int64_t row, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.stroke_ready();
+    const size_t nd = 2 * (size_t)std::max(1, c.ndir);
+    if (member < 0) {
+      if (!c.stroked()) throw Error(PUCFEM_ESTATE, "no stroke is set");
+      require(row >= 0 && row < c.sk_P, "row must be in 0 .. P - 1");
+      double* s = c.smp_scratch<double>(22, nd + 1);
+      HIPCHK(hipMemcpyAsync(s, c.ddval, sizeof(double) * 2 * (size_t)c.ndir, hipMemcpyDeviceToDevice, c.st));
+      c.stroke_launch(nullptr, row, s);
+      dirichlet_out(c, s, out);
+      return;
+    }
+    require(c.ens == nullptr || member < c.ens->M, "member index out of range");
+    Ens& e = *ens_of(c);
+    const int64_t* p = e.sk_par.empty() ? nullptr : e.sk_par.data() + (size_t)member * ENS_STROKE_PARM;
+    if (!p || p[0] == 0) throw Error(PUCFEM_ESTATE, "the member has no stroke");
+    require(row >= 0 && row < p[1], "row must be in 0 .. P - 1");
+    double* s = c.smp_scratch<double>(22, nd + 1);
+    HIPCHK(hipMemcpyAsync(s, e.dval + (size_t)member * e.dstride, sizeof(double) * 2 * (size_t)c.ndir,
+                          hipMemcpyDeviceToDevice, c.st));
+    hipLaunchKernelGGL(k_ens_stroke_bc, dim3(1), dim3(BS), 0, c.st, member, (const int64_t*)e.sk_parm, e.sk_ctr,
+                       (int64_t)row, (const double*)e.sk_tab, e.sk_n, (const int32_t*)e.sk_q,
+                       (const double*)e.sk_shape, reinterpret_cast<const dbl2*>(e.sk_dir), s, (int64_t)e.dstride);
+    KCHK();
+    dirichlet_out(c, s, out);
+  });
+}
+
+int pucfem_stroke_probe(void* ctx, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    c.stroke_ready();
+    if (!c.stroked()) throw Error(PUCFEM_ESTATE, "no stroke is set");
+    // the step's launch (counter read, barrier, counter store) on a scratch copy of the values and a scratch counter
+    const size_t nd = 2 * (size_t)std::max(1, c.ndir);
+    double* s = c.smp_scratch<double>(22, nd + 1);
+    i64* ctr = reinterpret_cast<i64*>(s + nd);
+    HIPCHK(hipMemcpyAsync(s, c.ddval, sizeof(double) * 2 * (size_t)c.ndir, hipMemcpyDeviceToDevice, c.st));
+    HIPCHK(hipMemsetAsync(ctr, 0, sizeof(i64), c.st));
+    auto launch = [&] { c.stroke_launch(ctr, 0, s); };
+    launch();  // (untimed: the first launch)
+    out2[0] = time_launches(c, iters, launch);
+    out2[1] = c.stroke_launch_bytes();
   });
 }
 

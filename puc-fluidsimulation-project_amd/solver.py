@@ -210,6 +210,99 @@ def squirmer_values(coords, inner, B1, B2, center=(0.5, 0.5)):
     return np.stack([vt * -np.sin(th), vt * np.cos(th)], 1)
 
 
+def stroke_geometry(coords, inner, K, center=(0.5, 0.5)):
+    """(shape (n, K), dir (n, 2)) of a stroke's driven nodes `inner`: shape[:, j] = sin((j + 1) theta) and
+    dir = (-sin theta, cos theta), formed with the numpy lines of squirmer_values, so that a table row (B1, B2) gives
+    that function's bits."""
+    X = np.asarray(coords, dtype=np.float64)
+    rx = X[inner, 0] - center[0]
+    ry = X[inner, 1] - center[1]
+    th = np.arctan2(ry, rx)
+    shape = np.stack([np.sin((j + 1) * th) for j in range(K)], 1)
+    return np.ascontiguousarray(shape), np.ascontiguousarray(np.stack([-np.sin(th), np.cos(th)], 1))
+
+
+class Stroke:
+    """A time-dependent stroke of the squirmer: a periodic table of mode amplitudes, one row per step.  table is
+    (P, K) float64, 1 <= P <= 65536 rows and 1 <= K <= 8 modes; column j drives sin((j + 1) theta), so columns 0 and 1
+    are B1 and B2 of SquirmerBC.  The k-th step after the stroke was set (k = 0 the first) imposes row
+    (start + k) mod P: v_t = sum_j table[row, j] sin((j + 1) theta) along the tangent, the products summed in the
+    order of j."""
+
+    def __init__(self, table, start=0):
+        t = np.array(table, dtype=np.float64)
+        if t.ndim != 2:
+            raise ValueError(f"stroke: the table is (P, K), got shape {t.shape}")
+        P, K = t.shape
+        if not 1 <= K <= _lib.STROKE_MAX_MODES:
+            raise ValueError(f"stroke: 1 .. {_lib.STROKE_MAX_MODES} modes, got K = {K}")
+        if not 1 <= P <= _lib.STROKE_MAX_PERIOD:
+            raise ValueError(f"stroke: 1 .. {_lib.STROKE_MAX_PERIOD} rows, got P = {P}")
+        if not np.all(np.isfinite(t)):
+            raise ValueError("stroke: the table must be finite")
+        if int(start) != start or int(start) < 0:
+            raise ValueError("stroke: start is a row count >= 0")
+        self.table = np.ascontiguousarray(t)
+        self.table.setflags(write=False)
+        self.start = int(start)
+
+    @property
+    def P(self):
+        return self.table.shape[0]
+
+    @property
+    def K(self):
+        return self.table.shape[1]
+
+    def row(self, k):
+        """The table row the k-th step imposes."""
+        return (self.start + int(k)) % self.P
+
+    def amplitudes(self, k):
+        """The amplitudes (K,) the k-th step imposes."""
+        return self.table[self.row(k)].copy()
+
+    @classmethod
+    def constant(cls, B1, B2):
+        """The steady squirmer SquirmerBC(B1, B2) as a stroke: the same boundary bits at every step."""
+        return cls([[B1, B2]])
+
+    @classmethod
+    def harmonic(cls, period, B1=(0.0, 0.0, 0.0), B2=(0.0, 0.0, 0.0), *modes, start=0):
+        """Each mode a (mean, amp, phase): row k holds mean + amp * np.sin(2 * np.pi * (k + 1) / period + phase)."""
+        if int(period) != period or period < 1:
+            raise ValueError("stroke: period is a row count >= 1")
+        k = np.arange(int(period), dtype=np.float64)
+        cols = []
+        for mode in (B1, B2) + tuple(modes):
+            mean, amp, phase = (float(v) for v in mode)
+            cols.append(mean + amp * np.sin(2 * np.pi * (k + 1) / period + phase))
+        return cls(np.stack(cols, 1), start)
+
+    @classmethod
+    def blinking(cls, period, a, b, duty=0.5, start=0):
+        """Piecewise constant: the first round(duty * period) rows hold the amplitudes a, the others b (a pusher /
+        puller alternation: a = (B1, -B2), b = (B1, +B2))."""
+        if int(period) != period or period < 1:
+            raise ValueError("stroke: period is a row count >= 1")
+        a, b = np.asarray(a, dtype=np.float64).reshape(-1), np.asarray(b, dtype=np.float64).reshape(-1)
+        if a.shape != b.shape:
+            raise ValueError("stroke: the two amplitude tuples have one length")
+        if not 0.0 <= duty <= 1.0:
+            raise ValueError("stroke: duty is in [0, 1]")
+        na = int(round(duty * int(period)))
+        return cls(np.stack([a] * na + [b] * (int(period) - na), 0), start)
+
+    def __repr__(self):
+        return f"Stroke(P={self.P}, K={self.K}, start={self.start})"
+
+
+def _check_stroke(stroke):
+    if stroke is not None and not isinstance(stroke, Stroke):
+        raise ValueError("stroke must be a Stroke or None")
+    return stroke
+
+
 @dataclass
 class Tolerances:
     rtol_visc: float = 1e-13
@@ -637,6 +730,57 @@ class Context:
         self._c(self.L.pucfem_force_probe(self.h, int(iters), o))
         return dict(kernel_ms=o[0], algo_bytes=o[1])
 
+    # ---- time-dependent strokes (pucfem_set_stroke)
+    def set_stroke(self, stroke, nodes=None, shape=None, dirs=None, member=None):
+        """The stroke of the context's steps (member=None, pucfem_set_stroke) or of ensemble member `member` (-1: all;
+        pucfem_ens_set_stroke): a Stroke with the driven nodes (caller numbering), their shapes (n, K) and directions
+        (n, 2), or None to clear it."""
+        if stroke is None:
+            if member is None:
+                self._c(self.L.pucfem_set_stroke(self.h, 0, 0, None, 0, None, None, None, 0))
+            else:
+                self._c(self.L.pucfem_ens_set_stroke(self.h, int(member), 0, 0, None, 0, None, None, None, 0))
+            return
+        nd = np.ascontiguousarray(nodes, dtype=np.int32)
+        sh = np.ascontiguousarray(shape, dtype=np.float64)
+        dr = np.ascontiguousarray(dirs, dtype=np.float64)
+        if sh.shape != (len(nd), stroke.K) or dr.shape != (len(nd), 2):
+            raise ValueError(f"stroke: shapes ({len(nd)}, {stroke.K}) and directions ({len(nd)}, 2), got {sh.shape} "
+                             f"and {dr.shape}")
+        args = (stroke.K, stroke.P, _lib.dptr(stroke.table), len(nd), _lib.iptr(nd), _lib.dptr(sh), _lib.dptr(dr),
+                stroke.start)
+        if member is None:
+            self._c(self.L.pucfem_set_stroke(self.h, *args))
+        else:
+            self._c(self.L.pucfem_ens_set_stroke(self.h, int(member), *args))
+
+    def stroke_info(self, member=-1):
+        """pucfem_stroke_info of the context (member=-1) or an ensemble member: modes K (0: off), period P, start row,
+        steps taken since the stroke was set, the row the next step imposes, driven nodes."""
+        o = (ct.c_int64 * 6)()
+        self._c(self.L.pucfem_stroke_info(self.h, int(member), o))
+        return dict(K=int(o[0]), P=int(o[1]), start=int(o[2]), steps=int(o[3]), row=int(o[4]), nodes=int(o[5]))
+
+    def get_dirichlet(self, count, ncomp=2, member=-1):
+        """The Dirichlet values the device holds now, (count, ncomp) in the order of the list given to set_dirichlet
+        (pucfem_get_dirichlet)."""
+        out = np.zeros((int(count), ncomp) if ncomp > 1 else (int(count),))
+        self._c(self.L.pucfem_get_dirichlet(self.h, int(member), _lib.dptr(out)))
+        return out
+
+    def stroke_apply(self, row, count, member=-1):
+        """Row `row` of the stroke through the step's kernel on a scratch copy of the Dirichlet values
+        (pucfem_stroke_apply), (count, 2) in the list's order; nothing of the step's state is touched."""
+        out = np.zeros((int(count), 2))
+        self._c(self.L.pucfem_stroke_apply(self.h, int(member), int(row), _lib.dptr(out)))
+        return out
+
+    def stroke_probe(self, iters=10):
+        """Kernel time of one k_stroke_bc launch with the current stroke (pucfem_stroke_probe; tools/stroke_bench.py)."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_stroke_probe(self.h, int(iters), o))
+        return dict(kernel_ms=o[0], algo_bytes=o[1])
+
     def set_advection(self, what, scheme):
         """The advection scheme (pucfem_set_advection) of the dye (what = ADV_DYE), of the inertial step's velocity
         (ADV_VELOCITY) or of both (their sum): 'sl' the reference's first-order step, 'maccormack' two of them and
@@ -756,8 +900,9 @@ class StokesSimulation:
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
                  tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl",
-                 tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None):
+                 tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None, stroke=None):
         adv = advection_scheme(advection)
+        _check_stroke(stroke)
         f_const, f_field = _force_args(force, mesh.N)
         if buoyancy is not None and not isinstance(buoyancy, Buoyancy):
             raise ValueError("buoyancy must be a Buoyancy or None")
@@ -776,6 +921,8 @@ class StokesSimulation:
         self.ctx.upload(mesh)
         pairs, nodes, vals = stokes_setup(mesh, self.bc)
         self.pairs = pairs
+        self.dirichlet_nodes = nodes
+        self._stroke = None
         self.ctx.set_pairs(0, pairs)
         self.ctx.set_pairs(1, pairs)
         self.ctx.set_dirichlet(nodes, vals)
@@ -805,9 +952,42 @@ class StokesSimulation:
                 self.set_force(f_const, f_field)
             if buoyancy is not None:
                 self.buoyancy = buoyancy
+            if stroke is not None:
+                self.stroke = stroke
         except Exception:
             self.ctx.close()
             raise
+
+    # ---- time-dependent strokes: the squirmer's boundary values per step
+    @property
+    def stroke(self):
+        """The Stroke of the steps, or None: every step imposes the squirmer values of its table row -- v_t =
+        sum_j amp[row, j] sin((j + 1) theta) along the tangent -- where a plain run holds SquirmerBC.B1 / B2 fixed.
+        The walls keep their values.  Setting it does not touch u and starts the stroke's step count at 0; None
+        restores the values of SquirmerBC.B1 / B2.  A stroked step is the static step of its row's amplitudes, taken
+        from the same fields; a small-mesh run steps uncaptured while a stroke is set."""
+        return self._stroke
+
+    @stroke.setter
+    def stroke(self, stroke):
+        _check_stroke(stroke)
+        if stroke is None:
+            self.ctx.set_stroke(None)
+        else:
+            inner = boundary_sets(self.mesh.coords, self.mesh.markers)[1]
+            shape, dirs = stroke_geometry(self.mesh.coords, inner, stroke.K, self.bc.center)
+            self.ctx.set_stroke(stroke, inner, shape, dirs)
+        self._stroke = stroke
+
+    def stroke_info(self):
+        """Context.stroke_info of this run: K (0: off), P, start, the steps taken since the stroke was set, the row
+        the next step imposes, the driven nodes."""
+        return self.ctx.stroke_info()
+
+    @property
+    def boundary_values(self):
+        """(nodes, values): the Dirichlet nodes and the (n, 2) values the device holds for them now."""
+        return self.dirichlet_nodes.copy(), self.ctx.get_dirichlet(len(self.dirichlet_nodes))
 
     # ---- body forces: r = base + dt * f in front of the viscous solve
     def set_force(self, constant=None, field=None):
@@ -1078,6 +1258,21 @@ def _ensemble_diffusion(tracer_diffusivity, tracer_seed, M):
     return np.broadcast_to(d, (M,)).copy(), seeds
 
 
+def _ensemble_strokes(stroke, M):
+    """The stroke= argument of an ensemble of M members checked: None, one Stroke for all, or M entries each a Stroke
+    or None, all of one K."""
+    if stroke is None or isinstance(stroke, Stroke):
+        return
+    if not isinstance(stroke, (list, tuple)):
+        raise ValueError("stroke must be a Stroke, None, or a list with one Stroke or None per member")
+    if len(stroke) != M:
+        raise ValueError(f"stroke: one entry per member: {M} members, got {len(stroke)}")
+    for s in stroke:
+        _check_stroke(s)
+    if len({s.K for s in stroke if s is not None}) > 1:
+        raise ValueError("stroke: the strokes of an ensemble have one number of modes K (the shapes are shared)")
+
+
 def _ensemble_advection(advection):
     """The advection= keyword of ensembles takes 'sl' alone: members carry a dye scheme and a velocity scheme each."""
     if advection_scheme(advection) != 0:
@@ -1131,11 +1326,12 @@ class StokesEnsemble:
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
                  tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
-                 buoyancy=None, dye_advection="sl", velocity_advection="sl"):
+                 buoyancy=None, dye_advection="sl", velocity_advection="sl", stroke=None):
         _ensemble_advection(advection)
         if buoyancy is not None and scheme != "color":
             raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
         self.bcs = _check_ensemble_bcs(bcs)
+        _ensemble_strokes(stroke, len(self.bcs))
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
         flags = _ensemble_flags(inertia, len(self.bcs))
@@ -1179,6 +1375,8 @@ class StokesEnsemble:
                 self.set_force(force)
             if buoyancy is not None:
                 self.set_buoyancy(buoyancy)
+            if stroke is not None:
+                self.set_stroke(stroke)
         except Exception:
             self.ctx.close()
             raise
@@ -1318,6 +1516,46 @@ class StokesEnsemble:
     @velocity_advection.setter
     def velocity_advection(self, scheme):
         self._set_schemes(_lib.ADV_VELOCITY, scheme, "velocity_advection")
+
+    # ---- time-dependent strokes per member (pucfem_ens_set_stroke)
+    def set_stroke(self, stroke, member=None):
+        """The Stroke of one member, or (member=None) of all: a Stroke or None -- or, member=None, a list with one
+        such entry per member.  Every stroke of an ensemble has one number of modes K (the shapes are shared).  A
+        stroked member steps as StokesSimulation(..., stroke=) does, bit for bit, from its own start row and step
+        count; a member without one keeps its SquirmerBC values.  It takes effect at the next step."""
+        def one(s, m):
+            _check_stroke(s)
+            if s is None:
+                return self.ctx.set_stroke(None, member=m)
+            inner = boundary_sets(self.mesh.coords, self.mesh.markers)[1]
+            shape, dirs = stroke_geometry(self.mesh.coords, inner, s.K, self.bcs[0].center)
+            self.ctx.set_stroke(s, inner, shape, dirs, member=m)
+
+        if member is not None:
+            return one(stroke, int(member))
+        if isinstance(stroke, (list, tuple)):
+            _ensemble_strokes(stroke, self.M)
+            for m, s in enumerate(stroke):
+                if s is None:
+                    one(None, m)
+            for m, s in enumerate(stroke):
+                if s is not None:
+                    one(s, m)
+        else:
+            one(stroke, -1)
+
+    def stroke_info(self, member=None):
+        """pucfem_stroke_info per member: K (0: off), P, start, the steps its stroke has taken, the row its next step
+        imposes, the driven nodes -- one member's dict, or (member=None) a dict of (M,) arrays."""
+        if member is not None:
+            return self.ctx.stroke_info(int(member))
+        rows = [self.ctx.stroke_info(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in rows[0]}
+
+    def boundary_values(self, member):
+        """(nodes, values) of one member: the Dirichlet nodes and the (n, 2) values the device holds for them now."""
+        nodes = stokes_setup(self.mesh, self.bcs[0])[1]
+        return nodes, self.ctx.get_dirichlet(len(nodes), member=int(member))
 
     # ---- body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy)
     def set_force(self, force, member=None):
@@ -1515,20 +1753,21 @@ class StokesEnsemble:
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
                    inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
-                   dye_advection="sl", velocity_advection="sl"):
+                   dye_advection="sl", velocity_advection="sl", stroke=None):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
     'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
     would not say which of the two).  tracer_diffusivity, tracer_seed: one value for all members or one per member
     (StokesEnsemble.set_tracer_diffusion).  force, buoyancy: one setting for all members or a list with one per
-    member (StokesEnsemble.set_force / set_buoyancy)."""
+    member (StokesEnsemble.set_force / set_buoyancy).  stroke: a Stroke for all members or a list with one Stroke or
+    None per member (StokesEnsemble.set_stroke)."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
     ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia, tracer_diffusivity=tracer_diffusivity,
                          tracer_seed=tracer_seed, force=force, buoyancy=buoyancy, dye_advection=dye_advection,
-                         velocity_advection=velocity_advection)
+                         velocity_advection=velocity_advection, stroke=stroke)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
@@ -1666,7 +1905,7 @@ class Result:
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
           tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
-          tracer_seed=0, force=None, buoyancy=None):
+          tracer_seed=0, force=None, buoyancy=None, stroke=None):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -1680,7 +1919,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     tracer_diffusivity, tracer_seed (schemes 'color' and 'food'): Brownian tracers, a random walk of that diffusivity
     per tracer and step on top of the move, reproducible from the seed (StokesSimulation.tracer_diffusivity).
     force, buoyancy (schemes 'color' and 'food'; buoyancy 'color'): the body force of the steps, a pair, an (N, 2)
-    field or None, and the Buoyancy of the dye (StokesSimulation.force / buoyancy; its terms may name the dyes=)."""
+    field or None, and the Buoyancy of the dye (StokesSimulation.force / buoyancy; its terms may name the dyes=).
+    stroke (schemes 'color' and 'food'): a Stroke, the squirmer's boundary values per step (StokesSimulation.stroke)."""
+    if stroke is not None and scheme not in ("color", "food"):
+        raise ValueError("stroke belongs to the Stokes schemes 'color' and 'food'")
+    _check_stroke(stroke)
     if force is not None and scheme not in ("color", "food"):
         raise ValueError("force belongs to the Stokes schemes 'color' and 'food'")
     if buoyancy is not None and scheme != "color":
@@ -1697,7 +1940,8 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
         bc = bc or (SquirmerBC() if scheme == "color" else SquirmerBC(nu=1.0))
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
         sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection,
-                               tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed, force=force)
+                               tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed, force=force,
+                               stroke=stroke)
         if dyes is not None:
             sim.dyes = dyes
         if buoyancy is not None:  # (behind the channels its terms may name)
