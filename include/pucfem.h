@@ -597,6 +597,66 @@ int pucfem_ens_set_advection(void* ctx, int32_t member /* -1 = all */, int32_t w
    scheme (for the velocity: or the inertia flag) is off -- [10] device bytes the ensemble holds for MacCormack */
 int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11);
 
+/* ---- midpoint trajectories: second-order back-traces and tracer steps --- */
+/* Every transported thing follows one straight step of the velocity at its starting point (PUCFEM_TRJ_EULER, the
+   default: X - dt u(X) for a semi-Lagrangian row, p + dt v(p) for a tracer).  With PUCFEM_TRJ_MIDPOINT the velocity is
+   read again half a step along that trace and the whole step is taken with it.  Every product and sum as written
+   (the library is built with -ffp-contract=off); hdt = 0.5 * dt is formed on the host.
+   Fields, per row g with v = u[g] (sl_point, sl_locate_row, sl_value: pucfem_locate.hpp):
+       (xm, ym) = sl_point(X_g, v, hdt);          okm = sl_locate_row(g, v, (xm, ym)) -> Tm
+       w        = okm ? sl_value(Tm, (xm, ym), u as interleaved pairs) : v
+       (xb, yb) = sl_point(X_g, w, dt);           ok  = sl_locate_row(g, w, (xb, yb)) -> T
+       value    = ok ? sl_value(T, (xb, yb), field) : field[g]
+   A row whose midpoint is not found is an Euler row (counted, and marked by the unit operations).  The second locate
+   is keyed on w.  That is, bit for bit, W = pucfem_sl_advect_vel(f = u, u, 0.5 * dt) followed by
+   pucfem_sl_advect_multi(c, W, dt) (pucfem_sl_advect_vel(f, W, dt) for a pair field), in one launch, with w in
+   registers.  With MacCormack (pucfem_set_advection) pass 1 is the above and T1 its final triangle; pass 2 is the same
+   from the same node with -dt and -hdt (the midpoint read from u, the value from ch); the clamp is unchanged.
+   Tracers, per tracer at p with (vx, vy) interpolated there (NaN outside the mesh):
+       mx = py_mod(px + vx * hdt, 1.0);  my = py + vy * hdt
+       (wx, wy) = the velocity interpolated at (mx, my); outside the mesh (or not finite): (wx, wy) = (vx, vy)
+   and then the move (with or without the Brownian increment) with (wx, wy) in place of (vx, vy).  The capture test,
+   the capture step, the Philox counters and the wall reflection are untouched.
+   what is a mask: PUCFEM_TRJ_DYE moves c and the dye channels of every pucfem_step this way (readiness as
+   pucfem_set_advection's PUCFEM_ADV_DYE; one launch where the Euler step has k_sl and k_sl_multi, one per pass with
+   MacCormack), with the same mixing sums, and sl_notfound the final locate's count; PUCFEM_TRJ_VELOCITY the inertial
+   step's u_a (readiness as pucfem_set_inertia; it waits for inertia); PUCFEM_TRJ_TRACERS the tracers of a
+   single-rank PUCFEM_STOKES_FOOD context, in pucfem_step and in pucfem_tracer_step (which follows the setting with
+   its own dt).  Else PUCFEM_ESTATE (multi-rank, heat, Poisson, the implicit dye or STOKES_FOOD for PUCFEM_TRJ_DYE, a
+   context without tracers for PUCFEM_TRJ_TRACERS; before the build; while the context has an ensemble, for either
+   order, and pucfem_ens_create while a part is on: members trace Euler steps) -- decided before the device is asked
+   for --; PUCFEM_EINVAL for an unknown mask or order; PUCFEM_ENODEV on a host-only context.  With PUCFEM_TRJ_EULER a
+   context steps as if this call did not exist, launch for launch.  A part holds the blocks' counts only, allocated
+   when it is first switched on and freed by pucfem_build_operators and pucfem_ctx_destroy, which also set every part
+   back to PUCFEM_TRJ_EULER.  Switching the velocity's order resets the viscous solve's extrapolation history.  A
+   small-mesh context steps uncaptured while a part is on and from its captured graph again when all are off.  The
+   trace uses the step's one frozen u: second order along a steady flow, first order in the flow's change in time. */
+enum { PUCFEM_TRJ_DYE = 1, PUCFEM_TRJ_VELOCITY = 2, PUCFEM_TRJ_TRACERS = 4 };
+enum { PUCFEM_TRJ_EULER = 1, PUCFEM_TRJ_MIDPOINT = 2 };
+int pucfem_set_trajectory(void* ctx, int32_t what /* bit mask */, int32_t order);
+/* out[0..2] the orders of the dye, the velocity, the tracers; [3..5] the steps each has taken with its part on since
+   it was switched on; [6] of the last dye launch with the part on, the rows whose midpoint was not found (with
+   MacCormack: of both passes), [7] the same of the last velocity launch, [8] of the last tracer launch the tracers
+   that had a velocity and whose midpoint left the mesh; [9] device bytes held.  Readiness as pucfem_inertia_info. */
+int pucfem_trajectory_info(void* ctx, int64_t* out10);
+/* Unit operations on scratch buffers (the step's state is not touched): one step of nch plain fields, or of one pair
+   field, along the trajectory `order` with the scheme PUCFEM_ADV_SL or PUCFEM_ADV_MACCORMACK.  marks (N or NULL):
+   bit 0 the final back-trace found no triangle, bit 1 the forward trace found none (MacCormack only), bit 2 pass 1's
+   midpoint was not found, bit 3 pass 2's.  tri (N or NULL): T1 (MacCormack), else -1.  With PUCFEM_TRJ_EULER they
+   return the bits of pucfem_sl_advect_multi / _vel / _mc / _vel_mc.  Readiness as those; PUCFEM_EINVAL for an unknown
+   order or scheme. */
+int pucfem_sl_advect_traj(void* ctx, int32_t order, int32_t scheme /* PUCFEM_ADV_* */, int32_t nch,
+                          const double* c /* nch x N */, const double* u, double dt, double* c_out /* nch x N */,
+                          int32_t* marks /* N or NULL */, int32_t* tri /* N or NULL */);
+int pucfem_sl_advect_vel_traj(void* ctx, int32_t order, int32_t scheme, const double* f /* N x 2 */,
+                              const double* u /* N x 2 */, double dt, double* f_out /* N x 2 */,
+                              int32_t* marks /* N or NULL */, int32_t* tri /* N or NULL */);
+/* Measurement, as pucfem_advection_probe: the fused midpoint launches on the context's current u and dt with scratch
+   buffers -- what = PUCFEM_TRJ_DYE: nch zero fields; PUCFEM_TRJ_VELOCITY: f = u (nch ignored).  out4: milliseconds
+   per launch of pass 1 (the whole step with PUCFEM_ADV_SL), of pass 2 (0 with PUCFEM_ADV_SL), algorithmic bytes of
+   each. */
+int pucfem_trajectory_probe(void* ctx, int32_t what, int32_t scheme, int32_t nch, int32_t iters, double* out4);
+
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,
    good_visualization.py:738).  These calls integrate the context's current u from caller-given seeds with the

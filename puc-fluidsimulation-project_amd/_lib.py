@@ -30,6 +30,9 @@ STROKE_MAX_MODES, STROKE_MAX_PERIOD = 8, 65536  # pucfem_set_stroke: K and P at 
 ADV_DYE, ADV_VELOCITY = 1, 2  # pucfem_set_advection: what (a mask)
 ADV_SL, ADV_MACCORMACK = 0, 1  # ... and the scheme
 MC_NO_BACK, MC_NO_FWD = 1, 2  # marks of pucfem_sl_advect_mc
+TRJ_DYE, TRJ_VELOCITY, TRJ_TRACERS = 1, 2, 4  # pucfem_set_trajectory: what (a mask)
+TRJ_EULER, TRJ_MIDPOINT = 1, 2  # ... and the order
+TRJ_NO_MID1, TRJ_NO_MID2 = 4, 8  # marks of pucfem_sl_advect_traj beside MC_NO_BACK / MC_NO_FWD
 OP_K, OP_VISC, OP_PRES, OP_GX, OP_GY, OP_DIV, OP_GRAD, OP_LIT, OP_MCONS, OP_MLUMP, OP_ASUM = range(11)
 OP_CURL = 11
 SLN_UNIT, SLN_EULER, SLN_BOTH = 1, 2, 4  # pucfem_streamline_flag
@@ -144,6 +147,11 @@ SIGNATURES = {
     "pucfem_sl_advect_mc": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
     "pucfem_sl_advect_vel_mc": ([_P, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
     "pucfem_advection_probe": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, _D], ct.c_int),
+    "pucfem_set_trajectory": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
+    "pucfem_trajectory_info": ([_P, _I64], ct.c_int),
+    "pucfem_sl_advect_traj": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
+    "pucfem_sl_advect_vel_traj": ([_P, ct.c_int32, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),
+    "pucfem_trajectory_probe": ([_P, ct.c_int32, ct.c_int32, ct.c_int32, ct.c_int32, _D], ct.c_int),
     "pucfem_ens_set_advection": ([_P, ct.c_int32, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_ens_advection_info": ([_P, ct.c_int32, _I64], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),

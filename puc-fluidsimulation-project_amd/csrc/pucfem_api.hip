@@ -33,6 +33,7 @@
 #include "pucfem_inertia.hpp"
 #include "pucfem_force.hpp"
 #include "pucfem_maccormack.hpp"
+#include "pucfem_trajectory.hpp"
 #include "pucfem_stroke.hpp"
 
 using namespace pucfem;
@@ -653,7 +654,9 @@ struct Ctx {
   // intermediate fields, the records, the marks, the triangle ids, pass 2's counts
   // Slot 22: pucfem_stroke_apply / pucfem_stroke_probe (pucfem_stroke.hpp): a copy of the Dirichlet values and, behind
   // it, the probe's counter
-  static constexpr int SMP_SLOTS = 23;
+  // Slot 23: pucfem_sl_advect_traj / pucfem_sl_advect_vel_traj / pucfem_trajectory_probe (pucfem_trajectory.hpp): the
+  // blocks' midpoint counts of the two passes (they share slots 14..21 with the operations above)
+  static constexpr int SMP_SLOTS = 24;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -886,6 +889,7 @@ struct Ctx {
       drop_force();
       drop_stroke(false);
       drop_advection();
+      drop_trajectory();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1297,7 +1301,19 @@ struct Ctx {
   // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity)
   void inertia_step() {
     if (!inertia) return;
-    if (adv_vel) {
+    if (trj_vel == PUCFEM_TRJ_MIDPOINT) {  // (the fused launches, into the Euler step's buffers and counts)
+      if (adv_vel) {
+        trj_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, mcv_ch, u_adv, mcv_rec, nullptr, nullptr, adv_nfpart, mcv_cnt,
+                       trjv_mid);
+        mcv_nb = nb_dye(lp.n_own);
+        ++mcv_steps;
+      } else {
+        trj_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, nullptr, nullptr, nullptr, adv_nfpart, nullptr,
+                       trjv_mid, 1);
+      }
+      trjv_nb = nb_dye(lp.n_own);
+      ++trjv_steps;
+    } else if (adv_vel) {
       mc_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, mcv_ch, u_adv, mcv_rec, nullptr, nullptr, adv_nfpart, mcv_cnt);
       mcv_nb = nb_dye(lp.n_own);
       ++mcv_steps;
@@ -1717,6 +1733,203 @@ struct Ctx {
     if (mc_ch) b += sizeof(double) * (size_t)mc_fields * N;
     if (mc_rec) b += sizeof(int4) * N + sizeof(int32_t) * 4 * SLB + sizeof(double) * SLB;
     if (mcv_rec) b += sizeof(double) * 2 * N + sizeof(int4) * N + sizeof(int32_t) * 3 * SLB;
+    return b;
+  }
+
+  // ------------------------------------------------------------------ midpoint trajectories (pucfem_trajectory.hpp)
+  // pucfem_set_trajectory: the dye (c and its channels), the inertial step's velocity and the tracers follow the
+  // midpoint trace instead of one straight step.  The fields keep their buffers (the dye's channel sets, u_adv, the
+  // MacCormack sets): a part that is on launches k_trj_* where the Euler step launches k_sl / k_sl_multi / k_sl_vel /
+  // k_mc_*, one launch per pass.  What a part holds of its own are the blocks' counts, allocated when it is first
+  // switched on and freed by drop_trajectory (they are not in `allocs`).
+  int trj_dye = PUCFEM_TRJ_EULER, trj_vel = PUCFEM_TRJ_EULER, trj_trc = PUCFEM_TRJ_EULER;
+  int32_t* trjd_mid = nullptr;     // dye: the blocks' midpoint-not-found rows, pass 1 then pass 2 (2 x SLB)
+  int32_t* trjd_nfpart = nullptr;  // ... final not-found rows where no other buffer takes them (SLB)
+  double* trjd_nfd = nullptr;      // ... as doubles, for the step record (SLB)
+  int32_t* trjv_mid = nullptr;     // velocity: as trjd_mid (2 x SLB)
+  int32_t* trjt_fell = nullptr;    // tracers: the last launch's count (1)
+  int trjd_nb = 0, trjv_nb = 0;    // blocks of the last dye / velocity launch with the part on (0: none)
+  bool trjt_ran = false;
+  i64 trjd_steps = 0, trjv_steps = 0, trjt_steps = 0;
+  bool trj_any() const {
+    return trj_dye == PUCFEM_TRJ_MIDPOINT || trj_vel == PUCFEM_TRJ_MIDPOINT || trj_trc == PUCFEM_TRJ_MIDPOINT;
+  }
+  // a fused pass reads what the composition's two launches read, less the midpoint velocity's store and load (32 B)
+  double trj_bytes1(int nf, i64 n, bool rec) const {
+    return dye_launch_bytes(nf, n) + vel_launch_bytes(n) - 32.0 * (double)n + (rec ? 16.0 * (double)n : 0.0);
+  }
+  double trj_bytes2(int nf, i64 n) const { return mc_bytes2(nf, n) + vel_launch_bytes(n) - 32.0 * (double)n; }
+  double trjv_bytes1(i64 n, bool rec) const {
+    return 2.0 * vel_launch_bytes(n) - 32.0 * (double)n + (rec ? 16.0 * (double)n : 0.0);
+  }
+  double trjv_bytes2(i64 n) const { return mcv_bytes2(n) + vel_launch_bytes(n) - 32.0 * (double)n; }
+  // the single-rank STOKES_FOOD context the tracers live on
+  void tracers_ready() const {
+    need_built();
+    auto state = [](bool ok, const char* msg) {
+      if (!ok) throw Error(PUCFEM_ESTATE, msg);
+    };
+    state(scheme == PUCFEM_STOKES_FOOD, "tracer trajectories need a STOKES_FOOD context (the tracers)");
+    state(!dist() && world == 1, "midpoint trajectories are single-rank (the midpoint would need a wide halo of u)");
+    need_dev();
+    state(has_tgrid, "the context has no tracer grid");
+  }
+  // k_trj_fwd / k_trj_bwd over rows [row0, row0 + n) of a single-rank context (u2: the full mesh's pairs)
+  void trj_fwd(i64 row0, i64 n, const double* u2, double dt, const double* c0, double* ch0, int nch, const double* cin,
+               double* chout, int4* rec, int32_t* marks, int32_t* nfpart, double* nfd, int32_t* mid) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
+    const double hdt = 0.5 * dt;
+    with_loc([&](const auto& L) {
+      klaunch(-1, trj_bytes1(nch + (c0 ? 1 : 0), n, rec != nullptr), k_trj_fwd<std::decay_t<decltype(L)>>, dim3(nb),
+              dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, c0, ch0, (int32_t)nch, cin, chout,
+              (int64_t)mesh.N, rec, marks, nfpart, nfd, mid);
+    });
+    KCHK();
+  }
+  void trj_bwd(i64 row0, i64 n, const double* u2, double dt, const double* c0, const double* ch0, double* out0, int nch,
+               const double* cin, const double* ch, double* cout, const int4* rec, int32_t* marks, int32_t* tri,
+               int32_t* cnt, int32_t* mid) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
+    const double hdt = 0.5 * dt;
+    with_loc([&](const auto& L) {
+      klaunch(-1, trj_bytes2(nch + (c0 ? 1 : 0), n), k_trj_bwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L,
+              cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, c0, ch0, out0, (int32_t)nch, cin, ch, cout, (int64_t)mesh.N,
+              rec, marks, tri, cnt, mid);
+    });
+    KCHK();
+  }
+  // the pair form: pass & 1 k_trj_fwd_vel (f -> ch; the whole of a one-pass step), pass & 2 k_trj_bwd_vel (-> out)
+  void trj_vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* ch2, double* out2,
+                      int4* rec, int32_t* marks, int32_t* tri, int32_t* nfpart, int32_t* cnt, int32_t* mid,
+                      int pass = 3) {
+    const MeshDev M{mx, my, mtri, mesh.T};
+    const int nb = nb_dye(n);
+    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
+    const dbl2* f = reinterpret_cast<const dbl2*>(f2);
+    dbl2* ch = reinterpret_cast<dbl2*>(ch2);
+    dbl2* out = reinterpret_cast<dbl2*>(out2);
+    const double hdt = 0.5 * dt;
+    with_loc([&](const auto& L) {
+      if (pass & 1)
+        klaunch(-1, trjv_bytes1(n, rec != nullptr), k_trj_fwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L,
+                cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, f, ch, rec, marks, nfpart, mid);
+      if (pass & 2)
+        klaunch(-1, trjv_bytes2(n), k_trj_bwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
+                (int64_t)row0, (int64_t)n, u, dt, hdt, f, (const dbl2*)ch, out, (const int4*)rec, marks, tri, cnt,
+                mid + SLB);
+    });
+    KCHK();
+  }
+  // the dye's part of a step with the midpoint on, where sl_launch + dyes_step or mc_dye_step stand (their stream,
+  // their buffers, the step's final u): c_full -> cnew, the channels dye_cur -> dye_nxt (swapped here), k_wsum's
+  // mixing sums of cnew into part_sl
+  void trj_dye_step(double* cnew) {
+    const i64 n = lp.n_own, N = mesh.N;
+    int32_t* nfp = ndye ? dye_nfpart : trjd_nfpart;
+    if (adv_dye) {
+      trj_fwd(lp.r0, n, ux, prm.dt, c_full, mc_ch, ndye, dye_cur, mc_ch + N, mc_rec, nullptr, nfp, trjd_nfd, trjd_mid);
+      trj_bwd(lp.r0, n, ux, prm.dt, c_full, mc_ch, cnew, ndye, dye_cur, mc_ch + N, dye_nxt, mc_rec, nullptr, nullptr,
+              mc_cnt, trjd_mid + SLB);
+      mc_nb = nb_dye(n);
+      ++mc_steps;
+    } else {
+      trj_fwd(lp.r0, n, ux, prm.dt, c_full, cnew, ndye, dye_cur, dye_nxt, nullptr, nullptr, nfp, trjd_nfd, trjd_mid);
+    }
+    trjd_nb = nb_dye(n);
+    ++trjd_steps;
+    if (ndye) {
+      std::swap(dye_cur, dye_nxt);
+      dye_nb = trjd_nb;
+      ++dye_steps;
+    }
+    hipLaunchKernelGGL(k_wsum, dim3(trjd_nb), dim3(BS), 0, st, lp.r0, n, (const double*)cnew, (const double*)dwmix,
+                       part_sl);
+    KCHK();
+  }
+  // ... and its sums, as mc_dye_reduce: sum wc, sum w, then the step record's not-found entry (the final locate's)
+  void trj_dye_reduce() {
+    reduce_into(part_sl, trjd_nb, 2, false, 2, SLB);
+    reduce_into(trjd_nfd, trjd_nb, 1, false, 4, SLB);
+  }
+  // the rows of the last launch whose midpoint was not found (pass 1's and, with pass2, pass 2's), in block order
+  int64_t trj_mid_rows(const int32_t* mid, int nb, bool pass2) {
+    return nf_rows(mid, nb) + (pass2 ? nf_rows(mid + SLB, nb) : 0);
+  }
+  void drop_trajectory() {
+    trj_dye = trj_vel = trj_trc = PUCFEM_TRJ_EULER;
+    trjd_nb = trjv_nb = 0;
+    trjt_ran = false;
+    trjd_steps = trjv_steps = trjt_steps = 0;
+    if (!trjd_mid && !trjv_mid && !trjt_fell) return;
+    if (st) (void)hipStreamSynchronize(st);
+    if (st_sl) (void)hipStreamSynchronize(st_sl);
+    for (void* q : {(void*)trjd_mid, (void*)trjd_nfpart, (void*)trjd_nfd, (void*)trjv_mid, (void*)trjt_fell})
+      if (q) (void)hipFree(q);
+    trjd_mid = trjd_nfpart = trjv_mid = trjt_fell = nullptr;
+    trjd_nfd = nullptr;
+  }
+  void set_trajectory(int what, int order) {
+    constexpr int all = PUCFEM_TRJ_DYE | PUCFEM_TRJ_VELOCITY | PUCFEM_TRJ_TRACERS;
+    if (what & ~all || what == 0)
+      throw Error(PUCFEM_EINVAL, "what is a mask of PUCFEM_TRJ_DYE, PUCFEM_TRJ_VELOCITY and PUCFEM_TRJ_TRACERS");
+    if (order != PUCFEM_TRJ_EULER && order != PUCFEM_TRJ_MIDPOINT)
+      throw Error(PUCFEM_EINVAL, "unknown trajectory order");
+    if (what & PUCFEM_TRJ_DYE) dye_ready();
+    if (what & PUCFEM_TRJ_VELOCITY) inertia_ready();
+    if (what & PUCFEM_TRJ_TRACERS) tracers_ready();
+    if (ens)
+      throw Error(PUCFEM_ESTATE,
+                  "the trajectory order cannot be set while the context has an ensemble (members trace one Euler step)");
+    const bool mid = order == PUCFEM_TRJ_MIDPOINT;
+    if ((what & PUCFEM_TRJ_DYE) && order != trj_dye) {
+      if (st_sl) HIPCHK(hipStreamSynchronize(st_sl));
+      if (mid) {
+        if (!trjd_mid) {
+          mc_alloc(trjd_mid, 2 * (size_t)SLB);
+          mc_alloc(trjd_nfpart, (size_t)SLB);
+          mc_alloc(trjd_nfd, (size_t)SLB);
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        trjd_steps = 0;
+        trjd_nb = 0;
+      }
+      trj_dye = order;
+    }
+    if ((what & PUCFEM_TRJ_VELOCITY) && order != trj_vel) {
+      if (mid) {
+        if (!trjv_mid) {
+          mc_alloc(trjv_mid, 2 * (size_t)SLB);
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        trjv_steps = 0;
+        trjv_nb = 0;
+      }
+      trj_vel = order;
+      have_vinc = 0;  // (as set_advection: the advected right-hand side changes)
+    }
+    if ((what & PUCFEM_TRJ_TRACERS) && order != trj_trc) {
+      if (mid) {
+        if (!trjt_fell) {
+          mc_alloc(trjt_fell, (size_t)1);
+          HIPCHK(hipStreamSynchronize(st));
+        }
+        trjt_steps = 0;
+        trjt_ran = false;
+      }
+      trj_trc = order;
+    }
+    // (a small-mesh context steps uncaptured while a part is on; its captured graphs hold the Euler step and are
+    // kept: with every part off again pucfem_step replays them)
+  }
+  size_t trajectory_dev_bytes() const {
+    size_t b = 0;
+    if (trjd_mid) b += sizeof(int32_t) * 3 * SLB + sizeof(double) * SLB;
+    if (trjv_mid) b += sizeof(int32_t) * 2 * SLB;
+    if (trjt_fell) b += sizeof(int32_t);
     return b;
   }
 
@@ -3526,7 +3739,10 @@ struct Ctx {
   void dye_tail_sl(double* rec) {
     const int nb = nb_sl(lp.n_own);
     const RedOut rs = ro(vals + 2, CNT_DYE_SL, 3, SLB);
-    if (adv_dye) {
+    const bool trj = trj_dye == PUCFEM_TRJ_MIDPOINT;
+    if (trj) {
+      trj_dye_step(c_new);  // (c and the channels, one or two fused launches; before ev_sl is recorded, as below)
+    } else if (adv_dye) {
       mc_dye_step(c_new);  // (c and the channels; before ev_sl is recorded, as below)
     } else {
       sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
@@ -3534,7 +3750,8 @@ struct Ctx {
       dyes_step();  // (before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
     }
     std::swap(c_full, c_new);
-    if (adv_dye) mc_dye_reduce();
+    if (trj) trj_dye_reduce();
+    else if (adv_dye) mc_dye_reduce();
     else if (!rs.out) reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
     const int nbm = nb_rows(lp.n_own);
     algo_bytes += 16.0 * (double)lp.n_own;  // c, w
@@ -3646,6 +3863,8 @@ struct Ctx {
         its[1] = itp;
         its[2] = itp2;
         return;
+      } else if (trj_dye == PUCFEM_TRJ_MIDPOINT) {
+        trj_dye_step(c_new);
       } else if (adv_dye) {
         mc_dye_step(c_new);
       } else {
@@ -3662,7 +3881,8 @@ struct Ctx {
       } else if (!mix_copy) {
         std::swap(c_full, c_new);
       }
-      if (adv_dye && !dye_impl) mc_dye_reduce();
+      if (trj_dye == PUCFEM_TRJ_MIDPOINT && !dye_impl) trj_dye_reduce();
+      else if (adv_dye && !dye_impl) mc_dye_reduce();
       else if (sl_ro.out) red_done(vals + 2, 3, false);
       else reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
       sl_ro = RedOut{};
@@ -3861,28 +4081,54 @@ struct Ctx {
       KCHK();
       return;
     }
+    if (trj_trc == PUCFEM_TRJ_MIDPOINT) {  // midpoint trajectories: the same launch, the MID instantiations
+      const MeshDev M{mx, my, mtri, mesh.T};
+      const TrjMid md{0.5 * dt, trjt_fell};
+      HIPCHK(hipMemsetAsync(trjt_fell, 0, sizeof(int32_t), st));
+      if (tr_D > 0.0) {
+        const Brown br{std::sqrt(6.0 * tr_D * dt), (uint32_t)(tr_seed & 0xffffffffu), (uint32_t)(tr_seed >> 32), tr_ylo,
+                       tr_yhi};
+        if (cloud)
+          hipLaunchKernelGGL((k_tracer_cloud<true, true>), dim3(nbt), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx, try_,
+                             trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt, br, md);
+        else
+          hipLaunchKernelGGL((k_tracer<true, true>), dim3(1), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx, try_, trs,
+                             trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6, br, md);
+      } else if (cloud) {
+        hipLaunchKernelGGL((k_tracer_cloud<false, true>), dim3(nbt), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx, try_,
+                           trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt,
+                           BrownOff{}, md);
+      } else {
+        hipLaunchKernelGGL((k_tracer<false, true>), dim3(1), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx, try_, trs,
+                           trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6, BrownOff{}, md);
+      }
+      KCHK();
+      trjt_ran = true;
+      ++trjt_steps;
+      return;
+    }
     if (tr_D > 0.0) {  // Brownian tracers: the same launch, the BROWN instantiation
       const Brown br{std::sqrt(6.0 * tr_D * dt), (uint32_t)(tr_seed & 0xffffffffu), (uint32_t)(tr_seed >> 32), tr_ylo,
                      tr_yhi};
       if (cloud)
         hipLaunchKernelGGL(k_tracer_cloud<true>, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx,
                            fy, ntr, trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius,
-                           part_tr, rt, br);
+                           part_tr, rt, br, TrjMidOff{});
       else
         hipLaunchKernelGGL(k_tracer<true>, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
                            trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6,
-                           br);
+                           br, TrjMidOff{});
       KCHK();
       return;
     }
     if (cloud)
       hipLaunchKernelGGL(k_tracer_cloud<false>, dim3(nbt), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx,
                          fy, ntr, trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius,
-                         part_tr, rt, BrownOff{});
+                         part_tr, rt, BrownOff{}, TrjMidOff{});
     else
       hipLaunchKernelGGL(k_tracer<false>, dim3(1), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T}, tgrid, fx, fy, ntr,
                          trx, try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6,
-                         BrownOff{});
+                         BrownOff{}, TrjMidOff{});
     KCHK();
   }
   // blocks in x of a tracer launch over n tracers: 1 = the one-block kernels, else the cloud kernels' capped grid
@@ -5760,6 +6006,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     if (!c.host_only) c.drop_force();
     if (!c.host_only) c.drop_stroke(false);
     if (!c.host_only) c.drop_advection();
+    if (!c.host_only) c.drop_trajectory();
     build(c);
   });
 }
@@ -5942,9 +6189,10 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       // inertia on: the captured step has no inertial launch, and a toggle takes effect at the next step; so does one
       // whose dye moves by MacCormack steps, and one with a body force: the same launches behind k_force_rhs, whose
       // by-value terms and dye pointers change between steps; and one with a stroke: the same launches behind
-      // k_stroke_bc, so that the captured graphs stay the unstroked step's, launch for launch)
+      // k_stroke_bc, so that the captured graphs stay the unstroked step's, launch for launch; and one with a
+      // midpoint trajectory on: the captured graphs hold the Euler launches)
       if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced() &&
-          !c.stroked()) {
+          !c.stroked() && !c.trj_any()) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -6333,6 +6581,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     state(!c.inertia, "ensembles step without inertia: switch it off first (pucfem_set_inertia)");
     state(!c.adv_dye && !c.adv_vel,
           "ensembles step the first-order advection: switch MacCormack off first (pucfem_set_advection)");
+    state(!c.trj_any(), "ensembles trace one Euler step: switch the midpoint off first (pucfem_set_trajectory)");
     state(!c.stroked(), "the context's stroke is on: clear it first (members carry their own: pucfem_ens_set_stroke)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
@@ -8228,6 +8477,184 @@ int pucfem_advection_probe(void* ctx, int32_t what, int32_t nch, int32_t iters, 
       out4[1] = time_launches(c, iters, [&] { pass(2); });
       out4[2] = c.mcv_bytes1(N);
       out4[3] = c.mcv_bytes2(N);
+    }
+  });
+}
+
+// ---- midpoint trajectories (pucfem_trajectory.hpp)
+int pucfem_set_trajectory(void* ctx, int32_t what, int32_t order) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.set_trajectory(what, order);
+  });
+}
+
+int pucfem_trajectory_info(void* ctx, int64_t* out10) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.inertia_ready();  // (a single-rank Stokes context on a device, built)
+    require(out10 != nullptr, "null output");
+    out10[0] = c.trj_dye;
+    out10[1] = c.trj_vel;
+    out10[2] = c.trj_trc;
+    out10[3] = c.trjd_steps;
+    out10[4] = c.trjv_steps;
+    out10[5] = c.trjt_steps;
+    if (c.st_sl) HIPCHK(hipStreamSynchronize(c.st_sl));
+    out10[6] = c.trj_mid_rows(c.trjd_mid, c.trjd_nb, c.adv_dye != 0);
+    out10[7] = c.trj_mid_rows(c.trjv_mid, c.trjv_nb, c.adv_vel != 0);
+    int32_t fell = 0;
+    if (c.trjt_fell && c.trjt_ran) c.d2h(&fell, c.trjt_fell, sizeof(int32_t));
+    out10[8] = fell;
+    out10[9] = (int64_t)c.trajectory_dev_bytes();
+  });
+}
+
+namespace {
+void trj_check(int32_t order, int32_t scheme) {
+  require(order == PUCFEM_TRJ_EULER || order == PUCFEM_TRJ_MIDPOINT, "unknown trajectory order");
+  require(scheme == PUCFEM_ADV_SL || scheme == PUCFEM_ADV_MACCORMACK, "unknown advection scheme");
+}
+}  // namespace
+
+int pucfem_sl_advect_traj(void* ctx, int32_t order, int32_t scheme, int32_t nch, const double* cin, const double* u,
+                          double dt, double* cout, int32_t* marks, int32_t* tri) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    trj_check(order, scheme);
+    c.dye_ready();
+    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    const size_t tot = (size_t)nch * (size_t)N;
+    const bool mc = scheme == PUCFEM_ADV_MACCORMACK, mid = order == PUCFEM_TRJ_MIDPOINT;
+    double *tx = c.u_scratch(), *ty = tx + 1;
+    double* din = c.smp_scratch<double>(14, tot);
+    double* dout = c.smp_scratch<double>(15, tot);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    double* dch = mc ? c.smp_scratch<double>(17, tot) : nullptr;
+    int4* drec = mc ? c.smp_scratch<int4>(18, (size_t)N) : nullptr;
+    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
+    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
+    c.put_all(1, nch, cin, din);
+    c.put_all(2, 1, u, tx);
+    if (mid) {
+      c.trj_fwd(0, N, tx, dt, nullptr, nullptr, nch, din, mc ? dch : dout, drec, dmark, dpart, nullptr, dmid);
+      if (mc)
+        c.trj_bwd(0, N, tx, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt, dmid + SLB);
+    } else if (mc) {
+      c.mc_fwd(0, N, tx, ty, dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr);
+      c.mc_bwd(0, N, tx, ty, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt);
+    } else {
+      c.dye_launch(0, N, tx, ty, dt, nch, din, dout, dmark, dpart);
+    }
+    c.get_all(1, nch, cout, dout);
+    if (marks) c.get_all(1, 1, marks, dmark);
+    if (tri) {
+      if (mc) {
+        c.get_all(1, 1, tri, dtri);
+      } else {
+        for (i64 i = 0; i < N; ++i) tri[i] = -1;  // (T1 belongs to the two-pass scheme)
+      }
+    }
+  });
+}
+
+int pucfem_sl_advect_vel_traj(void* ctx, int32_t order, int32_t scheme, const double* f, const double* u, double dt,
+                              double* f_out, int32_t* marks, int32_t* tri) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    trj_check(order, scheme);
+    c.inertia_ready();
+    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
+    const i64 N = c.mesh.N;
+    const bool mc = scheme == PUCFEM_ADV_MACCORMACK, mid = order == PUCFEM_TRJ_MIDPOINT;
+    double* tu = c.u_scratch();
+    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
+    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    double* dch = mc ? c.smp_scratch<double>(17, 2 * (size_t)N) : nullptr;
+    int4* drec = mc ? c.smp_scratch<int4>(18, (size_t)N) : nullptr;
+    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
+    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
+    c.put_all(2, 1, f, din);
+    c.put_all(2, 1, u, tu);
+    if (mid) {
+      if (mc) c.trj_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt, dmid);
+      else c.trj_vel_launch(0, N, tu, dt, din, dout, nullptr, nullptr, dmark, nullptr, dpart, nullptr, dmid, 1);
+    } else if (mc) {
+      c.mc_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt);
+    } else {
+      c.vel_launch(0, N, tu, dt, din, dout, dmark, dpart);
+    }
+    c.get_all(2, 1, f_out, dout);
+    if (marks) c.get_all(1, 1, marks, dmark);
+    if (tri) {
+      if (mc) {
+        c.get_all(1, 1, tri, dtri);
+      } else {
+        for (i64 i = 0; i < N; ++i) tri[i] = -1;
+      }
+    }
+  });
+}
+
+int pucfem_trajectory_probe(void* ctx, int32_t what, int32_t scheme, int32_t nch, int32_t iters, double* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(what == PUCFEM_TRJ_DYE || what == PUCFEM_TRJ_VELOCITY, "what is PUCFEM_TRJ_DYE or PUCFEM_TRJ_VELOCITY");
+    require(scheme == PUCFEM_ADV_SL || scheme == PUCFEM_ADV_MACCORMACK, "unknown advection scheme");
+    if (what == PUCFEM_TRJ_DYE) c.dye_ready();
+    else c.inertia_ready();
+    require(iters >= 1 && out4 != nullptr, "iters < 1 or null output");
+    const i64 N = c.mesh.N;
+    const bool mc = scheme == PUCFEM_ADV_MACCORMACK;
+    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
+    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
+    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
+    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
+    out4[0] = out4[1] = out4[2] = out4[3] = 0.0;
+    if (what == PUCFEM_TRJ_DYE) {
+      require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+      const size_t tot = (size_t)nch * (size_t)N;
+      double* din = c.smp_scratch<double>(14, tot);
+      double* dout = c.smp_scratch<double>(15, tot);
+      double* dch = c.smp_scratch<double>(17, tot);
+      HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
+      auto p1 = [&] {
+        c.trj_fwd(0, N, c.ux, c.prm.dt, nullptr, nullptr, nch, din, dch, mc ? drec : nullptr, nullptr, dpart, nullptr,
+                  dmid);
+      };
+      auto p2 = [&] {
+        c.trj_bwd(0, N, c.ux, c.prm.dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, nullptr, nullptr, dcnt,
+                  dmid + SLB);
+      };
+      p1();  // (untimed: the first launches)
+      out4[0] = time_launches(c, iters, p1);
+      out4[2] = c.trj_bytes1(nch, N, mc);
+      if (mc) {
+        p2();
+        out4[1] = time_launches(c, iters, p2);
+        out4[3] = c.trj_bytes2(nch, N);
+      }
+    } else {
+      double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
+      double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
+      auto pass = [&](int which) {
+        c.trj_vel_launch(0, N, c.ux, c.prm.dt, c.ux, dch, dout, mc ? drec : nullptr, nullptr, nullptr, dpart, dcnt, dmid,
+                         which);
+      };
+      pass(mc ? 3 : 1);  // (untimed: the first launches)
+      out4[0] = time_launches(c, iters, [&] { pass(1); });
+      out4[2] = c.trjv_bytes1(N, mc);
+      if (mc) {
+        out4[1] = time_launches(c, iters, [&] { pass(2); });
+        out4[3] = c.trjv_bytes2(N);
+      }
     }
   });
 }

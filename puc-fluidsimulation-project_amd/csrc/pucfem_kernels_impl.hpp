@@ -2667,17 +2667,43 @@ __device__ __forceinline__ double tracer_move(double* tx, double* ty, double* st
 constexpr int32_t TRACER_CLOUD_MIN = PUCFEM_TRACER_CLOUD_MIN;  // (a variant build sets it to measure the crossover)
 constexpr int TRACER_CLOUD_MAXB = 2048;  // the cloud kernels' grid cap in x (memory-bound: grid-stride beyond it)
 
+// Midpoint trajectories of the tracers (pucfem_set_trajectory), the compile-time variant MID of
+// the two kernels below: the velocity is read again half a step along the first one,
+//   m = (py_mod(px + vx * hdt, 1.0), py + vy * hdt),   (wx, wy) = u at m,
+// and the move is taken with (wx, wy).  A midpoint outside the mesh (or not finite: a tracer that already is) keeps
+// (vx, vy): an Euler step.  fell: those tracers of the launch that had a velocity and lost their midpoint (an integer
+// atomic per block, zeroed by the host in front of the launch).
+struct TrjMid {
+  double hdt;     // 0.5 * dt, from the host
+  int32_t* fell;
+};
+struct TrjMidOff {};  // the Euler kernels' (empty) argument
+template <bool MID>
+using TrjMidArg = std::conditional_t<MID, TrjMid, TrjMidOff>;
+// (vx, vy) at (px, py) -> at the midpoint; false: kept
+__device__ __forceinline__ bool tracer_mid(const MeshDev& M, const GridDev& G, const double* __restrict__ ux,
+                                           const double* __restrict__ uy, double px, double py, double hdt, double& vx,
+                                           double& vy) {
+  const double mx = py_mod(px + vx * hdt, 1.0), my = py + vy * hdt;
+  const int32_t t = tracer_locate(M, G, mx, my);
+  if (t < 0) return false;
+  tracer_interp(M, t, ux, uy, VS, mx, my, vx, vy);
+  return true;
+}
+
 // stepctr: the set's tracer steps so far, in device memory (a captured step's arguments are fixed); the step being
 // taken is *stepctr + 1.  Every thread reads it before the block's barrier, thread 0 stores the new count after it.
 // BROWN (pucfem_brownian.hpp): the move with the random increment of setting br; false is the plain step.  An
 // absorbed tracer leaves its loop iteration only: every thread reaches the barriers behind the loop.
-template <bool BROWN>
+template <bool BROWN, bool MID = false>
 __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, const double* __restrict__ uy,
                          int32_t ntr, double* tx, double* ty, double* status, int32_t* capstep, int32_t* stepctr,
-                         double dt, double cx, double cy, double capture, double* eaten_out, BrownArg<BROWN> br) {
+                         double dt, double cx, double cy, double capture, double* eaten_out, BrownArg<BROWN> br,
+                         TrjMidArg<MID> md) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
+  [[maybe_unused]] int32_t fell = 0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
     if constexpr (BROWN) {
       if (status[k] == 1.0) {
@@ -2689,10 +2715,17 @@ __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, co
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(M, G, px, py);
     if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+    if constexpr (MID) {
+      if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+    }
     if constexpr (BROWN)
       eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
     else
       eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  if constexpr (MID) {
+    const double f = block_sum((double)fell, sh);
+    if (threadIdx.x == 0 && f > 0.0) atomicAdd(md.fell, (int32_t)f);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) {
@@ -2703,15 +2736,16 @@ __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, co
 // k_tracer on a grid: one tracer per thread, grid-stride past the capped grid; the eaten count from per-block
 // partials (red_finish; ro.out is never null here).  The block that finishes the reduction stores the new step
 // count: every block read the old one before it drew its ticket.
-template <bool BROWN>
+template <bool BROWN, bool MID = false>
 __global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const double* __restrict__ ux,
                                                      const double* __restrict__ uy, int32_t ntr, double* tx,
                                                      double* ty, double* status, int32_t* capstep, int32_t* stepctr,
                                                      double dt, double cx, double cy, double capture, double* part,
-                                                     RedOut ro, BrownArg<BROWN> br) {
+                                                     RedOut ro, BrownArg<BROWN> br, TrjMidArg<MID> md) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
+  [[maybe_unused]] int32_t fell = 0;
   for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
     const int32_t k = (int32_t)i;
     if constexpr (BROWN) {
@@ -2724,10 +2758,17 @@ __global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(M, G, px, py);
     if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+    if constexpr (MID) {
+      if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+    }
     if constexpr (BROWN)
       eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
     else
       eaten += tracer_move(tx, ty, status, capstep, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  if constexpr (MID) {
+    const double f = block_sum((double)fell, sh);
+    if (threadIdx.x == 0 && f > 0.0) atomicAdd(md.fell, (int32_t)f);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) red_part(ro, part, 0, t);

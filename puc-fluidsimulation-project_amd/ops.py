@@ -163,10 +163,20 @@ def advect_semilagrange(c, u, DT, nodes=None, triangles=None):
     return nf.astype(bool)
 
 
-def advect_semilagrange_multi(C, u, DT, nodes=None, triangles=None):
+def _trajectory(trajectory):
+    from .solver import trajectory_order
+
+    return trajectory_order(trajectory)
+
+
+def advect_semilagrange_multi(C, u, DT, nodes=None, triangles=None, trajectory="euler", marks=None):
     """advect_semilagrange of the K fields C (K, N), K = 1 .. 16, at once (pucfem_sl_advect_multi): one back-trace
     and one point location per node for all of them, every field's bits those of advect_semilagrange alone.
-    In place on C like the reference (C[:] = C_new); returns the not-found mask (N,), the same for every field."""
+    In place on C like the reference (C[:] = C_new); returns the not-found mask (N,), the same for every field.
+    trajectory 'euler' | 'midpoint': with 'midpoint' (pucfem_sl_advect_traj) every node is traced with the velocity
+    read half a step along its straight trace; marks (N,) int32, if given, receives the row marks (bit 0 the final
+    point was not found, bit 2 the midpoint was not: that node took its Euler step)."""
+    order = _trajectory(trajectory)
     if nodes is None or triangles is None:
         m = _mesh_or_global(None)
         nodes, triangles = m.coords, m.triangles
@@ -177,17 +187,26 @@ def advect_semilagrange_multi(C, u, DT, nodes=None, triangles=None):
     uu = np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
     out = np.zeros_like(cin)
     nf = np.zeros(cin.shape[1], dtype=np.int32)
-    _lib.check(ctx.L.pucfem_sl_advect_multi(ctx.h, cin.shape[0], _lib.dptr(cin), _lib.dptr(uu), float(DT),
-                                            _lib.dptr(out), _lib.iptr(nf)), ctx.h)
+    if order == _lib.TRJ_EULER and marks is None:
+        _lib.check(ctx.L.pucfem_sl_advect_multi(ctx.h, cin.shape[0], _lib.dptr(cin), _lib.dptr(uu), float(DT),
+                                                _lib.dptr(out), _lib.iptr(nf)), ctx.h)
+    else:
+        _lib.check(ctx.L.pucfem_sl_advect_traj(ctx.h, order, _lib.ADV_SL, cin.shape[0], _lib.dptr(cin), _lib.dptr(uu),
+                                               float(DT), _lib.dptr(out), _lib.iptr(nf), None), ctx.h)
+        if marks is not None:
+            marks[:] = nf
+        nf &= _lib.MC_NO_BACK
     C[:] = out
     return nf.astype(bool)
 
 
-def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None):
+def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None, trajectory="euler", marks=None):
     """advect_semilagrange of the two components of f (N, 2) at once (pucfem_sl_advect_vel, the inertial step's
     kernel): one back-trace and one point location per node, each component's bits those of advect_semilagrange
     on f[:, k] alone.  f may be u (the inertial term's u_a = SL(u; u, DT)).  In place on f like the reference
-    (f[:] = f_new); returns the not-found mask (N,), the same for both components."""
+    (f[:] = f_new); returns the not-found mask (N,), the same for both components.  trajectory, marks: as
+    advect_semilagrange_multi (pucfem_sl_advect_vel_traj)."""
+    order = _trajectory(trajectory)
     if nodes is None or triangles is None:
         m = _mesh_or_global(None)
         nodes, triangles = m.coords, m.triangles
@@ -198,8 +217,15 @@ def advect_semilagrange_vector(f, u, DT, nodes=None, triangles=None):
     uu =np.ascontiguousarray(u, dtype=np.float64).reshape(-1, 2)
     out = np.zeros_like(fin)
     nf = np.zeros(len(fin), dtype=np.int32)
-    _lib.check(ctx.L.pucfem_sl_advect_vel(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
-                                          _lib.iptr(nf)), ctx.h)
+    if order == _lib.TRJ_EULER and marks is None:
+        _lib.check(ctx.L.pucfem_sl_advect_vel(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
+                                              _lib.iptr(nf)), ctx.h)
+    else:
+        _lib.check(ctx.L.pucfem_sl_advect_vel_traj(ctx.h, order, _lib.ADV_SL, _lib.dptr(fin), _lib.dptr(uu), float(DT),
+                                                   _lib.dptr(out), _lib.iptr(nf), None), ctx.h)
+        if marks is not None:
+            marks[:] = nf
+        nf &= _lib.MC_NO_BACK
     f[:] = out
     return nf.astype(bool)
 
@@ -245,13 +271,16 @@ def apply_body_force(u, dt, nodes=None, triangles=None, force=None, buoyancy=Non
             ctx._c(ctx.L.pucfem_set_field(ctx.h, _lib.F_DYES, None, 0))
 
 
-def advect_maccormack(c, u, DT, nodes=None, triangles=None, tri=None):
+def advect_maccormack(c, u, DT, nodes=None, triangles=None, tri=None, trajectory="euler"):
     """One limited MacCormack step (pucfem_sl_advect_mc; Selle et al. 2008) of the field c (N,) or of the K fields
     c (K, N), K = 1 .. 16, from one point location per pass and node: ch = SL(c; u, DT), cb = SL(ch; u, -DT),
     ch + (c - cb) / 2 clamped into the range of c at the vertices of ch's departure triangle.  In place on c as
     advect_semilagrange; returns the marks (N,) int32: bit 0 the back-trace found no triangle (the node kept c),
     bit 1 the forward trace found none (it kept ch).  tri (N,) int32, if given, receives the departure triangle's
-    index in `triangles` (-1: none)."""
+    index in `triangles` (-1: none).  trajectory 'euler' | 'midpoint': with 'midpoint' (pucfem_sl_advect_traj) both
+    passes trace with the velocity read half a step along the straight trace; the marks gain bit 2 (pass 1's
+    midpoint was not found) and bit 3 (pass 2's)."""
+    order = _trajectory(trajectory)
     if nodes is None or triangles is None:
         m = _mesh_or_global(None)
         nodes, triangles = m.coords, m.triangles
@@ -263,18 +292,26 @@ def advect_maccormack(c, u, DT, nodes=None, triangles=None, tri=None):
     out = np.zeros_like(cin)
     marks = np.zeros(len(nodes), dtype=np.int32)
     t = np.zeros(len(nodes), dtype=np.int32)
-    _lib.check(ctx.L.pucfem_sl_advect_mc(ctx.h, 1 if cin.ndim == 1 else cin.shape[0], _lib.dptr(cin), _lib.dptr(uu),
-                                         float(DT), _lib.dptr(out), _lib.iptr(marks), _lib.iptr(t)), ctx.h)
+    if order == _lib.TRJ_EULER:
+        _lib.check(ctx.L.pucfem_sl_advect_mc(ctx.h, 1 if cin.ndim == 1 else cin.shape[0], _lib.dptr(cin),
+                                             _lib.dptr(uu), float(DT), _lib.dptr(out), _lib.iptr(marks), _lib.iptr(t)),
+                   ctx.h)
+    else:
+        _lib.check(ctx.L.pucfem_sl_advect_traj(ctx.h, order, _lib.ADV_MACCORMACK, 1 if cin.ndim == 1 else cin.shape[0],
+                                               _lib.dptr(cin), _lib.dptr(uu), float(DT), _lib.dptr(out),
+                                               _lib.iptr(marks), _lib.iptr(t)), ctx.h)
     c[:] = out
     if tri is not None:
         tri[:] = t
     return marks
 
 
-def advect_maccormack_vector(f, u, DT, nodes=None, triangles=None, tri=None):
+def advect_maccormack_vector(f, u, DT, nodes=None, triangles=None, tri=None, trajectory="euler"):
     """advect_maccormack of the two components of f (N, 2) at once (pucfem_sl_advect_vel_mc, the inertial step's
     kernels): each vertex's pair one load, the components limited separately, each with the bits of
-    advect_maccormack on f[:, k] alone.  f may be u.  In place on f; returns the marks (N,)."""
+    advect_maccormack on f[:, k] alone.  f may be u.  In place on f; returns the marks (N,).  trajectory: as
+    advect_maccormack (pucfem_sl_advect_vel_traj)."""
+    order = _trajectory(trajectory)
     if nodes is None or triangles is None:
         m = _mesh_or_global(None)
         nodes, triangles = m.coords, m.triangles
@@ -286,8 +323,12 @@ def advect_maccormack_vector(f, u, DT, nodes=None, triangles=None, tri=None):
     out = np.zeros_like(fin)
     marks = np.zeros(len(fin), dtype=np.int32)
     t = np.zeros(len(fin), dtype=np.int32)
-    _lib.check(ctx.L.pucfem_sl_advect_vel_mc(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
-                                             _lib.iptr(marks), _lib.iptr(t)), ctx.h)
+    if order == _lib.TRJ_EULER:
+        _lib.check(ctx.L.pucfem_sl_advect_vel_mc(ctx.h, _lib.dptr(fin), _lib.dptr(uu), float(DT), _lib.dptr(out),
+                                                 _lib.iptr(marks), _lib.iptr(t)), ctx.h)
+    else:
+        _lib.check(ctx.L.pucfem_sl_advect_vel_traj(ctx.h, order, _lib.ADV_MACCORMACK, _lib.dptr(fin), _lib.dptr(uu),
+                                                   float(DT), _lib.dptr(out), _lib.iptr(marks), _lib.iptr(t)), ctx.h)
     f[:] = out
     if tri is not None:
         tri[:] = t

@@ -36,6 +36,20 @@ def advection_scheme(name):
     return int(name)
 
 
+TRAJECTORY_NAMES = ("euler", "midpoint")  # pucfem_set_trajectory's orders, PUCFEM_TRJ_EULER / PUCFEM_TRJ_MIDPOINT
+
+
+def trajectory_order(name):
+    """The PUCFEM_TRJ_* order of trajectory='euler' | 'midpoint' (an int 1 | 2 passes through)."""
+    if isinstance(name, str):
+        if name not in TRAJECTORY_NAMES:
+            raise ValueError(f"trajectory must be one of {TRAJECTORY_NAMES}, got {name!r}")
+        return TRAJECTORY_NAMES.index(name) + 1
+    if isinstance(name, bool) or int(name) not in (_lib.TRJ_EULER, _lib.TRJ_MIDPOINT):
+        raise ValueError(f"trajectory must be one of {TRAJECTORY_NAMES}, got {name!r}")
+    return int(name)
+
+
 def dye_field(name):
     """The pucfem_field value of a dye channel's name "dye0" .. "dye15" (PUCFEM_F_DYE0 + k); None for a name that is
     not of that form at all, ValueError for "dye" followed by anything but a channel index below 16."""
@@ -802,6 +816,28 @@ class Context:
         self._c(self.L.pucfem_advection_probe(self.h, int(what), int(nch), int(iters), o))
         return dict(pass1_ms=o[0], pass2_ms=o[1], pass1_bytes=o[2], pass2_bytes=o[3])
 
+    def set_trajectory(self, what, order):
+        """The trajectory order (pucfem_set_trajectory) of the dye (what = TRJ_DYE), of the inertial step's velocity
+        (TRJ_VELOCITY), of the tracers (TRJ_TRACERS) or of several (their sum): 'euler' one straight step of the
+        velocity at the starting point, 'midpoint' a step with the velocity read half a step along it."""
+        self._c(self.L.pucfem_set_trajectory(self.h, int(what), trajectory_order(order)))
+
+    def trajectory_info(self):
+        """pucfem_trajectory_info: the three orders, the steps each part has taken while on, the rows of the last dye
+        and velocity launch whose midpoint was not found, the tracers of the last launch that fell back to their
+        Euler step, and the device bytes held."""
+        o = (ct.c_int64 * 10)()
+        self._c(self.L.pucfem_trajectory_info(self.h, o))
+        return dict(dye=TRAJECTORY_NAMES[o[0] - 1], velocity=TRAJECTORY_NAMES[o[1] - 1],
+                    tracers=TRAJECTORY_NAMES[o[2] - 1], dye_steps=o[3], velocity_steps=o[4], tracer_steps=o[5],
+                    dye_mid_notfound=o[6], velocity_mid_notfound=o[7], tracers_fell_back=o[8], bytes=o[9])
+
+    def trajectory_probe(self, what, scheme="sl", nch=1, iters=10):
+        """Kernel times of the fused midpoint launches (pucfem_trajectory_probe; tools/trajectory_bench.py)."""
+        o = (ct.c_double * 4)()
+        self._c(self.L.pucfem_trajectory_probe(self.h, int(what), advection_scheme(scheme), int(nch), int(iters), o))
+        return dict(pass1_ms=o[0], pass2_ms=o[1], pass1_bytes=o[2], pass2_bytes=o[3])
+
     def flow_info(self, member=None):
         """Flow summaries of the current u, reduced on the device (pucfem_flow_info; one launch, four doubles
         copied): max |vorticity|, the enstrophy 1/2 sum w vorticity^2, the kinetic energy 1/2 sum w |u|^2 and the
@@ -900,8 +936,10 @@ class StokesSimulation:
 
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
                  tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl",
-                 tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None, stroke=None):
+                 tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None, stroke=None,
+                 trajectory="euler"):
         adv = advection_scheme(advection)
+        trj = trajectory_order(trajectory)
         _check_stroke(stroke)
         f_const, f_field = _force_args(force, mesh.N)
         if buoyancy is not None and not isinstance(buoyancy, Buoyancy):
@@ -913,6 +951,9 @@ class StokesSimulation:
         if adv and not adv_what:
             raise ValueError("advection='maccormack' moves the dye of a 'color' run and the velocity of an inertial "
                              "one: a 'food' run without inertia has neither")
+        # (whatever the run transports: the dye on color runs, the velocity on inertial ones, the tracers on food runs)
+        trj_what = ((_lib.TRJ_DYE if scheme == "color" else 0) | (_lib.TRJ_VELOCITY if inertia else 0) |
+                    (_lib.TRJ_TRACERS if scheme == "food" else 0))
         self.mesh = mesh
         self.bc = bc or SquirmerBC()
         self.dt = dt
@@ -944,6 +985,8 @@ class StokesSimulation:
                 self.ctx.set_inertia(True)
             if adv:
                 self.ctx.set_advection(adv_what, adv)
+            if trj != _lib.TRJ_EULER:
+                self.ctx.set_trajectory(trj_what, trj)
             if tracer_diffusivity != 0.0 or tracer_seed != 0:
                 self.ctx.set_tracer_diffusion(tracer_diffusivity, tracer_seed)
             self._force = (None, None)
@@ -1150,6 +1193,41 @@ class StokesSimulation:
     def advection_info(self):
         """Context.advection_info of this run."""
         return self.ctx.advection_info()
+
+    # ---- midpoint trajectories (pucfem_set_trajectory)
+    @property
+    def dye_trajectory(self):
+        """'euler' | 'midpoint': the path the dye and its channels are traced back along.  'midpoint' reads the
+        velocity again half a step along the straight trace and takes the whole step with it (second order along a
+        steady flow); 'euler' is the reference's step."""
+        return self.ctx.trajectory_info()["dye"]
+
+    @dye_trajectory.setter
+    def dye_trajectory(self, order):
+        self.ctx.set_trajectory(_lib.TRJ_DYE, order)
+
+    @property
+    def velocity_trajectory(self):
+        """... of the inertial step's velocity (it may be set while inertia is off and waits for it)."""
+        return self.ctx.trajectory_info()["velocity"]
+
+    @velocity_trajectory.setter
+    def velocity_trajectory(self, order):
+        self.ctx.set_trajectory(_lib.TRJ_VELOCITY, order)
+
+    @property
+    def tracer_trajectory(self):
+        """... of the tracers of a 'food' run: the move is taken with the velocity at the midpoint of the Euler
+        step; a tracer whose midpoint leaves the mesh takes its Euler step (trajectory_info counts them)."""
+        return self.ctx.trajectory_info()["tracers"]
+
+    @tracer_trajectory.setter
+    def tracer_trajectory(self, order):
+        self.ctx.set_trajectory(_lib.TRJ_TRACERS, order)
+
+    def trajectory_info(self):
+        """Context.trajectory_info of this run."""
+        return self.ctx.trajectory_info()
 
     def dye_mixing(self):
         """(K, 3): mixing_index (StokesColor.py:391-403) (I, mu, var) of every dye channel over marker == 0, reduced
@@ -1905,7 +1983,7 @@ class Result:
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
           tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
-          tracer_seed=0, force=None, buoyancy=None, stroke=None):
+          tracer_seed=0, force=None, buoyancy=None, stroke=None, trajectory="euler"):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -1920,7 +1998,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     per tracer and step on top of the move, reproducible from the seed (StokesSimulation.tracer_diffusivity).
     force, buoyancy (schemes 'color' and 'food'; buoyancy 'color'): the body force of the steps, a pair, an (N, 2)
     field or None, and the Buoyancy of the dye (StokesSimulation.force / buoyancy; its terms may name the dyes=).
-    stroke (schemes 'color' and 'food'): a Stroke, the squirmer's boundary values per step (StokesSimulation.stroke)."""
+    stroke (schemes 'color' and 'food'): a Stroke, the squirmer's boundary values per step (StokesSimulation.stroke).
+    trajectory 'euler' | 'midpoint' (schemes 'color' and 'food'): the path of whatever the run transports -- the dye
+    on 'color', the velocity with inertia, the tracers on 'food' (StokesSimulation.dye_trajectory and its kin)."""
+    if trajectory_order(trajectory) != _lib.TRJ_EULER and scheme not in ("color", "food"):
+        raise ValueError("trajectory belongs to the Stokes schemes 'color' and 'food'")
     if stroke is not None and scheme not in ("color", "food"):
         raise ValueError("stroke belongs to the Stokes schemes 'color' and 'food'")
     _check_stroke(stroke)
@@ -1941,7 +2023,7 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
         sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection,
                                tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed, force=force,
-                               stroke=stroke)
+                               stroke=stroke, trajectory=trajectory)
         if dyes is not None:
             sim.dyes = dyes
         if buoyancy is not None:  # (behind the channels its terms may name)
