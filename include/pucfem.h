@@ -624,7 +624,8 @@ int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11);
    single-rank PUCFEM_STOKES_FOOD context, in pucfem_step and in pucfem_tracer_step (which follows the setting with
    its own dt).  Else PUCFEM_ESTATE (multi-rank, heat, Poisson, the implicit dye or STOKES_FOOD for PUCFEM_TRJ_DYE, a
    context without tracers for PUCFEM_TRJ_TRACERS; before the build; while the context has an ensemble, for either
-   order, and pucfem_ens_create while a part is on: members trace Euler steps) -- decided before the device is asked
+   order, and pucfem_ens_create while a part is on: members carry their own orders, pucfem_ens_set_trajectory) --
+   decided before the device is asked
    for --; PUCFEM_EINVAL for an unknown mask or order; PUCFEM_ENODEV on a host-only context.  With PUCFEM_TRJ_EULER a
    context steps as if this call did not exist, launch for launch.  A part holds the blocks' counts only, allocated
    when it is first switched on and freed by pucfem_build_operators and pucfem_ctx_destroy, which also set every part
@@ -656,6 +657,38 @@ int pucfem_sl_advect_vel_traj(void* ctx, int32_t order, int32_t scheme, const do
    per launch of pass 1 (the whole step with PUCFEM_ADV_SL), of pass 2 (0 with PUCFEM_ADV_SL), algorithmic bytes of
    each. */
 int pucfem_trajectory_probe(void* ctx, int32_t what, int32_t scheme, int32_t nch, int32_t iters, double* out4);
+/* Midpoint trajectories per ensemble member: the comparison of swimmers without the first-order path error, in one
+   launch chain.  Each member has an order per part -- its dye, its inertial velocity, its tracers, all
+   PUCFEM_TRJ_EULER at first -- apart from the context's own, which keeps governing pucfem_step and
+   pucfem_tracer_step alone (and pucfem_set_trajectory beside an ensemble, and pucfem_ens_create with a part on, stay
+   PUCFEM_ESTATE).  The per-row and per-tracer formulas above, unchanged, with hdt = 0.5 * dt formed on the host.
+   PUCFEM_TRJ_DYE (PUCFEM_STOKES_COLOR ensembles): the member's c moves along midpoint traces under whichever dye
+   scheme it has (pucfem_ens_set_advection: one pass, or MacCormack's two with the same clamp and T1 record): bit for
+   bit the c, the mixing record and sl_notfound (the final locate's count) of a pucfem_step run with PUCFEM_TRJ_DYE
+   set, that scheme and the member's boundary values.  PUCFEM_TRJ_VELOCITY: the member's u_a moves along midpoint
+   traces while its inertia flag is on (the part may be set at any time and waits for the flag), under either velocity
+   scheme; PUCFEM_F_U_ADV, the forces and the viscous product read that u_a, and pucfem_ens_inertia_info's not-found
+   count is the final locate's.  PUCFEM_TRJ_TRACERS (PUCFEM_STOKES_FOOD ensembles with tracers): the member's tracers
+   read their velocity again at the midpoint, with or without its Brownian increment.  A member with every part
+   PUCFEM_TRJ_EULER steps as without this call.  Orders may differ between members and between parts; one set between
+   two pucfem_ens_step calls takes effect at the next step, and switching a part on starts that member's counts
+   again.  The step stays one captured chain -- one launch more per pass behind the first-order dye / inertial launch
+   while a member runs it, the MID instantiation of the tracer launch while a member's tracer part is on -- captured
+   again only when the set of launches changes; which members run which, the kernels read from device memory.
+   Allocated when a part is first switched on: the members' counts, the launches' partials and ticket counters (a
+   MacCormack-and-midpoint member uses the MacCormack set's intermediate field and T1 records); they are counted in
+   pucfem_ens_info's bytes and freed with the ensemble.
+   member = -1: every member.  PUCFEM_ENODEV on a host-only context; PUCFEM_ESTATE without an ensemble, for
+   PUCFEM_TRJ_DYE on a PUCFEM_STOKES_FOOD ensemble and for PUCFEM_TRJ_TRACERS on an ensemble without tracers;
+   PUCFEM_EINVAL for a member out of range, an unknown mask or order. */
+int pucfem_ens_set_trajectory(void* ctx, int32_t member /* -1 = all */, int32_t what /* PUCFEM_TRJ_* mask */,
+                              int32_t order);
+/* member 0 .. members - 1, pucfem_trajectory_info's layout: out[0..2] the member's orders, [3..5] the steps each part
+   has taken while on (the velocity's: those taken with inertia on), [6] of the member's last dye launch with the part
+   on the rows whose midpoint was not found (with MacCormack: of both passes), [7] the same of its last velocity
+   launch, [8] of its last tracer launch the tracers that had a velocity and lost their midpoint -- summed on the
+   device --, [9] device bytes the ensemble holds for trajectories */
+int pucfem_ens_trajectory_info(void* ctx, int32_t member, int64_t* out10);
 
 /* ---- streamlines: the frozen flow integrated from many seeds, on the device --- */
 /* The reference's flow picture is ax.streamplot(...) of a resampled velocity (stokes_flow.py:536,

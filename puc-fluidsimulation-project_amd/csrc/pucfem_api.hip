@@ -183,6 +183,28 @@ struct Ens {
   int mc_vel_any = 0;                        // members with inertia on whose velocity does
   bool chain_mcd = false, chain_mcv = false; // the captured graphs hold the dye's / the velocity's MacCormack launches
   int nb_ws = 1;                             // blocks in x of k_ens_wsum: the single path's k_wsum grid
+  // midpoint trajectories per member (pucfem_ens_set_trajectory; k_ens_trj_fwd / k_ens_trj_bwd and the MID tracer
+  // kernels), allocated when a part is first switched on and kept: the members' counts (M x ENS_VALS, the slots
+  // ENS_TRJ_*) and the launches' ticket counters (4 M: dye pass 1 / 2, velocity pass 1 / 2); per part the launches'
+  // partials (M x 5 nb_sl) or the tracers' flags as the kernels read them (M).  The dye's order rides in mc_on_dev
+  // (ENS_DYE_*), the velocity's in adv_on_dev (ENS_ADV_*); a MacCormack-and-midpoint member uses the MacCormack set's
+  // ch and records.
+  double *trj_vals = nullptr, *trj_part_d = nullptr, *trj_part_v = nullptr;
+  unsigned* trj_cnt = nullptr;
+  int32_t* trj_trc_dev = nullptr;
+  size_t trj_bytes = 0;
+  std::vector<int32_t> trj_dye, trj_vel, trj_trc;            // the orders (empty: never switched on)
+  std::vector<int64_t> trjd_steps, trjv_steps, trjt_steps;   // per member: steps taken with the part on
+  std::vector<double> trj_host;                              // host copy of trj_vals, current while !trj_stale
+  bool trj_stale = true;
+  int dye_n[4] = {0, 0, 0, 0};     // members per dye flag ENS_DYE_*
+  int vel_n[5] = {0, 0, 0, 0, 0};  // members per inertial flag ENS_ADV_*
+  int trjt_any = 0;                // members whose tracers take the midpoint
+  int chain_trj = 0;               // the midpoint launches the captured graphs hold (trj_chain's mask)
+  int trj_chain() const {
+    return (dye_n[2] > 0 ? 1 : 0) | (dye_n[3] > 0 ? 2 : 0) | (vel_n[3] > 0 ? 4 : 0) | (vel_n[4] > 0 ? 8 : 0) |
+           (trjt_any > 0 ? 16 : 0);
+  }
   // body forces per member (pucfem_ens_set_force, pucfem_ens_set_buoyancy; k_ens_force_rhs), allocated when a member
   // is first forced and kept: the members' r (M x 2n), their term masks (M) and parameters (M x ENS_FORCE_PARM) as
   // the kernel reads them; the nodal planes (M x 2n) when a member is first given a field
@@ -1883,7 +1905,8 @@ struct Ctx {
     if (what & PUCFEM_TRJ_TRACERS) tracers_ready();
     if (ens)
       throw Error(PUCFEM_ESTATE,
-                  "the trajectory order cannot be set while the context has an ensemble (members trace one Euler step)");
+                  "the trajectory order cannot be set while the context has an ensemble (members carry their own: "
+                  "pucfem_ens_set_trajectory)");
     const bool mid = order == PUCFEM_TRJ_MIDPOINT;
     if ((what & PUCFEM_TRJ_DYE) && order != trj_dye) {
       if (st_sl) HIPCHK(hipStreamSynchronize(st_sl));
@@ -6371,7 +6394,7 @@ void ens_enqueue_step(Ctx& c) {
     KCHK();
     // with at least one inertial member's velocity scheme on: u_a = MC(u^n; u^n, dt) of those members (flag ENS_ADV_MC,
     // which k_ens_sl_vel skips) into their planes of ua -- Ctx::inertia_step's mc_vel_launch
-    if (e.mc_vel_any > 0) {
+    if (e.vel_n[ENS_ADV_MC] > 0) {
       const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
       const dbl2* f = reinterpret_cast<const dbl2*>(e.u);
       const size_t sM = (size_t)M;
@@ -6386,6 +6409,34 @@ void ens_enqueue_step(Ctx& c) {
                          reinterpret_cast<const dbl2*>(e.mcv_ch), reinterpret_cast<dbl2*>(e.ua),
                          (const int4*)e.mcv_rec, e.mcv_part + sM * e.nb_sl, r2);
       KCHK();
+    }
+    // with at least one inertial member's velocity part on: u_a along the midpoint trace of those members (flags
+    // ENS_ADV_SL_MID / ENS_ADV_MC_MID, which the launches above skip) -- Ctx::inertia_step's trj_vel_launch.  One pass
+    // straight into their planes of ua; with MacCormack pass 1 into the set's ch and records, pass 2 into ua
+    if (e.vel_n[ENS_ADV_SL_MID] > 0 || e.vel_n[ENS_ADV_MC_MID] > 0) {
+      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+      const dbl2* f = reinterpret_cast<const dbl2*>(e.u);
+      const size_t sM = (size_t)M;
+      const double hdt = 0.5 * c.prm.dt;
+      const RedOut r1{e.vals + 10, e.trj_vals + ENS_TRJ_VEL, e.trj_cnt + 2 * sM, 2, 0, 0u};
+      if (e.vel_n[ENS_ADV_SL_MID] > 0) {
+        hipLaunchKernelGGL(k_ens_trj_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_SL_MID, f,
+                           reinterpret_cast<dbl2*>(e.ua), (int4*)nullptr, e.trj_part_v, r1);
+        KCHK();
+      }
+      if (e.vel_n[ENS_ADV_MC_MID] > 0) {
+        hipLaunchKernelGGL(k_ens_trj_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC_MID, f,
+                           reinterpret_cast<dbl2*>(e.mcv_ch), e.mcv_rec, e.trj_part_v, r1);
+        KCHK();
+        const RedOut r2{e.trj_vals + ENS_TRJ_VEL + 1, nullptr, e.trj_cnt + 3 * sM, 3, 0, 0u};
+        hipLaunchKernelGGL(k_ens_trj_bwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC_MID, f,
+                           reinterpret_cast<const dbl2*>(e.mcv_ch), reinterpret_cast<dbl2*>(e.ua),
+                           (const int4*)e.mcv_rec, e.trj_part_v + sM * 2 * e.nb_sl, r2, e.vals + 13);
+        KCHK();
+      }
     }
   }
   // with at least one member forced: r = base + dt * f of those members behind it (Ctx::force_step), and the viscous
@@ -6444,27 +6495,56 @@ void ens_enqueue_step(Ctx& c) {
   div(e.u, 1, false);
   if (c.scheme == PUCFEM_STOKES_COLOR) {
     const RedOut rs{e.vals + 2, nullptr, e.cnt + M, 3, 0, 0u};
+    // (a member whose dye flag is not 0 moves its dye below: by MacCormack, along the midpoint trace, or both)
+    const bool dye_alt = e.dye_n[ENS_DYE_MC] + e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0;
     hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
                        c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
                        (const double*)c.dwmix, e.part_sl, rs,
-                       e.mc_dye_any > 0 ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
+                       dye_alt ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
     KCHK();
     // with at least one member's dye scheme on: cn = MC(c; u, dt) of those members (which k_ens_sl skipped), pass 1's
     // not-found count into slot 4 and the single path's k_wsum sums into slots 2 and 3 -- Ctx::mc_dye_step /
     // mc_dye_reduce
-    if (e.mc_dye_any > 0) {
+    if (dye_alt) {
       const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
       const size_t sM = (size_t)M;
-      const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
-      hipLaunchKernelGGL(k_ens_mc_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                         (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c, e.mc_ch,
-                         e.mc_rec, e.mc_part, r1);
-      KCHK();
-      const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
-      hipLaunchKernelGGL(k_ens_mc_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                         (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c,
-                         (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2);
-      KCHK();
+      if (e.dye_n[ENS_DYE_MC] > 0) {
+        const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
+        hipLaunchKernelGGL(k_ens_mc_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                           (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c, e.mc_ch,
+                           e.mc_rec, e.mc_part, r1);
+        KCHK();
+        const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
+        hipLaunchKernelGGL(k_ens_mc_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                           (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c,
+                           (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2);
+        KCHK();
+      }
+      // with at least one member's dye part on: cn along the midpoint trace of those members (flags ENS_DYE_SL_MID /
+      // ENS_DYE_MC_MID) -- Ctx::trj_dye_step.  One pass straight into cn; with MacCormack pass 1 into the set's ch and
+      // records, pass 2 into cn.  The final locate's count into slot 4, the sums by k_ens_wsum below
+      if (e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0) {
+        const double hdt = 0.5 * c.prm.dt;
+        const RedOut t1{e.vals + 4, e.trj_vals + ENS_TRJ_DYE, e.trj_cnt, 2, 0, 0u};
+        if (e.dye_n[ENS_DYE_SL_MID] > 0) {
+          hipLaunchKernelGGL(k_ens_trj_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_SL_MID,
+                             (const double*)e.c, e.cn, (int4*)nullptr, e.trj_part_d, t1);
+          KCHK();
+        }
+        if (e.dye_n[ENS_DYE_MC_MID] > 0) {
+          hipLaunchKernelGGL(k_ens_trj_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_MC_MID,
+                             (const double*)e.c, e.mc_ch, e.mc_rec, e.trj_part_d, t1);
+          KCHK();
+          const RedOut t2{e.trj_vals + ENS_TRJ_DYE + 1, nullptr, e.trj_cnt + sM, 3, 0, 0u};
+          hipLaunchKernelGGL(k_ens_trj_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_MC_MID,
+                             (const double*)e.c, (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec,
+                             e.trj_part_d + sM * 2 * e.nb_sl, t2, e.vals + 11);
+          KCHK();
+        }
+      }
       const RedOut rw{e.vals + 2, nullptr, e.mc_cnt + 2 * sM, 2, 0, 0u};
       hipLaunchKernelGGL(k_ens_wsum, dim3(e.nb_ws, M), dim3(BS), 0, st, (int64_t)n, (const int32_t*)e.mc_on_dev,
                          (const double*)e.cn, (const double*)c.dwmix, e.mc_part_ws, rw);
@@ -6481,14 +6561,29 @@ void ens_enqueue_step(Ctx& c) {
     const RedOut rt{e.vals + 6, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
     auto launch = [&](auto brown, auto eb) {
       constexpr bool B = decltype(brown)::value;
+      if (e.trjt_any > 0) {
+        // with at least one member's tracer part on: the MID instantiation of the same launch (which members take the
+        // midpoint the kernel reads from device memory); the members' fell-back counts beside the eaten counts
+        const EnsMid em{(const int32_t*)e.trj_trc_dev, 0.5 * c.prm.dt, e.trj_vals + ENS_TRJ_FELL};
+        const RedOut rm{e.vals + 6, e.trj_vals + ENS_TRJ_FELL, e.cnt + 3 * (size_t)M, 2, 0, 0u};
+        if (e.nb_tr > 1)
+          hipLaunchKernelGGL((k_ens_tracer_cloud<B, true>), dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
+                             (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                             c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rm, eb, em);
+        else
+          hipLaunchKernelGGL((k_ens_tracer<B, true>), dim3(1, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
+                             (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                             c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.vals, eb, em);
+        return;
+      }
       if (e.nb_tr > 1)
         hipLaunchKernelGGL(k_ens_tracer_cloud<B>, dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
                            (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
-                           c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt, eb);
+                           c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt, eb, EnsMidOff{});
       else
         hipLaunchKernelGGL(k_ens_tracer<B>, dim3(1, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n, (const double*)e.u,
                            e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt, c.prm.center_x, c.prm.center_y,
-                           c.prm.capture_radius, e.vals, eb);
+                           c.prm.capture_radius, e.vals, eb, EnsMidOff{});
     };
     if (e.br_any > 0)
       launch(std::true_type{}, EnsBrown{(const double*)e.br_a, (const uint2*)e.br_key, c.tr_ylo, c.tr_yhi});
@@ -6581,7 +6676,7 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
     state(!c.inertia, "ensembles step without inertia: switch it off first (pucfem_set_inertia)");
     state(!c.adv_dye && !c.adv_vel,
           "ensembles step the first-order advection: switch MacCormack off first (pucfem_set_advection)");
-    state(!c.trj_any(), "ensembles trace one Euler step: switch the midpoint off first (pucfem_set_trajectory)");
+    state(!c.trj_any(), "the context's midpoint is on: switch it off first (members carry their own: pucfem_ens_set_trajectory)");
     state(!c.stroked(), "the context's stroke is on: clear it first (members carry their own: pucfem_ens_set_stroke)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
@@ -6683,20 +6778,51 @@ int pucfem_ens_info(void* ctx, int64_t* out4) {
 
 // ---- inertia per member (k_ens_sl_vel, pucfem_ensemble.hpp)
 namespace {
-// the members' inertia flags as the kernels read them: ENS_ADV_MC where the member's velocity scheme is MacCormack
+// the members' inertia flags as the kernels read them: ENS_ADV_MC where the member's velocity scheme is MacCormack,
+// ENS_ADV_SL_MID / ENS_ADV_MC_MID where its velocity part is on (pucfem_ens_set_trajectory)
 void ens_adv_upload(Ctx& c, Ens& e) {
   const size_t sM = (size_t)e.M;
   e.adv_any = (int)std::count(e.adv_on.begin(), e.adv_on.end(), 1);
   e.mc_vel_any = 0;
+  for (int& k : e.vel_n) k = 0;
   if (!e.adv_on_dev) return;
   std::vector<int32_t> f(sM, ENS_ADV_OFF);
   for (size_t m = 0; m < sM; ++m)
     if (e.adv_on[m]) {
       const bool mc = !e.mc_vel.empty() && e.mc_vel[m] != PUCFEM_ADV_SL;
-      f[m] = mc ? ENS_ADV_MC : ENS_ADV_SL;
+      const bool mid = !e.trj_vel.empty() && e.trj_vel[m] == PUCFEM_TRJ_MIDPOINT;
+      f[m] = mid ? (mc ? ENS_ADV_MC_MID : ENS_ADV_SL_MID) : (mc ? ENS_ADV_MC : ENS_ADV_SL);
       e.mc_vel_any += mc ? 1 : 0;
+      ++e.vel_n[f[m]];
     }
   c.h2d(e.adv_on_dev, f.data(), sizeof(int32_t) * sM);
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+// what k_ens_sl, k_ens_wsum and the dye's MacCormack / midpoint launches read, allocated when a member's dye first
+// leaves k_ens_sl (its scheme or its trajectory part switched on) and kept: the members' dye flags (M), k_ens_wsum's
+// partials and the ticket counters of the MacCormack launches and of the sums (3 M)
+void ens_dye_flag_bufs(Ctx& c, Ens& e) {
+  if (e.mc_on_dev) return;
+  const size_t sM = (size_t)e.M;
+  e.mc_part_ws = e.alloc<double>(sM * 2 * e.nb_ws, c.st);
+  e.mc_on_dev = e.alloc<int32_t>(sM, c.st);
+  e.mc_cnt = e.alloc<unsigned>(3 * sM, c.st);
+}
+// the members' dye flags as the kernels read them (ENS_DYE_*): the scheme in bit 0, the trajectory part in bit 1
+void ens_dye_upload(Ctx& c, Ens& e) {
+  const size_t sM = (size_t)e.M;
+  e.mc_dye_any = 0;
+  for (int& k : e.dye_n) k = 0;
+  std::vector<int32_t> f(sM, ENS_DYE_SL);
+  for (size_t m = 0; m < sM; ++m) {
+    const bool mc = !e.mc_dye.empty() && e.mc_dye[m] != PUCFEM_ADV_SL;
+    const bool mid = !e.trj_dye.empty() && e.trj_dye[m] == PUCFEM_TRJ_MIDPOINT;
+    f[m] = mid ? (mc ? ENS_DYE_MC_MID : ENS_DYE_SL_MID) : (mc ? ENS_DYE_MC : ENS_DYE_SL);
+    e.mc_dye_any += mc ? 1 : 0;
+    ++e.dye_n[f[m]];
+  }
+  if (!e.mc_on_dev) return;
+  c.h2d(e.mc_on_dev, f.data(), sizeof(int32_t) * sM);
   HIPCHK(hipStreamSynchronize(c.st));
 }
 }  // namespace
@@ -6778,9 +6904,7 @@ int pucfem_ens_set_advection(void* ctx, int32_t member, int32_t what, int32_t sc
         e.mc_ch = e.alloc<double>(sM * sn, c.st);
         e.mc_rec = e.alloc<int4>(sM * sn, c.st);
         e.mc_part = e.alloc<double>(sM * 3 * e.nb_sl, c.st);
-        e.mc_part_ws = e.alloc<double>(sM * 2 * e.nb_ws, c.st);
-        e.mc_on_dev = e.alloc<int32_t>(sM, c.st);
-        e.mc_cnt = e.alloc<unsigned>(3 * sM, c.st);
+        ens_dye_flag_bufs(c, e);
         e.mc_dye.assign(sM, 0);
         e.mc_steps.assign(sM, 0);
       }
@@ -6814,10 +6938,7 @@ int pucfem_ens_set_advection(void* ctx, int32_t member, int32_t what, int32_t sc
       }
     }
     e.mc_bytes += e.bytes - before;
-    if (up_dye) {
-      e.mc_dye_any = (int)std::count(e.mc_dye.begin(), e.mc_dye.end(), (int32_t)PUCFEM_ADV_MACCORMACK);
-      c.h2d(e.mc_on_dev, e.mc_dye.data(), sizeof(int32_t) * sM);
-    }
+    if (up_dye) ens_dye_upload(c, e);
     if (up_vel) ens_adv_upload(c, e);  // (takes effect while the member's inertia flag is on)
     e.adv_stale = true;
     HIPCHK(hipStreamSynchronize(c.st));
@@ -6855,6 +6976,102 @@ int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11) {
       out11[9] = val(14);
     }
     out11[10] = (int64_t)e.mc_bytes;
+  });
+}
+
+// ---- midpoint trajectories per member (k_ens_trj_fwd / k_ens_trj_bwd, the MID tracer kernels, pucfem_ensemble.hpp)
+int pucfem_ens_set_trajectory(void* ctx, int32_t member, int32_t what, int32_t order) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= -1 && member < e.M, "member index out of range");
+    constexpr int all = PUCFEM_TRJ_DYE | PUCFEM_TRJ_VELOCITY | PUCFEM_TRJ_TRACERS;
+    if (what & ~all || what == 0)
+      throw Error(PUCFEM_EINVAL, "what is a mask of PUCFEM_TRJ_DYE, PUCFEM_TRJ_VELOCITY and PUCFEM_TRJ_TRACERS");
+    if (order != PUCFEM_TRJ_EULER && order != PUCFEM_TRJ_MIDPOINT)
+      throw Error(PUCFEM_EINVAL, "unknown trajectory order");
+    if ((what & PUCFEM_TRJ_DYE) && c.scheme != PUCFEM_STOKES_COLOR)
+      throw Error(PUCFEM_ESTATE, "the dye's trajectory needs a STOKES_COLOR ensemble: STOKES_FOOD has no dye");
+    if ((what & PUCFEM_TRJ_TRACERS) && e.ntr <= 0)
+      throw Error(PUCFEM_ESTATE, "the tracers' trajectory needs a STOKES_FOOD ensemble with tracers");
+    const size_t sM = (size_t)e.M;
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
+    const bool mid = order == PUCFEM_TRJ_MIDPOINT;
+    const size_t before = e.bytes;
+    if (mid && !e.trj_vals) {  // (nothing was ever on: nothing is allocated until now)
+      e.trj_vals = e.alloc<double>(sM * ENS_VALS, c.st);
+      e.trj_cnt = e.alloc<unsigned>(4 * sM, c.st);
+    }
+    // one part: its buffers at the first switch-on, the members' orders, and for a member switched on its counts anew
+    auto part = [&](std::vector<int32_t>& ord, std::vector<int64_t>& steps, int slot0, int nslots, auto&& bufs) {
+      if (ord.empty()) {
+        if (!mid) return false;
+        bufs();
+        ord.assign(sM, PUCFEM_TRJ_EULER);
+        steps.assign(sM, 0);
+      }
+      bool changed = false;
+      for (size_t m = m0; m < m1; ++m) {
+        if (ord[m] == order) continue;
+        ord[m] = order;
+        changed = true;
+        if (mid) {
+          steps[m] = 0;
+          HIPCHK(hipMemsetAsync(e.trj_vals + ENS_VALS * m + slot0, 0, nslots * sizeof(double), c.st));
+        }
+      }
+      return changed;
+    };
+    bool up_dye = false, up_vel = false, up_trc = false;
+    if (what & PUCFEM_TRJ_DYE)
+      up_dye = part(e.trj_dye, e.trjd_steps, ENS_TRJ_DYE, 4, [&] {
+        e.trj_part_d = e.alloc<double>(sM * 5 * e.nb_sl, c.st);
+        ens_dye_flag_bufs(c, e);
+      });
+    if (what & PUCFEM_TRJ_VELOCITY)
+      up_vel = part(e.trj_vel, e.trjv_steps, ENS_TRJ_VEL, 4,
+                    [&] { e.trj_part_v = e.alloc<double>(sM * 5 * e.nb_sl, c.st); });
+    if (what & PUCFEM_TRJ_TRACERS)
+      up_trc = part(e.trj_trc, e.trjt_steps, ENS_TRJ_FELL, 1, [&] { e.trj_trc_dev = e.alloc<int32_t>(sM, c.st); });
+    e.trj_bytes += e.bytes - before;
+    if (up_dye) ens_dye_upload(c, e);
+    if (up_vel) ens_adv_upload(c, e);  // (takes effect while the member's inertia flag is on)
+    if (up_trc) {
+      std::vector<int32_t> f(sM);
+      for (size_t m = 0; m < sM; ++m) f[m] = e.trj_trc[m] == PUCFEM_TRJ_MIDPOINT ? 1 : 0;
+      e.trjt_any = (int)std::count(f.begin(), f.end(), 1);
+      c.h2d(e.trj_trc_dev, f.data(), sizeof(int32_t) * sM);
+    }
+    e.trj_stale = e.adv_stale = true;
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_ens_trajectory_info(void* ctx, int32_t member, int64_t* out10) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_of(c);
+    require(member >= 0 && member < e.M, "member index out of range");
+    require(out10 != nullptr, "null output");
+    const size_t m = (size_t)member;
+    if (e.trj_vals && (e.trj_stale || e.trj_host.empty())) {  // (one copy serves every member until the next step)
+      e.trj_host.resize((size_t)e.M * ENS_VALS);
+      c.d2h(e.trj_host.data(), e.trj_vals, sizeof(double) * e.trj_host.size());
+      e.trj_stale = false;
+    }
+    auto val = [&](int slot) { return e.trj_vals ? (int64_t)std::llround(e.trj_host[ENS_VALS * m + slot]) : 0; };
+    const bool dye = !e.trj_dye.empty(), vel = !e.trj_vel.empty(), trc = !e.trj_trc.empty();
+    out10[0] = dye ? e.trj_dye[m] : PUCFEM_TRJ_EULER;
+    out10[1] = vel ? e.trj_vel[m] : PUCFEM_TRJ_EULER;
+    out10[2] = trc ? e.trj_trc[m] : PUCFEM_TRJ_EULER;
+    out10[3] = dye ? e.trjd_steps[m] : 0;
+    out10[4] = vel ? e.trjv_steps[m] : 0;
+    out10[5] = trc ? e.trjt_steps[m] : 0;
+    // (of the member's last launch with the part on, as pucfem_trajectory_info: with MacCormack both passes count)
+    out10[6] = val(ENS_TRJ_DYE) + (!e.mc_dye.empty() && e.mc_dye[m] ? val(ENS_TRJ_DYE + 3) : 0);
+    out10[7] = val(ENS_TRJ_VEL) + (!e.mc_vel.empty() && e.mc_vel[m] ? val(ENS_TRJ_VEL + 3) : 0);
+    out10[8] = val(ENS_TRJ_FELL);
+    out10[9] = (int64_t)e.trj_bytes;
   });
 }
 
@@ -7023,11 +7240,13 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     // (and for the body forces: the force launch iff a member is forced, with the nodal planes once they exist)
     // (and for MacCormack: the dye's three launches iff a member's dye scheme is on, the velocity's two iff an
     // inertial member's velocity scheme is)
+    // (and for the midpoint trajectories: each of their launches iff a member runs it, Ens::trj_chain)
     // (and for the strokes: the stroke launch iff a member has one; pucfem_ens_set_stroke drops the graphs itself when
     // it reallocates the tables or the shared shapes)
     if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0) || e.chain_force != (e.force_any > 0) ||
-        e.chain_fnod != (e.fnod != nullptr) || e.chain_mcd != (e.mc_dye_any > 0) ||
-        e.chain_mcv != (e.mc_vel_any > 0) || e.chain_stroke != (e.stroke_any > 0)) {
+        e.chain_fnod != (e.fnod != nullptr) || e.chain_mcd != (e.dye_n[ENS_DYE_MC] > 0) ||
+        e.chain_mcv != (e.vel_n[ENS_ADV_MC] > 0) || e.chain_stroke != (e.stroke_any > 0) ||
+        e.chain_trj != e.trj_chain()) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
       e.chain_stroke = e.stroke_any > 0;
@@ -7035,8 +7254,9 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       e.chain_br = e.br_any > 0;
       e.chain_force = e.force_any > 0;
       e.chain_fnod = e.fnod != nullptr;
-      e.chain_mcd = e.mc_dye_any > 0;
-      e.chain_mcv = e.mc_vel_any > 0;
+      e.chain_mcd = e.dye_n[ENS_DYE_MC] > 0;
+      e.chain_mcv = e.vel_n[ENS_ADV_MC] > 0;
+      e.chain_trj = e.trj_chain();
     }
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
@@ -7072,6 +7292,13 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     for (size_t m = 0; m < sM && e.mc_vel_any > 0; ++m)
       if (e.mc_vel[m] && e.adv_on[m]) e.mcv_steps[m] += nsteps;
     if (e.mc_dye_any > 0 || e.mc_vel_any > 0) e.adv_stale = true;
+    for (size_t m = 0; m < sM && !e.trj_dye.empty(); ++m)
+      if (e.trj_dye[m] == PUCFEM_TRJ_MIDPOINT) e.trjd_steps[m] += nsteps;
+    for (size_t m = 0; m < sM && !e.trj_vel.empty() && e.adv_any > 0; ++m)
+      if (e.trj_vel[m] == PUCFEM_TRJ_MIDPOINT && e.adv_on[m]) e.trjv_steps[m] += nsteps;
+    for (size_t m = 0; m < sM && !e.trj_trc.empty(); ++m)
+      if (e.trj_trc[m] == PUCFEM_TRJ_MIDPOINT) e.trjt_steps[m] += nsteps;
+    if (e.trj_vals) e.trj_stale = e.adv_stale = true;
     for (size_t m = 0; m < sM && e.force_any > 0; ++m)
       if (e.fmask[m]) e.fsteps[m] += nsteps;
     if (stats)

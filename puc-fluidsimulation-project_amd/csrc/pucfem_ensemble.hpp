@@ -29,6 +29,16 @@ constexpr int ENS_VALS = 16;
 // a member's flag as the inertial kernels read it (Ens::adv_on_dev): off, first order (k_ens_sl_vel), MacCormack
 // (k_ens_mc_fwd / k_ens_mc_bwd); the consumers of ua (k_ens_force_rhs, k_ens_mv2_bc) read any non-zero value as on
 constexpr int32_t ENS_ADV_OFF = 0, ENS_ADV_SL = 1, ENS_ADV_MC = 2;
+// ... with the midpoint trajectory (k_ens_trj_fwd / k_ens_trj_bwd<dbl2>): values k_ens_sl_vel and k_ens_mc_*<dbl2> skip
+constexpr int32_t ENS_ADV_SL_MID = 3, ENS_ADV_MC_MID = 4;
+// a member's dye flag (Ens::mc_on_dev): 0 k_ens_sl moves its dye; 1 k_ens_mc_*<double>; 2 / 3 the midpoint trajectory
+// with one pass / with MacCormack's two (k_ens_trj_*<double>).  k_ens_sl leaves, and k_ens_wsum runs, on any non-zero
+constexpr int32_t ENS_DYE_SL = 0, ENS_DYE_MC = 1, ENS_DYE_SL_MID = 2, ENS_DYE_MC_MID = 3;
+// the members' trajectory counts (Ens::trj_vals, stride ENS_VALS like vals): 0 the rows of the last dye launch whose
+// pass-1 midpoint was not found, 1 / 2 pass 2's rows without T2 and clamped values (copied into vals 11 / 12), 3 its
+// rows without midpoint; 4..7 the same of the last velocity launch (5 / 6 copied into vals 13 / 14); 8 the tracers of
+// the last launch that fell back to their Euler step
+constexpr int ENS_TRJ_DYE = 0, ENS_TRJ_VEL = 4, ENS_TRJ_FELL = 8;
 
 // the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
 // (NP partial arrays of gridDim.x blocks per member)
@@ -545,6 +555,144 @@ __global__ __launch_bounds__(BS) void k_ens_wsum(int64_t n, const int32_t* __res
   red_finish(R, part, sh);
 }
 
+// Midpoint trajectories per member (pucfem_ens_set_trajectory; pucfem_trajectory.hpp): the
+// wave-per-row forms of k_trj_fwd / k_trj_bwd (F = double: the dye) and of k_trj_fwd_vel / k_trj_bwd_vel (F = dbl2: the
+// velocity's interleaved pairs), on k_ens_sl's grid in x, with the locate members already run (sl_point,
+// sl_locate_wave, sl_value).  The single path's sl_locate_row is, for the record locator, sl_locate_general, whose
+// triangle sl_locate_wave returns (pucfem_locate.hpp): the midpoint velocity, the final point and the value hold the
+// single path's bits.  A member whose flag on[m] is not `want` leaves at once (block-uniform, in front of every barrier
+// and of the ticket), as in k_ens_mc_*.
+//
+// The two locates of a row as one loop body run twice (trj_locate's form: one inlined locate and one SlTri, so that the
+// kernel keeps the registers of a one-pass kernel and no scratch).  In: (vx, vy) = u[g]; out: the velocity the row was
+// traced with (in registers only), (xb, yb) and r the final point and its triangle, okm whether the midpoint was found.
+__device__ __forceinline__ bool ens_trj_locate(const MeshDev& Mh, const LocDev& L, const GridDev& G, int64_t g,
+                                               double& vx, double& vy, double dt, double hdt, const dbl2* um,
+                                               double& xb, double& yb, SlTri& r, bool& okm) {
+  bool ok = false;
+  okm = true;
+#pragma unroll 1
+  for (int ph = 0; ph < 2; ++ph) {
+    sl_point(Mh, g, vx, vy, ph == 0 ? hdt : dt, xb, yb);
+    ok = sl_locate_wave(L, G, xb, yb, r);
+    if (ph == 0) {
+      okm = ok;
+      if (ok) {
+        const dbl2 w = sl_value(r, xb, yb, um);
+        vx = w.x;
+        vy = w.y;
+      }
+    }
+  }
+  return ok;
+}
+// Pass 1 (and the whole of a one-pass step): out = SL(f; w, +dt) along the midpoint velocity w, and with rec the row's
+// T1 (id = -1: none, and out keeps f).  u: M x 2n, f / out: M x n values of F (out aliases neither u nor f), rec: M x n
+// or null.  Per member, per-block partials summed by red_finish in block order: value 0 the rows whose final locate
+// found nothing (ro.out), value 1 those whose midpoint was not found (ro.out1).  part: M x 2 gridDim.x.
+template <class F>
+__global__ __launch_bounds__(BS) void k_ens_trj_fwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                    const double* __restrict__ u, double dt, double hdt,
+                                                    const int32_t* __restrict__ on, int32_t want, const F* f,
+                                                    F* __restrict__ out, int4* __restrict__ rec, double* part,
+                                                    RedOut ro) {
+  __shared__ double sw_[2][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (on[m] != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  const F* fm = f + (int64_t)m * n;
+  F* om = out + (int64_t)m * n;
+  int4* rm = rec ? rec + (int64_t)m * n : nullptr;
+  const RedOut R = ens_red<2>(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nnf = 0.0, nmid = 0.0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double wx = v.x, wy = v.y, xb, yb;
+    SlTri r{};
+    bool okm;
+    const bool ok = ens_trj_locate(Mh, L, G, i, wx, wy, dt, hdt, um, xb, yb, r, okm);
+    if (!ok) nnf = 1.0;
+    if (!okm) nmid = 1.0;
+    const F o = ok ? sl_value(r, xb, yb, fm) : fm[i];
+    if (lane == 0) {
+      om[i] = o;
+      if (rm) rm[i] = ok ? make_int4(r.a, r.b, r.d, r.id) : make_int4(0, 0, 0, -1);
+    }
+  }
+  if (lane == 0) {
+    sw_[0][wv] = nnf;
+    sw_[1][wv] = nmid;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 0; v < 2; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  red_finish(R, part, sh);
+}
+// Pass 2 (MacCormack members): the same two locates from the same node with -dt and -hdt (the midpoint read from u),
+// pass 1's record and mc_row on (f, ch).  out aliases neither f nor ch.  Per member, values 0..2 into ro.out: the rows
+// without T2, the clamped values, the rows whose pass-2 midpoint was not found; the block that reduced copies the first
+// two into cnt2 (the member's MacCormack slots of vals: thread 0 stored them itself).  part: M x 3 gridDim.x.
+template <class F>
+__global__ __launch_bounds__(BS) void k_ens_trj_bwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                    const double* __restrict__ u, double dt, double hdt,
+                                                    const int32_t* __restrict__ on, int32_t want, const F* f,
+                                                    const F* ch, F* __restrict__ out, const int4* __restrict__ rec,
+                                                    double* part, RedOut ro, double* __restrict__ cnt2) {
+  __shared__ double sw_[3][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (on[m] != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  const F* fm = f + (int64_t)m * n;
+  const F* chm = ch + (int64_t)m * n;
+  F* om = out + (int64_t)m * n;
+  const int4* rm = rec + (int64_t)m * n;
+  const RedOut R = ens_red<3>(ro, m, part);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nb2 = 0.0, nmid = 0.0;
+  int32_t ncl = 0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double wx = v.x, wy = v.y, xb, yb;
+    SlTri r{};
+    bool okm;
+    const bool ok2 = ens_trj_locate(Mh, L, G, i, wx, wy, -dt, -hdt, um, xb, yb, r, okm);
+    if (!ok2) nb2 = 1.0;
+    if (!okm) nmid = 1.0;
+    const F o = mc_row(rm[i], ok2, r, xb, yb, i, fm, chm, ncl);
+    if (lane == 0) om[i] = o;
+  }
+  if (lane == 0) {
+    sw_[0][wv] = nb2;
+    sw_[1][wv] = (double)ncl;
+    sw_[2][wv] = nmid;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  if (red_finish(R, part, sh) && threadIdx.x == 0) {
+    double* c2 = cnt2 + (int64_t)ENS_VALS * m;
+    c2[0] = R.out[0];
+    c2[1] = R.out[1];
+  }
+}
+
 // k_mix2 per member: sum w (c - mu)^2 of the new dye cn (mu from vals 2 / 3), copied into c.  cn, c: M x n.
 __global__ __launch_bounds__(BS) void k_ens_mix2(int64_t n, const double* __restrict__ cn, const double* __restrict__ wmix,
                                                  const double* vals, double* part, RedOut ro, double* __restrict__ c) {
@@ -582,14 +730,28 @@ __device__ __forceinline__ Brown ens_brown(const EnsBrownArg<BROWN>& eb, int32_t
   }
 }
 
+// midpoint tracer steps per member (pucfem_ens_set_trajectory, PUCFEM_TRJ_TRACERS), the MID variants' argument:
+// on[m] != 0: member m takes tracer_mid's velocity (a block-uniform branch, as a[m] == 0 is for BROWN); fell: the
+// members' counts of their last midpoint launch (stride ENS_VALS), the tracers that had a velocity and lost their
+// midpoint -- stored (not added) by every launch for the members that are on, so nothing is zeroed outside the chain
+struct EnsMid {
+  const int32_t* on;
+  double hdt;  // 0.5 * dt, from the host
+  double* fell;
+};
+struct EnsMidOff {};  // the Euler kernels' (empty) argument
+template <bool MID>
+using EnsMidArg = std::conditional_t<MID, EnsMid, EnsMidOff>;
+
 // k_tracer per member (one block each): the single path's locate / interpolate / move.  tx, ty, status: M x ntr.
 // BROWN (pucfem_brownian.hpp): the member's amplitude and key from device memory; a block-uniform branch, a[m] == 0
-// the plain move.
-template <bool BROWN>
+// the plain move.  MID: tracer_mid itself for the members whose flag is set, and their count of the launch.
+template <bool BROWN, bool MID = false>
 __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                    int32_t ntr, double* tx, double* ty, double* status,
                                                    int32_t* capstep, int32_t* stepctr, double dt, double cx, double cy,
-                                                   double capture, double* vals, EnsBrownArg<BROWN> eb) {
+                                                   double capture, double* vals, EnsBrownArg<BROWN> eb,
+                                                   EnsMidArg<MID> em) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -601,6 +763,9 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
   const int32_t stepno = stepctr[m] + 1;  // (the member's own count: k_tracer's)
   const Brown br = ens_brown<BROWN>(eb, m);
   double eaten = 0.0;
+  [[maybe_unused]] int32_t fell = 0;
+  [[maybe_unused]] bool mid = false;
+  if constexpr (MID) mid = em.on[m] != 0;
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
     if (BROWN && br.a != 0.0) {
       if (stm[k] == 1.0) {
@@ -612,10 +777,17 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(Mh, G, px, py);
     if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+    if constexpr (MID) {
+      if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+    }
     if (BROWN && br.a != 0.0)
       eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
     else
       eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  if constexpr (MID) {
+    const double f = block_sum((double)fell, sh);
+    if (threadIdx.x == 0 && mid) em.fell[(int64_t)ENS_VALS * m] = f;
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) {
@@ -623,13 +795,14 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
     stepctr[m] = stepno;
   }
 }
-// k_tracer_cloud per member: grid (blocks, M), the member's partials, ticket and step count (ro.out: vals + 6)
-template <bool BROWN>
+// k_tracer_cloud per member: grid (blocks, M), the member's partials, ticket and step count (ro.out: vals + 6; MID:
+// value 1 of the reduction is the member's fell-back count, into ro.out1)
+template <bool BROWN, bool MID = false>
 __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                          int32_t ntr, double* tx, double* ty, double* status,
                                                          int32_t* capstep, int32_t* stepctr, double dt, double cx,
                                                          double cy, double capture, double* part, RedOut ro,
-                                                         EnsBrownArg<BROWN> eb) {
+                                                         EnsBrownArg<BROWN> eb, EnsMidArg<MID> em) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -638,10 +811,16 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
   double* tym = ty + (int64_t)m * ntr;
   double* stm = status + (int64_t)m * ntr;
   int32_t* cpm = capstep + (int64_t)m * ntr;
-  const RedOut R = ens_red(ro, m, part);
+  RedOut R = ens_red(ro, m, part);
   const int32_t stepno = stepctr[m] + 1;
   const Brown br = ens_brown<BROWN>(eb, m);
   double eaten = 0.0;
+  [[maybe_unused]] int32_t fell = 0;
+  [[maybe_unused]] bool mid = false;
+  if constexpr (MID) {
+    mid = em.on[m] != 0;
+    if (!mid) R.nv = 1;  // (the launch reduces two values: a member off keeps its count of its last midpoint launch)
+  }
   for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
     const int32_t k = (int32_t)i;
     if (BROWN && br.a != 0.0) {
@@ -654,10 +833,17 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
     double vx = NAN, vy = NAN;
     const int32_t found = tracer_locate(Mh, G, px, py);
     if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+    if constexpr (MID) {
+      if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+    }
     if (BROWN && br.a != 0.0)
       eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
     else
       eaten += tracer_move(txm, tym, stm, cpm, k, vx, vy, dt, cx, cy, capture, stepno);
+  }
+  if constexpr (MID) {
+    const double f = block_sum((double)fell, sh);
+    if (threadIdx.x == 0 && mid) red_part(R, part, 1, f);
   }
   const double t = block_sum(eaten, sh);
   if (threadIdx.x == 0) red_part(R, part, 0, t);

@@ -15,6 +15,8 @@
 //
 // u is the full mesh's interleaved pairs (single-rank contexts: the rows of a launch are rows of u).  The kernels are
 // new ones beside k_sl_multi / k_sl_vel / k_mc_*: the instantiations an Euler step launches are untouched.
+// Ensemble members run the wave-per-row forms of these kernels, k_ens_trj_fwd / k_ens_trj_bwd (pucfem_ensemble.hpp,
+// DESIGN.md section 28), whose two phases are trj_locate's loop with sl_locate_wave in sl_locate_row's place.
 #pragma once
 #include "pucfem_maccormack.hpp"
 

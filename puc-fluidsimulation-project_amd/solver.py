@@ -1370,6 +1370,38 @@ def _ensemble_schemes(scheme, M, name):
     return np.array([advection_scheme(v) for v in names], dtype=np.int32)
 
 
+def _ensemble_orders(order, M, name):
+    """The dye_trajectory= / velocity_trajectory= / tracer_trajectory= argument of an ensemble of M members as an (M,)
+    array of PUCFEM_TRJ_* values: one name for all, or M of them."""
+    if isinstance(order, (str, int, np.integer)):
+        return np.full(M, trajectory_order(order), dtype=np.int32)
+    names = list(order)
+    if len(names) != M:
+        raise ValueError(f"{name} must be one name or one per member: {M} members, got {len(names)}")
+    return np.array([trajectory_order(v) for v in names], dtype=np.int32)
+
+
+def _ensemble_trajectories(scheme, flags, trajectory, dye, velocity, tracers):
+    """The trajectory keywords of an ensemble as three (M,) arrays of PUCFEM_TRJ_* values (dye, velocity, tracers).
+    trajectory= is StokesSimulation's rule per member: the dye on 'color', the tracers on 'food', the velocity for the
+    members whose inertia flag is on; a per-part keyword, where given, wins for that part."""
+    M = len(flags)
+    euler = np.full(M, _lib.TRJ_EULER, dtype=np.int32)
+    if not isinstance(trajectory, (str, int, np.integer)):
+        raise ValueError("trajectory is one name for the ensemble: use dye_trajectory=, velocity_trajectory= and "
+                         "tracer_trajectory= for one per member")
+    trj = np.full(M, trajectory_order(trajectory), dtype=np.int32)
+    d = _ensemble_orders(dye, M, "dye_trajectory") if dye is not None else (trj if scheme == "color" else euler)
+    v = (_ensemble_orders(velocity, M, "velocity_trajectory") if velocity is not None
+         else np.where(flags, trj, euler).astype(np.int32))
+    t = _ensemble_orders(tracers, M, "tracer_trajectory") if tracers is not None else (trj if scheme == "food" else euler)
+    if dye is not None and (d != _lib.TRJ_EULER).any() and scheme != "color":
+        raise ValueError("dye_trajectory='midpoint' belongs to scheme 'color': a 'food' run has no dye")
+    if tracers is not None and (t != _lib.TRJ_EULER).any() and scheme != "food":
+        raise ValueError("tracer_trajectory='midpoint' belongs to scheme 'food': a 'color' run has no tracers")
+    return d, v, t
+
+
 def ensemble_dirichlet_values(mesh: Mesh, bcs):
     """Dirichlet nodes and per-member values (M, n_dir, 2) of an ensemble: row m is stokes_setup(mesh, bcs[m])'s
     values (the wall values, then the squirmer surface values of makeDirBCU, StokesColor.py:405-427).  Host only."""
@@ -1400,11 +1432,17 @@ class StokesEnsemble:
     bit (set_force, set_buoyancy).
     dye_advection, velocity_advection: 'sl' or 'maccormack', one name for all members or one per member -- a member
     whose dye scheme is 'maccormack' moves its c as StokesSimulation(..., advection="maccormack") does, one whose
-    velocity scheme is forms its u_a that way while its inertia is on, bit for bit (set_advection)."""
+    velocity scheme is forms its u_a that way while its inertia is on, bit for bit (set_advection).
+    dye_trajectory, velocity_trajectory, tracer_trajectory: 'euler' or 'midpoint', one name for all members or one per
+    member -- a member with a part on moves its c, its u_a (while its inertia is on) or its tracers along midpoint
+    traces as StokesSimulation(...) with that part on does, bit for bit (set_trajectory).  trajectory= is
+    StokesSimulation's keyword applied per member: the dye on 'color', the tracers on 'food', the velocity of the
+    members whose inertia flag is on; a per-part keyword, where given, wins over it for that part."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
                  tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
-                 buoyancy=None, dye_advection="sl", velocity_advection="sl", stroke=None):
+                 buoyancy=None, dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
+                 velocity_trajectory=None, tracer_trajectory=None, trajectory="euler"):
         _ensemble_advection(advection)
         if buoyancy is not None and scheme != "color":
             raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
@@ -1417,6 +1455,8 @@ class StokesEnsemble:
         adv_vel = _ensemble_schemes(velocity_advection, len(self.bcs), "velocity_advection")
         if adv_dye.any() and scheme != "color":
             raise ValueError("dye_advection='maccormack' belongs to scheme 'color': a 'food' run has no dye")
+        trj_dye, trj_vel, trj_trc = _ensemble_trajectories(scheme, flags, trajectory, dye_trajectory,
+                                                           velocity_trajectory, tracer_trajectory)
         diff, seeds = _ensemble_diffusion(tracer_diffusivity, tracer_seed, len(self.bcs))
         nodes, vals = ensemble_dirichlet_values(mesh, self.bcs)
         self.mesh = mesh
@@ -1447,6 +1487,12 @@ class StokesEnsemble:
                 self.dye_advection = adv_dye
             if adv_vel.any():
                 self.velocity_advection = adv_vel
+            if (trj_dye != _lib.TRJ_EULER).any():
+                self.dye_trajectory = trj_dye
+            if (trj_vel != _lib.TRJ_EULER).any():
+                self.velocity_trajectory = trj_vel
+            if (trj_trc != _lib.TRJ_EULER).any():
+                self.tracer_trajectory = trj_trc
             if diff.any() or seeds.any():
                 self.set_tracer_diffusion(diff, seeds)
             if force is not None:
@@ -1594,6 +1640,72 @@ class StokesEnsemble:
     @velocity_advection.setter
     def velocity_advection(self, scheme):
         self._set_schemes(_lib.ADV_VELOCITY, scheme, "velocity_advection")
+
+    # ---- midpoint trajectories per member (pucfem_ens_set_trajectory)
+    def set_trajectory(self, what, order, member=None):
+        """The trajectory order of one member (or, member=None, of all): of its dye (what = TRJ_DYE), of its inertial
+        step's velocity (TRJ_VELOCITY), of its tracers (TRJ_TRACERS) or of several (their sum); 'euler' or 'midpoint'.
+        It takes effect at the next step (the velocity's while the member's inertia is on); switching a part on starts
+        the member's counts (trajectory_info) again."""
+        self.ctx._c(self.ctx.L.pucfem_ens_set_trajectory(self.ctx.h, -1 if member is None else int(member), int(what),
+                                                         trajectory_order(order)))
+
+    def trajectory_info(self, member=None):
+        """pucfem_ens_trajectory_info, with Context.trajectory_info's keys: the member's three orders, the steps each
+        part has taken while on, the rows of its last dye and velocity launch whose midpoint was not found, the tracers
+        of its last launch that fell back to their Euler step and the device bytes the ensemble holds for
+        trajectories -- one member's dict, or (member=None) a list of them, one per member."""
+        def one(m):
+            o = (ct.c_int64 * 10)()
+            self.ctx._c(self.ctx.L.pucfem_ens_trajectory_info(self.ctx.h, int(m), o))
+            return dict(dye=TRAJECTORY_NAMES[o[0] - 1], velocity=TRAJECTORY_NAMES[o[1] - 1],
+                        tracers=TRAJECTORY_NAMES[o[2] - 1], dye_steps=o[3], velocity_steps=o[4], tracer_steps=o[5],
+                        dye_mid_notfound=o[6], velocity_mid_notfound=o[7], tracers_fell_back=o[8], bytes=o[9])
+
+        if member is not None:
+            return one(member)
+        return [one(m) for m in range(self.M)]
+
+    def _set_orders(self, what, order, name):
+        v = _ensemble_orders(order, self.M, name)
+        if (v == v[0]).all():
+            self.set_trajectory(what, int(v[0]))
+        else:
+            for m, k in enumerate(v):
+                self.set_trajectory(what, int(k), m)
+
+    def _orders(self, key):
+        return np.array([r[key] for r in self.trajectory_info()])
+
+    @property
+    def dye_trajectory(self):
+        """(M,) names, 'euler' or 'midpoint': the trace each member's step moves its c along
+        (StokesSimulation.dye_trajectory per member).  Set it with one name for all or one per member."""
+        return self._orders("dye")
+
+    @dye_trajectory.setter
+    def dye_trajectory(self, order):
+        self._set_orders(_lib.TRJ_DYE, order, "dye_trajectory")
+
+    @property
+    def velocity_trajectory(self):
+        """(M,) names: the trace each member's inertial step forms u_a along.  It may be set while the member's
+        inertia is off and takes effect when it is on."""
+        return self._orders("velocity")
+
+    @velocity_trajectory.setter
+    def velocity_trajectory(self, order):
+        self._set_orders(_lib.TRJ_VELOCITY, order, "velocity_trajectory")
+
+    @property
+    def tracer_trajectory(self):
+        """(M,) names: 'midpoint' members read their tracers' velocity again half a step along the first one; a
+        tracer whose midpoint leaves the mesh takes its Euler step (trajectory_info counts them)."""
+        return self._orders("tracers")
+
+    @tracer_trajectory.setter
+    def tracer_trajectory(self, order):
+        self._set_orders(_lib.TRJ_TRACERS, order, "tracer_trajectory")
 
     # ---- time-dependent strokes per member (pucfem_ens_set_stroke)
     def set_stroke(self, stroke, member=None):
@@ -1831,21 +1943,26 @@ class StokesEnsemble:
 
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
                    inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
-                   dye_advection="sl", velocity_advection="sl", stroke=None):
+                   dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
+                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler"):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
     'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
     would not say which of the two).  tracer_diffusivity, tracer_seed: one value for all members or one per member
     (StokesEnsemble.set_tracer_diffusion).  force, buoyancy: one setting for all members or a list with one per
     member (StokesEnsemble.set_force / set_buoyancy).  stroke: a Stroke for all members or a list with one Stroke or
-    None per member (StokesEnsemble.set_stroke)."""
+    None per member (StokesEnsemble.set_stroke).  dye_trajectory, velocity_trajectory, tracer_trajectory: 'euler' or
+    'midpoint', one name for all members or one per member; trajectory: StokesSimulation's keyword per member
+    (StokesEnsemble.set_trajectory)."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
     dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
     ens = StokesEnsemble(mesh, bcs, dt, scheme, device, tol, inertia=inertia, tracer_diffusivity=tracer_diffusivity,
                          tracer_seed=tracer_seed, force=force, buoyancy=buoyancy, dye_advection=dye_advection,
-                         velocity_advection=velocity_advection, stroke=stroke)
+                         velocity_advection=velocity_advection, stroke=stroke, dye_trajectory=dye_trajectory,
+                         velocity_trajectory=velocity_trajectory, tracer_trajectory=tracer_trajectory,
+                         trajectory=trajectory)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
