@@ -312,9 +312,10 @@ int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t
    1 .. PUCFEM_MAX_DYES, or a channel k >= K.  Setting PUCFEM_F_DYES resets the channel step count; setting one
    channel (PUCFEM_F_DYE0 + k), PUCFEM_F_C or PUCFEM_F_U leaves the channels and their count alone.
    pucfem_build_operators and pucfem_ctx_destroy drop the channels.  PUCFEM_F_DYE0 + k is also a one-component
-   field of pucfem_sample_points, pucfem_raster and the values of pucfem_streamlines; ensembles have no channels
-   (PUCFEM_EINVAL in the pucfem_ens_* calls).  A small-mesh context steps from a captured graph only while it has
-   no channels; with channels it runs the same launches uncaptured (the same bits). */
+   field of pucfem_sample_points, pucfem_raster and the values of pucfem_streamlines.  Ensembles carry channels of
+   their own, the same number for every member (pucfem_ens_set_dyes below); an ensemble without channels takes no
+   dye field (PUCFEM_EINVAL in the pucfem_ens_* calls).  A small-mesh context steps from a captured graph only while
+   it has no channels; with channels it runs the same launches uncaptured (the same bits). */
 /* out[0] K, [1] channel steps since the channels were set, [2] not-found rows of the last channel launch (the same
    for every channel; 0 before the first), [3] device bytes held for the channels */
 int pucfem_dyes_info(void* ctx, int64_t* out4);
@@ -326,6 +327,33 @@ int pucfem_dyes_mixing(void* ctx, double* out /* K x 3 */);
    dt, launched once untimed and then `iters` times back to back between two events.  out2[0]: milliseconds per
    launch; out2[1]: algorithmic bytes per launch. */
 int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2);
+/* Dye channels of an ensemble: K = 0 .. PUCFEM_MAX_DYES channels, the same K for every member, beside each member's
+   c.  Every pucfem_ens_step advects a member's channels with that step's final u of that member along the path that
+   moves its c -- the member's dye scheme (pucfem_ens_set_advection) and trajectory (pucfem_ens_set_trajectory) --
+   the departure point and its triangle found once per pass and row for c and all channels.  Channel k of member m
+   holds, bit for bit, channel k of a single-context run with the member's boundary values, settings and starting
+   channels; the member's u, u*, p, p2, c and step records are those of the same ensemble without channels, its
+   pucfem_ens_advection_info / pucfem_ens_trajectory_info counts those of the single run with the same channels (pass
+   2 counts the clamped values of c and the channels).  The step stays a captured graph.
+   pucfem_ens_set_dyes defines K; every member's channels start from buf (K x N, caller numbering; NULL iff K == 0).
+   K = 0 removes the channels and frees their memory: the ensemble then steps as one that never had any, launch for
+   launch.  The call resets the channel step counts and drops the captured graphs.  PUCFEM_ESTATE without an ensemble
+   (decided before the device is asked for) or on a PUCFEM_STOKES_FOOD ensemble; PUCFEM_EINVAL for K outside
+   0 .. PUCFEM_MAX_DYES or a NULL buf with K > 0; PUCFEM_ENODEV on a host-only context.
+   pucfem_ens_set_field / pucfem_ens_get_field take PUCFEM_F_DYES (K * N values per member, channel-major; member = -1:
+   M * K * N, member-major) and PUCFEM_F_DYE0 + k (N values per member).  A count that does not match the ensemble's K,
+   or a channel k >= K, is PUCFEM_EINVAL -- every such call while K = 0 included; pucfem_ens_raster takes
+   PUCFEM_F_DYE0 + k, k < K, as a one-component field, else PUCFEM_EINVAL.  Setting a field never changes K and leaves
+   the channel step counts alone, except PUCFEM_F_DYES, which resets them for the members it sets.  Not done: buoyancy
+   terms on a member's channels, channel values along pucfem_ens_streamlines, a different K per member. */
+int pucfem_ens_set_dyes(void* ctx, int32_t K, const double* buf /* K x N; NULL iff K == 0 */);
+/* out[0] K, [1] channel steps since the member's channels were last set, [2] not-found rows of the member's last dye
+   launch (pass 1's; 0 before the first), [3] device bytes the ensemble holds for channels, all sets */
+int pucfem_ens_dyes_info(void* ctx, int32_t member, int64_t* out4);
+/* (I, mu, var) of every channel of the requested members, out[(m * K + k) * 3 + {0, 1, 2}]: computed at the call by
+   the reduction of pucfem_mixing_index (one launch per stage over every member and channel), so each row holds the
+   bits of pucfem_mixing_index(ctx, that channel read back, ...).  Changes no state.  PUCFEM_ESTATE with K = 0. */
+int pucfem_ens_dyes_mixing(void* ctx, int32_t member /* -1 = all */, double* out /* [members x] K x 3 */);
 
 /* ---- inertia: semi-Lagrangian advection of the velocity in front of the viscous solve ---- */
 /* The reference's step is at Reynolds number zero: its viscous solve takes u + DT * 0 as the right-hand side

@@ -156,6 +156,9 @@ SIGNATURES = {
     "pucfem_ens_advection_info": ([_P, ct.c_int32, _I64], ct.c_int),
     "pucfem_ens_set_trajectory": ([_P, ct.c_int32, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_ens_trajectory_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_ens_set_dyes": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_ens_dyes_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_ens_dyes_mixing": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_apply_bc": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_dye_step": ([_P, _D, _D, _D, _I32], ct.c_int),
     "pucfem_comm_info": ([_P, ct.POINTER(ct.c_int64)], ct.c_int),

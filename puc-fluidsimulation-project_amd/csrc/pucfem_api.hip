@@ -242,6 +242,27 @@ struct Ens {
   std::vector<double> sk_shape_h, sk_dir_h, dval0;
   int stroke_any = 0;                        // members with a stroke
   bool chain_stroke = false;                 // the captured graphs hold the stroke launch
+  // dye channels per member (pucfem_ens_set_dyes; k_ens_dye_fwd / k_ens_dye_bwd / k_ens_dye_copy), the same K for
+  // every member: the current and the next set (M x K x n each, channel k of member m at (m K + k) n), the MacCormack
+  // set's ch of the channels (the same size, allocated by ens_dye_ch_fit when a member's dye scheme is on while K > 0)
+  // and what pucfem_ens_dyes_mixing reduces with (per plane: ENS_VALS values, 2 nb_mix partials, a ticket counter, the
+  // three results).  Not in `allocs`: pucfem_ens_set_dyes frees them when K changes.
+  int dy_K = 0;
+  double *dy_cur = nullptr, *dy_nxt = nullptr, *dy_ch = nullptr;
+  double *dy_mvals = nullptr, *dy_mpart = nullptr, *dy_mout = nullptr;
+  unsigned* dy_mcnt = nullptr;
+  size_t dy_bytes = 0;
+  std::vector<int64_t> dy_steps;             // per member: channel steps since its channels were last set
+  void drop_dyes() {
+    for (void* q : {(void*)dy_cur, (void*)dy_nxt, (void*)dy_ch, (void*)dy_mvals, (void*)dy_mpart, (void*)dy_mout,
+                    (void*)dy_mcnt})
+      if (q) (void)hipFree(q);
+    dy_cur = dy_nxt = dy_ch = dy_mvals = dy_mpart = dy_mout = nullptr;
+    dy_mcnt = nullptr;
+    dy_K = 0;
+    dy_bytes = 0;
+    dy_steps.clear();
+  }
   int nb_tr = 1;             // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
@@ -272,6 +293,7 @@ struct Ens {
   }
   ~Ens() {
     drop_graphs();
+    drop_dyes();
     for (void* a : allocs) (void)hipFree(a);
   }
 };
@@ -6366,6 +6388,57 @@ Ens* ens_of(Ctx& c) {
   if (!c.ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
   return c.ens.get();
 }
+// The dye's launches of a step while the ensemble carries channels (e.dy_K > 0): per dye flag with members on it, the
+// with-channels form of the launches ens_enqueue_step makes without channels -- the same buffers, partials, ticket
+// counters and value slots for c, the channels beside it -- then the channels' next set copied into their current
+// set.  Every member is on exactly one flag, so every plane of the next set is written.  rs: k_ens_sl's reduction.
+void ens_enqueue_dyes(Ctx& c, Ens& e, const RedOut& rs, bool dye_alt) {
+  const i64 n = e.n;
+  const int32_t M = e.M, K = e.dy_K;
+  const size_t sM = (size_t)M;
+  hipStream_t st = c.st;
+  const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+  const dim3 grid(e.nb_sl, M);
+  const double dt = c.prm.dt, hdt = 0.5 * c.prm.dt;
+  const int32_t* on = dye_alt ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr;
+  const double *cc = e.c, *dy = e.dy_cur, *wm = c.dwmix, *nowm = nullptr;
+  hipLaunchKernelGGL(k_ens_dye_fwd<false>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
+                     dt, hdt, on, ENS_DYE_SL, K, cc, dy, e.cn, e.dy_nxt, (int4*)nullptr, wm, e.part_sl, rs);
+  KCHK();
+  if (e.dye_n[ENS_DYE_MC] > 0) {
+    const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
+    hipLaunchKernelGGL(k_ens_dye_fwd<false>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                       (const double*)e.u, dt, hdt, on, ENS_DYE_MC, K, cc, dy, e.mc_ch, e.dy_ch, e.mc_rec, nowm,
+                       e.mc_part, r1);
+    KCHK();
+    const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
+    hipLaunchKernelGGL(k_ens_dye_bwd<false>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
+                       (const double*)e.u, dt, hdt, on, ENS_DYE_MC, K, cc, (const double*)e.mc_ch, dy,
+                       (const double*)e.dy_ch, e.cn, e.dy_nxt, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2,
+                       (double*)nullptr);
+    KCHK();
+  }
+  const RedOut t1{e.vals + 4, e.trj_vals + ENS_TRJ_DYE, e.trj_cnt, 2, 0, 0u};
+  if (e.dye_n[ENS_DYE_SL_MID] > 0) {
+    hipLaunchKernelGGL(k_ens_dye_fwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
+                       dt, hdt, on, ENS_DYE_SL_MID, K, cc, dy, e.cn, e.dy_nxt, (int4*)nullptr, nowm, e.trj_part_d, t1);
+    KCHK();
+  }
+  if (e.dye_n[ENS_DYE_MC_MID] > 0) {
+    hipLaunchKernelGGL(k_ens_dye_fwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
+                       dt, hdt, on, ENS_DYE_MC_MID, K, cc, dy, e.mc_ch, e.dy_ch, e.mc_rec, nowm, e.trj_part_d, t1);
+    KCHK();
+    const RedOut t2{e.trj_vals + ENS_TRJ_DYE + 1, nullptr, e.trj_cnt + sM, 3, 0, 0u};
+    hipLaunchKernelGGL(k_ens_dye_bwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
+                       dt, hdt, on, ENS_DYE_MC_MID, K, cc, (const double*)e.mc_ch, dy, (const double*)e.dy_ch, e.cn,
+                       e.dy_nxt, (const int4*)e.mc_rec, e.trj_part_d + sM * 2 * e.nb_sl, t2, e.vals + 11);
+    KCHK();
+  }
+  const int64_t count = (int64_t)M * K * n;
+  hipLaunchKernelGGL(k_ens_dye_copy, dim3(Ctx::grid_ew(count)), dim3(BS), 0, st, count, (const double*)e.dy_nxt,
+                     e.dy_cur);
+  KCHK();
+}
 // One ensemble step: the dense small-mesh step's launches (Ctx::stokes_step in graph mode), each over every member,
 // in one chain on the context's stream.
 void ens_enqueue_step(Ctx& c) {
@@ -6497,10 +6570,15 @@ void ens_enqueue_step(Ctx& c) {
     const RedOut rs{e.vals + 2, nullptr, e.cnt + M, 3, 0, 0u};
     // (a member whose dye flag is not 0 moves its dye below: by MacCormack, along the midpoint trace, or both)
     const bool dye_alt = e.dye_n[ENS_DYE_MC] + e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0;
-    hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
-                       c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
-                       (const double*)c.dwmix, e.part_sl, rs,
-                       dye_alt ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
+    // with dye channels (pucfem_ens_set_dyes): the with-channels kernels move c and the channels of every member from
+    // one locate per pass and row, in place of the launches below up to the sums
+    if (e.dy_K > 0)
+      ens_enqueue_dyes(c, e, rs, dye_alt);
+    else
+      hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
+                         c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
+                         (const double*)c.dwmix, e.part_sl, rs,
+                         dye_alt ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
     KCHK();
     // with at least one member's dye scheme on: cn = MC(c; u, dt) of those members (which k_ens_sl skipped), pass 1's
     // not-found count into slot 4 and the single path's k_wsum sums into slots 2 and 3 -- Ctx::mc_dye_step /
@@ -6508,7 +6586,7 @@ void ens_enqueue_step(Ctx& c) {
     if (dye_alt) {
       const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
       const size_t sM = (size_t)M;
-      if (e.dye_n[ENS_DYE_MC] > 0) {
+      if (e.dy_K == 0 && e.dye_n[ENS_DYE_MC] > 0) {
         const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
         hipLaunchKernelGGL(k_ens_mc_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
                            (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c, e.mc_ch,
@@ -6523,7 +6601,7 @@ void ens_enqueue_step(Ctx& c) {
       // with at least one member's dye part on: cn along the midpoint trace of those members (flags ENS_DYE_SL_MID /
       // ENS_DYE_MC_MID) -- Ctx::trj_dye_step.  One pass straight into cn; with MacCormack pass 1 into the set's ch and
       // records, pass 2 into cn.  The final locate's count into slot 4, the sums by k_ens_wsum below
-      if (e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0) {
+      if (e.dy_K == 0 && e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0) {
         const double hdt = 0.5 * c.prm.dt;
         const RedOut t1{e.vals + 4, e.trj_vals + ENS_TRJ_DYE, e.trj_cnt, 2, 0, 0u};
         if (e.dye_n[ENS_DYE_SL_MID] > 0) {
@@ -6808,6 +6886,7 @@ void ens_dye_flag_bufs(Ctx& c, Ens& e) {
   e.mc_on_dev = e.alloc<int32_t>(sM, c.st);
   e.mc_cnt = e.alloc<unsigned>(3 * sM, c.st);
 }
+void ens_dye_ch_fit(Ctx& c, Ens& e);  // (with the dye channels' calls below)
 // the members' dye flags as the kernels read them (ENS_DYE_*): the scheme in bit 0, the trajectory part in bit 1
 void ens_dye_upload(Ctx& c, Ens& e) {
   const size_t sM = (size_t)e.M;
@@ -6939,6 +7018,7 @@ int pucfem_ens_set_advection(void* ctx, int32_t member, int32_t what, int32_t sc
     }
     e.mc_bytes += e.bytes - before;
     if (up_dye) ens_dye_upload(c, e);
+    if (up_dye) ens_dye_ch_fit(c, e);  // (with dye channels: the set's ch of the channels)
     if (up_vel) ens_adv_upload(c, e);  // (takes effect while the member's inertia flag is on)
     e.adv_stale = true;
     HIPCHK(hipStreamSynchronize(c.st));
@@ -7152,10 +7232,150 @@ int pucfem_ens_set_buoyancy(void* ctx, int32_t member, const double* g2, double 
   });
 }
 
+// ---- dye channels per member (k_ens_dye_fwd / k_ens_dye_bwd, pucfem_ensemble.hpp)
+namespace {
+// the ensemble of the channel calls: no ensemble is decided before the device is asked for
+Ens* ens_dyes_of(Ctx& c) {
+  c.need_built();
+  if (!c.ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
+  c.need_dev();
+  return c.ens.get();
+}
+bool ens_dye_field(int32_t field) {
+  return field == PUCFEM_F_DYES || (field >= PUCFEM_F_DYE0 && field < PUCFEM_F_DYE0 + DYE_MAX);
+}
+// the MacCormack set's ch of the channels, while K > 0 and a member's dye scheme is on: the ensemble's mc_dye_fit
+void ens_dye_ch_fit(Ctx& c, Ens& e) {
+  if (e.dy_K == 0 || e.mc_dye_any == 0 || e.dy_ch) return;
+  HIPCHK(hipStreamSynchronize(c.st));
+  e.drop_graphs();
+  const size_t b = sizeof(double) * (size_t)e.M * (size_t)e.dy_K * (size_t)e.n;
+  HIPCHK(hipMalloc(reinterpret_cast<void**>(&e.dy_ch), b));
+  HIPCHK(hipMemsetAsync(e.dy_ch, 0, b, c.st));
+  HIPCHK(hipStreamSynchronize(c.st));
+  e.dy_bytes += b;
+}
+// PUCFEM_F_DYES / PUCFEM_F_DYE0 + k of the requested members, to (put) or from the current set
+void ens_dye_io(Ctx& c, Ens& e, int32_t field, int32_t member, const double* src, double* dst, int64_t count) {
+  require(member >= -1 && member < e.M, "member index out of range");
+  const i64 N = c.mesh.N, K = e.dy_K;
+  const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
+  if (field == PUCFEM_F_DYES) {
+    require(K > 0 && count == nm * K * N, "count does not match the ensemble's channels (members x K x N)");
+    require(src != nullptr || dst != nullptr, "null buffer");
+    double* d = e.dy_cur + (size_t)(m0 * K) * (size_t)e.n;
+    if (src) {
+      c.put_all(1, nm * K, src, d);
+      for (i64 m = m0; m < m0 + nm; ++m) e.dy_steps[(size_t)m] = 0;
+    } else {
+      c.get_all(1, nm * K, dst, d);
+    }
+  } else {
+    const i64 k = field - PUCFEM_F_DYE0;
+    require(k < K, "dye channel index >= the ensemble's number of channels");
+    require(count == nm * N, "count does not match the field's shape (members x N)");
+    require(src != nullptr || dst != nullptr, "null buffer");
+    for (i64 m = m0; m < m0 + nm; ++m) {  // (a member's channel k: one plane out of its K)
+      double* d = e.dy_cur + (size_t)(m * K + k) * (size_t)e.n;
+      if (src) c.put_all(1, 1, src + (m - m0) * N, d);
+      else c.get_all(1, 1, dst + (m - m0) * N, d);
+    }
+  }
+  HIPCHK(hipStreamSynchronize(c.st));
+}
+}  // namespace
+
+int pucfem_ens_set_dyes(void* ctx, int32_t K, const double* buf) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_dyes_of(c);
+    if (c.scheme != PUCFEM_STOKES_COLOR)
+      throw Error(PUCFEM_ESTATE, "dye channels need a STOKES_COLOR ensemble: STOKES_FOOD has no dye");
+    require(K >= 0 && K <= DYE_MAX, "K must be in 0 .. PUCFEM_MAX_DYES (16)");
+    require((K == 0) == (buf == nullptr), "buf is K x N; NULL iff K == 0");
+    HIPCHK(hipStreamSynchronize(c.st));
+    e.drop_graphs();
+    const size_t sM = (size_t)e.M, sn = (size_t)e.n;
+    if (K != e.dy_K) {
+      e.drop_dyes();
+      if (K > 0) {
+        const size_t planes = sM * (size_t)K;
+        auto get = [&](auto*& p, size_t count_) {
+          const size_t b = sizeof(*p) * count_;
+          HIPCHK(hipMalloc(reinterpret_cast<void**>(&p), b));
+          HIPCHK(hipMemsetAsync(p, 0, b, c.st));
+          e.dy_bytes += b;
+        };
+        e.dy_K = K;  // (set first: drop_dyes frees whatever was allocated if a later allocation throws)
+        get(e.dy_cur, planes * sn);
+        get(e.dy_nxt, planes * sn);
+        get(e.dy_mvals, planes * ENS_VALS);
+        get(e.dy_mpart, planes * 2 * (size_t)e.nb_mix);
+        get(e.dy_mout, planes * 3);
+        get(e.dy_mcnt, planes);
+      }
+    }
+    e.dy_steps.assign(K > 0 ? sM : 0, 0);
+    if (K > 0) {
+      for (size_t m = 0; m < sM; ++m) c.put_all(1, K, buf, e.dy_cur + m * (size_t)K * sn);
+      ens_dye_ch_fit(c, e);
+    }
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_ens_dyes_info(void* ctx, int32_t member, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_dyes_of(c);
+    require(member >= 0 && member < e.M, "member index out of range");
+    require(out4 != nullptr, "null output");
+    const size_t m = (size_t)member;
+    out4[0] = e.dy_K;
+    out4[1] = e.dy_K > 0 ? e.dy_steps[m] : 0;
+    out4[2] = 0;
+    if (e.dy_K > 0 && e.dy_steps[m] > 0) {  // (the count of the member's last dye launch: pass 1's, slot 4)
+      double v = 0.0;
+      c.d2h(&v, e.vals + ENS_VALS * m + 4, sizeof(double));
+      out4[2] = (int64_t)std::llround(v);
+    }
+    out4[3] = (int64_t)e.dy_bytes;
+  });
+}
+
+int pucfem_ens_dyes_mixing(void* ctx, int32_t member, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    Ens& e = *ens_dyes_of(c);
+    if (e.dy_K == 0) throw Error(PUCFEM_ESTATE, "the ensemble has no dye channels (pucfem_ens_set_dyes)");
+    require(member >= -1 && member < e.M, "member index out of range");
+    require(out != nullptr, "null output");
+    const size_t K = (size_t)e.dy_K, m0 = member < 0 ? 0 : (size_t)member, nm = member < 0 ? (size_t)e.M : 1;
+    const size_t q0 = m0 * K, planes = nm * K;
+    double* vals = e.dy_mvals + q0 * ENS_VALS;
+    // one launch per stage over every requested plane (a grid's y extent holds 65535: 4096 members x 16 channels go
+    // in two halves)
+    constexpr size_t YMAX = 32768;
+    for (int stage = 0; stage < 2; ++stage)
+      for (size_t p0 = 0; p0 < planes; p0 += YMAX) {
+        const size_t q = q0 + p0, np = std::min(YMAX, planes - p0);
+        hipLaunchKernelGGL(k_ens_dyes_mix, dim3(e.nb_mix, (unsigned)np), dim3(BS), 0, c.st, (int64_t)e.n, stage,
+                           (const double*)(e.dy_cur + q * (size_t)e.n), (const double*)c.dwmix,
+                           e.dy_mvals + q * ENS_VALS, e.dy_mpart + q * 2 * (size_t)e.nb_mix, e.dy_mcnt + q);
+        KCHK();
+      }
+    hipLaunchKernelGGL(k_ens_dyes_stats, dim3((unsigned)((planes + 255) / 256)), dim3(256), 0, c.st, (int32_t)planes,
+                       (const double*)vals, e.dy_mout + 3 * q0);
+    KCHK();
+    c.d2h(out, e.dy_mout + 3 * q0, sizeof(double) * 3 * planes);
+  });
+}
+
 int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double* buf, int64_t count) {
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
     Ens& e = *ens_of(c);
+    if (ens_dye_field(field)) return ens_dye_io(c, e, field, member, buf, nullptr, count);
     require(member >= -1 && member < e.M, "member index out of range");
     require(field != PUCFEM_F_CAPTURE_STEP, "capture steps cannot be set");
     require(field != PUCFEM_F_VORTICITY, "the vorticity cannot be set");
@@ -7179,6 +7399,7 @@ int pucfem_ens_get_field(void* ctx, int32_t field, int32_t member, double* buf, 
   return guard(ctx, [&] {
     Ctx& c = *C(ctx);
     Ens& e = *ens_of(c);
+    if (ens_dye_field(field)) return ens_dye_io(c, e, field, member, nullptr, buf, count);
     require(member >= -1 && member < e.M, "member index out of range");
     const EnsField f = ens_field(c, e, field);
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
@@ -7301,6 +7522,7 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     if (e.trj_vals) e.trj_stale = e.adv_stale = true;
     for (size_t m = 0; m < sM && e.force_any > 0; ++m)
       if (e.fmask[m]) e.fsteps[m] += nsteps;
+    for (size_t m = 0; m < sM && e.dy_K > 0; ++m) e.dy_steps[m] += nsteps;
     if (stats)
       for (size_t k = 0; k < (size_t)nsteps * sM; ++k) {
         pucfem_step_stats& o = stats[k];
@@ -7463,6 +7685,12 @@ int pucfem_ens_raster(void* ctx, int32_t nfields, const int32_t* fields, int32_t
     for (int32_t k = 0; k < nfields; ++k) {
       require(fields[k] != PUCFEM_F_TRACERS && fields[k] != PUCFEM_F_STATUS, "tracer fields are not rasterised");
       require(fields[k] != PUCFEM_F_U_ADV, "u_adv is read with pucfem_ens_get_field, not rasterised");
+      if (fields[k] >= PUCFEM_F_DYE0 && fields[k] < PUCFEM_F_DYE0 + DYE_MAX) {  // (the member's plane of channel k)
+        const int ch = fields[k] - PUCFEM_F_DYE0;
+        require(ch < e.dy_K, "dye channel index >= the ensemble's number of channels");
+        sample_push(F, e.dy_cur + (size_t)ch * (size_t)e.n, 1, (i64)e.dy_K * e.n);
+        continue;
+      }
       const EnsField f = ens_field(c, e, fields[k]);
       for (int q = 0; q < f.comp; ++q) sample_push(F, f.a + q, f.comp, f.per);
     }

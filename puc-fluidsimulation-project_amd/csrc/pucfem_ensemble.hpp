@@ -850,6 +850,220 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
   if (red_finish(R, part, sh) && threadIdx.x == 0) stepctr[m] = stepno;
 }
 
+// Dye channels per member (pucfem_ens_set_dyes): the with-channels forms of k_ens_sl,
+// k_ens_mc_fwd / k_ens_mc_bwd<double> and k_ens_trj_fwd / k_ens_trj_bwd<double>, launched in their place while the
+// ensemble carries K > 0 channels.  Their grid, their block-uniform exit for members whose flag is not `want` and their
+// locate sequence (sl_point, sl_locate_wave; MID: ens_trj_locate), so the row's triangle is theirs.  After the locate
+// every lane of the wave holds the triangle: lane 0 takes the member's c and lane k (1..K) channel k - 1, each with the
+// single field's expression (sl_value, the row's own value, mc_row) and one store; lanes above K compute lane 0's value
+// again and store nothing.  Channel k of member m is the plain vector at (m K + k) n of dy (M x K x n).
+//
+// Pass 1 (and the whole of a one-pass step).  c -> cout and dy -> dyout; rec (or null): the row's T1.  Three uses:
+//   wmix != null (the plain SL members, MID = false): k_ens_sl's three values in its grouping -- sum w c of lane 0's
+//     value, sum w, the not-found rows; per wave, thread 0 over the block's waves, red_finish in block order
+//   MID = false, wmix == null (MacCormack pass 1): k_ens_mc_fwd's one value, the rows without T1
+//   MID = true: k_ens_trj_fwd's two, the rows whose final locate found nothing and those without midpoint (ro.out1)
+// on: the members' flags (null: every member's is 0).  part: M x ro.nv gridDim.x.
+template <bool MID>
+__global__ __launch_bounds__(BS) void k_ens_dye_fwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                    const double* __restrict__ u, double dt, double hdt,
+                                                    const int32_t* __restrict__ on, int32_t want, int32_t K,
+                                                    const double* c, const double* dy, double* __restrict__ cout,
+                                                    double* __restrict__ dyout, int4* __restrict__ rec,
+                                                    const double* __restrict__ wmix, double* part, RedOut ro) {
+  __shared__ double sw_[3][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if ((on ? on[m] : 0) != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  RedOut R = ro;
+  R.out = ro.out + (int64_t)ENS_VALS * m;
+  R.out1 = ro.out1 ? ro.out1 + (int64_t)ENS_VALS * m : nullptr;
+  R.cnt = ro.cnt + m;
+  R.stride = (int)gridDim.x;
+  part += (int64_t)m * ro.nv * gridDim.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int fl = lane <= K ? lane : 0;  // this lane's field: 0 the member's c, k the channel k - 1
+  const int64_t fo = fl == 0 ? (int64_t)m * n : ((int64_t)m * K + (fl - 1)) * n;
+  const double* fin = (fl == 0 ? c : dy) + fo;
+  double* fout = (fl == 0 ? cout : dyout) + fo;
+  int4* rm = rec ? rec + (int64_t)m * n : nullptr;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double swc = 0.0, sw = 0.0, nnf = 0.0, nmid = 0.0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double xb, yb;
+    SlTri r{};
+    bool ok;
+    if constexpr (MID) {
+      double wx = v.x, wy = v.y;
+      bool okm;
+      ok = ens_trj_locate(Mh, L, G, i, wx, wy, dt, hdt, um, xb, yb, r, okm);
+      if (!okm) nmid = 1.0;
+    } else {
+      sl_point(Mh, i, v.x, v.y, dt, xb, yb);
+      ok = sl_locate_wave(L, G, xb, yb, r);
+    }
+    if (!ok) nnf = 1.0;
+    const double o = ok ? sl_value(r, xb, yb, fin) : fin[i];
+    if (lane <= K) fout[i] = o;
+    if (lane == 0 && rm) rm[i] = ok ? make_int4(r.a, r.b, r.d, r.id) : make_int4(0, 0, 0, -1);
+    if (wmix) {
+      const double w = wmix[i];
+      sw = w;
+      swc = w * o;  // (read from lane 0 below: the member's c)
+    }
+  }
+  if (lane == 0) {
+    if (wmix) {
+      sw_[0][wv] = swc;
+      sw_[1][wv] = sw;
+      sw_[2][wv] = nnf;
+    } else {
+      sw_[0][wv] = nnf;
+      sw_[1][wv] = nmid;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int v = 0; v < R.nv; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  red_finish(R, part, sh);
+}
+// Pass 2 (MacCormack members), its own launch: the trace with -dt (MID: -dt and -hdt), pass 1's record and mc_row on
+// the lane's (field, ch).  c / ch / cout: M x n, dy / dch / dyout: M x K x n; the outputs alias none of the inputs.
+// The wave's clamp count is the sum of the K + 1 lanes' counts (integers in doubles: the order is free).  Values
+// 0..nv-1 into ro.out: the rows without T2, the clamped values, MID: the rows whose pass-2 midpoint was not found; MID:
+// the block that reduced copies the first two into cnt2 (k_ens_trj_bwd's).  part: M x ro.nv gridDim.x.
+template <bool MID>
+__global__ __launch_bounds__(BS) void k_ens_dye_bwd(MeshDev Mh, LocDev L, GridDev G, int64_t n,
+                                                    const double* __restrict__ u, double dt, double hdt,
+                                                    const int32_t* __restrict__ on, int32_t want, int32_t K,
+                                                    const double* c, const double* ch, const double* dy,
+                                                    const double* dch, double* __restrict__ cout,
+                                                    double* __restrict__ dyout, const int4* __restrict__ rec,
+                                                    double* part, RedOut ro, double* __restrict__ cnt2) {
+  __shared__ double sw_[3][BS / 64];
+  __shared__ double sh[4];
+  const int32_t m = (int32_t)blockIdx.y;
+  if (on[m] != want) return;
+  const dbl2* um = reinterpret_cast<const dbl2*>(u) + (int64_t)m * n;
+  RedOut R = ro;
+  R.out = ro.out + (int64_t)ENS_VALS * m;
+  R.cnt = ro.cnt + m;
+  R.stride = (int)gridDim.x;
+  part += (int64_t)m * ro.nv * gridDim.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int fl = lane <= K ? lane : 0;
+  const int64_t fo = fl == 0 ? (int64_t)m * n : ((int64_t)m * K + (fl - 1)) * n;
+  const double* fin = (fl == 0 ? c : dy) + fo;
+  const double* chin = (fl == 0 ? ch : dch) + fo;
+  double* fout = (fl == 0 ? cout : dyout) + fo;
+  const int4* rm = rec + (int64_t)m * n;
+  const int64_t i = (int64_t)blockIdx.x * (BS / 64) + wv;
+  double nb2 = 0.0, nmid = 0.0, ncl = 0.0;
+  if (i < n) {
+    const dbl2 v = um[i];
+    double xb, yb;
+    SlTri r{};
+    bool ok2;
+    if constexpr (MID) {
+      double wx = v.x, wy = v.y;
+      bool okm;
+      ok2 = ens_trj_locate(Mh, L, G, i, wx, wy, -dt, -hdt, um, xb, yb, r, okm);
+      if (!okm) nmid = 1.0;
+    } else {
+      sl_point(Mh, i, v.x, v.y, -dt, xb, yb);
+      ok2 = sl_locate_wave(L, G, xb, yb, r);
+    }
+    if (!ok2) nb2 = 1.0;
+    int32_t hit = 0;
+    const double o = mc_row(rm[i], ok2, r, xb, yb, i, fin, chin, hit);
+    if (lane <= K) fout[i] = o;
+    ncl = wave_sum(lane <= K ? (double)hit : 0.0);
+  }
+  if (lane == 0) {
+    sw_[0][wv] = nb2;
+    sw_[1][wv] = ncl;
+    sw_[2][wv] = nmid;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int v = 0; v < R.nv; ++v) {
+      double a = 0.0;
+      for (int k = 0; k < BS / 64; ++k) a += sw_[v][k];
+      red_part(R, part, v, a);
+    }
+  }
+  const bool red = red_finish(R, part, sh);
+  if constexpr (MID) {
+    if (red && threadIdx.x == 0) {
+      double* c2 = cnt2 + (int64_t)ENS_VALS * m;
+      c2[0] = R.out[0];
+      c2[1] = R.out[1];
+    }
+  }
+}
+// the channels' next set into their current set behind the advection (a one-step graph holds fixed pointers), as
+// k_ens_mix2 copies cn into c: a streaming copy of count doubles
+__global__ __launch_bounds__(BS) void k_ens_dye_copy(int64_t count, const double* __restrict__ src,
+                                                     double* __restrict__ dst) {
+  for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < count; i += (int64_t)gridDim.x * BS) dst[i] = src[i];
+}
+// pucfem_ens_dyes_mixing: the reduction of pucfem_mixing_index for every (member, channel) plane f (planes x n) in one
+// launch per stage, blockIdx.y the plane, gridDim.x the single reduction's grid (Ctx::nb_rows): k_dot2's block sums
+// (sum w c, and sum w as w * 1) and k_mix2's (sum w (c - mu)^2, mu from the plane's reduced sums), the blocks' partials
+// summed by red_finish in block order -- k_reduce's order over these few blocks.  vals: planes x ENS_VALS, slots 2, 3
+// (stage 0) and 5 (stage 1); part: planes x 2 gridDim.x; cnt: planes.
+__global__ __launch_bounds__(BS) void k_ens_dyes_mix(int64_t n, int stage, const double* __restrict__ f,
+                                                     const double* __restrict__ wmix, double* vals, double* part,
+                                                     unsigned* cnt) {
+  __shared__ double sh[4];
+  const int64_t q = blockIdx.y;
+  const double* c = f + q * n;
+  double* vq = vals + (int64_t)ENS_VALS * q;
+  part += q * 2 * gridDim.x;
+  const RedOut R{vq + (stage == 0 ? 2 : 5), nullptr, cnt + q, stage == 0 ? 2 : 1, (int)gridDim.x, 0u};
+  int64_t r0, r1;
+  block_rows(n, r0, r1);
+  if (stage == 0) {
+    double s1 = 0.0, s2 = 0.0;
+    for (int64_t i = r0 + threadIdx.x; i < r1; i += BS) {
+      s1 += wmix[i] * c[i];
+      s2 += wmix[i] * 1.0;
+    }
+    const double t1 = block_sum(s1, sh), t2 = block_sum(s2, sh);
+    if (threadIdx.x == 0) {
+      red_part(R, part, 0, t1);
+      red_part(R, part, 1, t2);
+    }
+  } else {
+    const double mu = vq[2] / vq[3];
+    double acc = 0.0;
+    for (int64_t i = r0 + threadIdx.x; i < r1; i += BS) {
+      const double d = c[i] - mu;
+      acc += wmix[i] * (d * d);
+    }
+    const double t = block_sum(acc, sh);
+    if (threadIdx.x == 0) red_part(R, part, 0, t);
+  }
+  red_finish(R, part, sh);
+}
+// ... and the planes' (I, mu, var): k_stats' arithmetic (stats_body) on each plane's values; out: planes x 3
+__global__ void k_ens_dyes_stats(int32_t planes, const double* vals, double* out) {
+  const int32_t q = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (q >= planes) return;
+  double r[8];
+  stats_body(vals + (int64_t)ENS_VALS * q, r, 4);
+  out[3 * q] = r[2];
+  out[3 * q + 1] = r[3];
+  out[3 * q + 2] = r[4];
+}
+
 // the step's record of every member (k_stats_ring per member): slot count[m] of the ring (steps x M x 8)
 __global__ void k_ens_record(int32_t M, const double* vals, double* ring, int* count) {
   const int32_t m = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);

@@ -1402,6 +1402,24 @@ def _ensemble_trajectories(scheme, flags, trajectory, dye, velocity, tracers):
     return d, v, t
 
 
+def _ensemble_dyes(dyes, M, N):
+    """The dyes= argument of an ensemble of M members on N nodes as an (M, K, N) float64 array, K = 0 .. 16: (K, N)
+    channels for all members, or (M, K, N) with each member's own; None or an empty array means no channels
+    ((M, 0, N))."""
+    a = np.zeros((0, N)) if dyes is None else np.asarray(dyes, dtype=np.float64)
+    if a.size == 0:
+        return np.zeros((M, 0, N))
+    if a.ndim == 2:
+        if a.shape[1] != N:
+            raise ValueError(f"dyes must have shape (K, {N}) or ({M}, K, {N}): got {a.shape}")
+        a = np.broadcast_to(a, (M,) + a.shape)
+    elif a.ndim != 3 or a.shape[0] != M or a.shape[2] != N:
+        raise ValueError(f"dyes must have shape (K, {N}) or ({M}, K, {N}): got {a.shape}")
+    if a.shape[1] > _lib.MAX_DYES:
+        raise ValueError(f"at most {_lib.MAX_DYES} dye channels: got {a.shape[1]}")
+    return np.ascontiguousarray(a)
+
+
 def ensemble_dirichlet_values(mesh: Mesh, bcs):
     """Dirichlet nodes and per-member values (M, n_dir, 2) of an ensemble: row m is stokes_setup(mesh, bcs[m])'s
     values (the wall values, then the squirmer surface values of makeDirBCU, StokesColor.py:405-427).  Host only."""
@@ -1437,16 +1455,22 @@ class StokesEnsemble:
     member -- a member with a part on moves its c, its u_a (while its inertia is on) or its tracers along midpoint
     traces as StokesSimulation(...) with that part on does, bit for bit (set_trajectory).  trajectory= is
     StokesSimulation's keyword applied per member: the dye on 'color', the tracers on 'food', the velocity of the
-    members whose inertia flag is on; a per-part keyword, where given, wins over it for that part."""
+    members whose inertia flag is on; a per-part keyword, where given, wins over it for that part.
+    dyes (scheme 'color'): (K, N) dye channels for all members or (M, K, N), K = 0 .. 16 -- every member's channels
+    move beside its c along the path of its c, as StokesSimulation.dyes do, bit for bit (dyes, set_dyes, dye_mixing,
+    dyes_info)."""
 
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
                  tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
                  buoyancy=None, dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
-                 velocity_trajectory=None, tracer_trajectory=None, trajectory="euler"):
+                 velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None):
         _ensemble_advection(advection)
         if buoyancy is not None and scheme != "color":
             raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
         self.bcs = _check_ensemble_bcs(bcs)
+        dyes = _ensemble_dyes(dyes, len(self.bcs), mesh.N)
+        if dyes.shape[1] and scheme != "color":
+            raise ValueError("dyes belong to scheme 'color': a 'food' run has no dye")
         _ensemble_strokes(stroke, len(self.bcs))
         if scheme not in ("color", "food"):
             raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -1501,6 +1525,8 @@ class StokesEnsemble:
                 self.set_buoyancy(buoyancy)
             if stroke is not None:
                 self.set_stroke(stroke)
+            if dyes.shape[1]:
+                self.dyes = dyes
         except Exception:
             self.ctx.close()
             raise
@@ -1545,6 +1571,64 @@ class StokesEnsemble:
     @c.setter
     def c(self, v):
         self.set(_lib.F_C, v)
+
+    # ---- dye channels per member (pucfem_ens_set_dyes)
+    def dyes_info(self, member=None):
+        """pucfem_ens_dyes_info per member, with Context.dyes_info's keys: the number of channels, the channel steps
+        since the member's channels were last set, the not-found rows of its last dye launch and the device bytes the
+        ensemble holds for channels -- one member's dict, or (member=None) a dict of (M,) arrays."""
+        def one(m):
+            o = (ct.c_int64 * 4)()
+            self.ctx._c(self.ctx.L.pucfem_ens_dyes_info(self.ctx.h, int(m), o))
+            return dict(channels=int(o[0]), steps=int(o[1]), notfound=int(o[2]), bytes=int(o[3]))
+
+        if member is not None:
+            return one(member)
+        rows = [one(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in ("channels", "steps", "notfound", "bytes")}
+
+    @property
+    def dyes(self):
+        """(M, K, N) every member's dye channels: K extra dye fields per member, the same K for all, advected beside
+        the member's c with every step's final u along the path of its c (its dye scheme and trajectory), the
+        departure point and its triangle found once per pass and row for c and all of them.  Channel k of member m
+        holds the bits of channel k of a StokesSimulation with the member's boundary values, settings and starting
+        channels.  Setting them takes (K, N) for all members or (M, K, N) and resets the channel step counts; an empty
+        array removes them."""
+        K = self.dyes_info(0)["channels"]
+        out = np.zeros((self.M, K, self.mesh.N))
+        if K:
+            self.ctx._c(self.ctx.L.pucfem_ens_get_field(self.ctx.h, _lib.F_DYES, -1, _lib.dptr(out), out.size))
+        return out
+
+    @dyes.setter
+    def dyes(self, v):
+        a = _ensemble_dyes(v, self.M, self.mesh.N)
+        K = a.shape[1]
+        if K == 0:
+            self.ctx._c(self.ctx.L.pucfem_ens_set_dyes(self.ctx.h, 0, None))
+            return
+        # (defines K from member 0's channels; then every member's own where they differ)
+        self.ctx._c(self.ctx.L.pucfem_ens_set_dyes(self.ctx.h, K, _lib.dptr(np.ascontiguousarray(a[0]))))
+        if (a != a[0]).any():
+            self.set(_lib.F_DYES, a)
+
+    def set_dyes(self, a, member):
+        """One member's channels, (K, N) with the ensemble's K (pucfem_ens_set_field, PUCFEM_F_DYES): its channel step
+        count starts again, the other members keep theirs."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.mesh.N:
+            raise ValueError(f"a member's dyes must have shape (K, {self.mesh.N})")
+        self.set(_lib.F_DYES, a, int(member))
+
+    def dye_mixing(self, member=None):
+        """(M, K, 3), or (K, 3) of one member: (I, mu, var) of every dye channel over marker == 0
+        (pucfem_ens_dyes_mixing), row for row StokesSimulation.dye_mixing of the member's single run."""
+        K = self.dyes_info(0)["channels"]
+        out = np.zeros((self.M, K, 3) if member is None else (K, 3))
+        self.ctx._c(self.ctx.L.pucfem_ens_dyes_mixing(self.ctx.h, -1 if member is None else int(member),
+                                                      _lib.dptr(out)))
+        return out
 
     @property
     def vorticity(self):
@@ -1892,7 +1976,8 @@ class StokesEnsemble:
     def raster(self, width, height, fields=("c", "u"), window=None, member=None):
         """Every member's fields as images (pucfem_ens_raster: the swimmers side by side, each pixel located once
         for all members): {name: float32 (M, height, width) or (M, 2, height, width)}; member = m: that member's
-        images without the leading axis.  Fields "u", "u_star", "p", "p2", "c", "vorticity"."""
+        images without the leading axis.  Fields "u", "u_star", "p", "p2", "c", "vorticity" and, with dye channels,
+        "dye0" .. "dye15" (channel k < K of every member)."""
         names, ids, ncomp = _sample_spec(fields)
         w, wp = _window(window)
         nm = self.M if member is None else 1
@@ -1944,7 +2029,7 @@ class StokesEnsemble:
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
                    inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
                    dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
-                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler"):
+                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
     'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
@@ -1953,7 +2038,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
     member (StokesEnsemble.set_force / set_buoyancy).  stroke: a Stroke for all members or a list with one Stroke or
     None per member (StokesEnsemble.set_stroke).  dye_trajectory, velocity_trajectory, tracer_trajectory: 'euler' or
     'midpoint', one name for all members or one per member; trajectory: StokesSimulation's keyword per member
-    (StokesEnsemble.set_trajectory)."""
+    (StokesEnsemble.set_trajectory).  dyes (scheme 'color'): (K, N) dye channels for all members or (M, K, N)
+    (StokesEnsemble.dyes); each member's Result.dyes holds its channels after the last step."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -1962,10 +2048,11 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
                          tracer_seed=tracer_seed, force=force, buoyancy=buoyancy, dye_advection=dye_advection,
                          velocity_advection=velocity_advection, stroke=stroke, dye_trajectory=dye_trajectory,
                          velocity_trajectory=velocity_trajectory, tracer_trajectory=tracer_trajectory,
-                         trajectory=trajectory)
+                         trajectory=trajectory, dyes=dyes)
     try:
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
+        dy = ens.dyes if dyes is not None else None
         c = ens.c if scheme == "color" else None
         tr, ts, cs = (ens.tracers, ens.tracer_status, ens.capture_step) if scheme == "food" else (None, None, None)
     finally:
@@ -1975,6 +2062,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
         r = Result(scheme, steps, u=u[m], p=p[m], stats=[s[m] for s in st])
         if scheme == "color":
             r.c = c[m]
+            if dy is not None:
+                r.dyes = dy[m]
         else:
             r.tracers, r.tracer_status, r.capture_step = tr[m], ts[m], cs[m]
         res.append(r)
