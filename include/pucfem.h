@@ -782,6 +782,53 @@ int pucfem_ens_streamlines(void* ctx, int32_t member /* -1 = all, member-major *
    Stokes contexts after pucfem_build_operators, else PUCFEM_ESTATE; PUCFEM_ENODEV on a host-only context. */
 int pucfem_flow_info(void* ctx, int32_t member, double* out4);
 
+/* ---- swimmer loads: force, torque, power and dissipation on the device ---- */
+/* What the fluid does to the swimmer and what the swimmer spends, reduced on the device in one launch (k_loads,
+   pucfem_loads.hpp) from the current u and the two projection pressures of the last step, P = p + p2 (zeros before any
+   step).  The swimmer surface is the closed polygon of mesh edges whose two end nodes carry marker 2 and which lie in
+   exactly one triangle, listed in ascending (triangle, local edge k) order; local edge k runs from vertex k to vertex
+   (k + 1) mod 3 of its triangle and o is the third vertex.  Per edge (i, j) of triangle t, every product and sum as
+   written (pucfem_loads.hpp spells out the order; tests/loads_reference.py restates it in numpy, bit for bit):
+     e = X_j - X_i,  n = (e_y, -e_x), negated if n . (X_o - X_i) < 0   (length-weighted, from the body into the fluid)
+     G = the constant P1 gradient of u on t (G_ab = d u_a / d x_b, formed with inv = 1 / det)
+     f_p = -((P_i + P_j) / 2) n            f_v = nu (G + G^T) n              (force ON the swimmer, per unit density)
+     torque = r x f  with r = (X_i + X_j) / 2 - center      power = -((u_i + u_j) / 2) . f   (delivered TO the fluid)
+   and per triangle with |det| >= 1e-14 the dissipation nu A_t (2 G_xx^2 + 2 G_yy^2 + (G_xy + G_yx)^2).  The ten
+   reduced values, in this order:
+     [0] [1] pressure force x, y   [2] [3] viscous force x, y   [4] pressure torque   [5] viscous torque
+     [6] pressure power            [7] viscous power            [8] dissipation        [9] perimeter (sum |e|)
+   The sums are taken in a fixed order (a thread its items, the block, the blocks in order): two calls without a step
+   in between return identical bits, and an ensemble member's values are those of a single run with its fields.
+   member = -1: the context's own run; otherwise that member of its ensemble.  Changes no state: no field, no step
+   buffer, no kernel-class counter.
+   PUCFEM_ESTATE, decided before the device is asked for: before pucfem_build_operators, a heat or Poisson context, a
+   multi-rank context, member >= 0 without an ensemble.  PUCFEM_ENODEV on a host-only context (every call below but
+   pucfem_host_surface_edges).  PUCFEM_EINVAL: member < -1 or >= members, a negative capacity, rows out of range. */
+int pucfem_swimmer_loads(void* ctx, int32_t member, double* out10);
+/* The eight per-edge values [0] .. [7] of the list above, E x 8 in the surface list's order: the pressure and shear
+   distribution around the body. */
+int pucfem_surface_traction(void* ctx, int32_t member, double* out /* E x 8 */);
+/* Unit operation on caller-supplied fields: u (N,2) and P = p (N) in the caller's numbering, p2 = 0, with the
+   context's nu and centre; edges (E x 8) may be NULL.  The step's state is not touched. */
+int pucfem_loads_apply(void* ctx, const double* u, const double* p, double* out10, double* edges /* E x 8 or NULL */);
+/* The record: with capacity > 0 every pucfem_step, and every member's pucfem_ens_step, appends one row of 11 doubles
+   -- the rows recorded since this call counting this one (1, 2, ...), then the ten values -- from the step's final u,
+   p and p2, into a device ring of `capacity` rows (per member for an ensemble).  The row's index is a count in device
+   memory taken modulo the capacity, advanced by the launch's reducing block.  capacity = 0 switches it off; every
+   call frees the ring and starts again from zero rows.  The ensemble's step stays a captured graph (captured again
+   when the capacity changes); a small-mesh single context steps uncaptured while recording, as a forced one does.
+   Off is the default, and with the record off a step is launch for launch what it was.
+   pucfem_build_operators clears it. */
+int pucfem_set_loads_record(void* ctx, int32_t capacity);
+/* Rows first .. first + count - 1 of the rows held (the last min(recorded, capacity), oldest first), count x 11. */
+int pucfem_loads_record(void* ctx, int32_t member, int64_t first, int64_t count, double* out);
+/* out[0] surface edges, [1] triangles visited, [2] rows recorded since the record was set, [3] capacity (0: off). */
+int pucfem_loads_info(void* ctx, int32_t member, int64_t* out4);
+/* Measurement: the context's launch once untimed and then `iters` times back to back between two events.  out2[0]:
+   milliseconds per launch; out2[1]: algorithmic bytes per launch (12 per triangle for its ids, 32 per node for its
+   coordinates and velocity, each counted once, and 40 per edge for its record and four pressures). */
+int pucfem_loads_probe(void* ctx, int32_t iters, double* out2);
+
 /* ---- unit operations (reference-named shims and parity tests) --------------------- */
 int pucfem_apply(void* ctx, int32_t op, const double* x, double* y);
 /* op VISC: b,x are (N,2) (both velocity components, StokesColor.py:544-545);
@@ -986,6 +1033,11 @@ int pucfem_host_lattice_apply(void* ctx, int32_t level, int32_t kind, const doub
 int pucfem_host_partition(void* ctx, int32_t rank, int32_t world, int64_t* n_own, int64_t* n_ghost,
                           int64_t* owned, int64_t* ghosts, int32_t* ghost_owner,
                           int64_t* n_send, int64_t* send_ids, int32_t* send_peer);
+
+/* The swimmer surface's edge list (see "swimmer loads"): n edges, per edge its triangle, its end nodes a -> b (the
+   triangle's local edge) and the opposite node, caller numbering, in ascending (triangle, local edge) order.  Every
+   array NULL to get n.  Works on a host-only context once a mesh is uploaded. */
+int pucfem_host_surface_edges(void* ctx, int64_t* n, int32_t* tri, int32_t* a, int32_t* b, int32_t* opp);
 
 #ifdef __cplusplus
 }

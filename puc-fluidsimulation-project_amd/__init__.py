@@ -14,8 +14,9 @@ from .mesh import (Mesh, boundary_sets, filter_wall_pairs, find_boundary_pairs, 
 from .ops import (advect_maccormack, advect_maccormack_vector, advect_semilagrange, advect_semilagrange_multi, advect_semilagrange_vector, apply_body_force, buildLumpedMassMatrix,  # noqa: F401
                   buildStiffnessMatrix, calculate_divergence, build_mass_and_convection_mass, calculate_gradiant,
                   calculate_vorticity, dye_implicit_step,
-                  makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous)
-from .solver import (SAMPLE_FIELDS, Buoyancy, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
+                  makeDirBCU, makePerBCU, mixing_index, set_globals, solve_pressure, solve_viscous, surface_edges,
+                  swimmer_loads)
+from .solver import (LOADS_KEYS, SAMPLE_FIELDS, Buoyancy, Context, HeatSimulation, Result, SquirmerBC, StokesEnsemble,  # noqa: F401
                      StokesSimulation, Streamlines, Stroke, Tolerances, dye_patterns, ensemble_dirichlet_values,
                      pixel_centres, poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments,
                      stroke_geometry)

@@ -13,7 +13,7 @@ DEPS = SRC + ["csrc/pucfem_host.hpp", "csrc/pucfem_kernels.hpp", "csrc/pucfem_ke
               "csrc/pucfem_sample.hpp", "csrc/pucfem_streamline.hpp",
               "csrc/pucfem_dye_channels.hpp", "csrc/pucfem_inertia.hpp", "csrc/pucfem_force.hpp",
               "csrc/pucfem_maccormack.hpp", "csrc/pucfem_brownian.hpp", "csrc/pucfem_stroke.hpp",
-              "csrc/pucfem_trajectory.hpp"]
+              "csrc/pucfem_trajectory.hpp", "csrc/pucfem_loads.hpp"]
 
 
 def hipcc():

@@ -27,6 +27,9 @@ F_U_RHS = 16  # r (N, 2) of the last forced step, read only
 FORCE_UNIFORM, FORCE_NODAL, FORCE_BUOYANCY = 1, 2, 4  # pucfem_force_info: the terms present (a mask)
 MAX_DYES = 16
 STROKE_MAX_MODES, STROKE_MAX_PERIOD = 8, 65536  # pucfem_set_stroke: K and P at the most
+# pucfem_swimmer_loads: the ten reduced values, in order; the first eight are also pucfem_surface_traction's columns
+LOADS_KEYS = ("force_pressure_x", "force_pressure_y", "force_viscous_x", "force_viscous_y", "torque_pressure",
+              "torque_viscous", "power_pressure", "power_viscous", "dissipation", "perimeter")
 ADV_DYE, ADV_VELOCITY = 1, 2  # pucfem_set_advection: what (a mask)
 ADV_SL, ADV_MACCORMACK = 0, 1  # ... and the scheme
 MC_NO_BACK, MC_NO_FWD = 1, 2  # marks of pucfem_sl_advect_mc
@@ -187,6 +190,14 @@ SIGNATURES = {
     "pucfem_host_get_csr": ([_P, ct.c_int32, _I64, _I64, _I64, _I64, _D], ct.c_int),
     "pucfem_host_lattice_apply": ([_P, ct.c_int32, ct.c_int32, _D, _D], ct.c_int),
     "pucfem_host_partition": ([_P, ct.c_int32, ct.c_int32, _I64, _I64, _I64, _I64, _I32, _I64, _I64, _I32], ct.c_int),
+    "pucfem_host_surface_edges": ([_P, _I64, _I32, _I32, _I32, _I32], ct.c_int),
+    "pucfem_swimmer_loads": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_surface_traction": ([_P, ct.c_int32, _D], ct.c_int),
+    "pucfem_loads_apply": ([_P, _D, _D, _D, _D], ct.c_int),
+    "pucfem_set_loads_record": ([_P, ct.c_int32], ct.c_int),
+    "pucfem_loads_record": ([_P, ct.c_int32, ct.c_int64, ct.c_int64, _D], ct.c_int),
+    "pucfem_loads_info": ([_P, ct.c_int32, _I64], ct.c_int),
+    "pucfem_loads_probe": ([_P, ct.c_int32, _D], ct.c_int),
 }
 
 _lib = None

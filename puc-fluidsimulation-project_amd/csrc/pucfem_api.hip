@@ -35,6 +35,7 @@
 #include "pucfem_maccormack.hpp"
 #include "pucfem_trajectory.hpp"
 #include "pucfem_stroke.hpp"
+#include "pucfem_loads.hpp"
 
 using namespace pucfem;
 using namespace pucfem::dev;
@@ -247,6 +248,21 @@ struct Ens {
   // set's ch of the channels (the same size, allocated by ens_dye_ch_fit when a member's dye scheme is on while K > 0)
   // and what pucfem_ens_dyes_mixing reduces with (per plane: ENS_VALS values, 2 nb_mix partials, a ticket counter, the
   // three results).  Not in `allocs`: pucfem_ens_set_dyes frees them when K changes.
+  // swimmer loads per member (pucfem_swimmer_loads, pucfem_set_loads_record; k_loads with the member in blockIdx.y),
+  // allocated at first use and kept: the launch's partials (M x LOADS_NV grid), the reduced values (M x ENS_VALS), the
+  // per-edge values (M x E x LOADS_EV) and ticket counters (M).  The record's ring (M x cap rows) and row counts (M)
+  // are not in `allocs`: a changed capacity frees them.  ld_cap: the capacity the ring was made for (the context's).
+  double *ld_part = nullptr, *ld_out = nullptr, *ld_eout = nullptr, *ld_ring = nullptr;
+  unsigned* ld_cnt = nullptr;
+  int64_t* ld_count = nullptr;
+  int32_t ld_cap = 0;
+  void drop_loads_ring() {
+    for (void* q : {(void*)ld_ring, (void*)ld_count})
+      if (q) (void)hipFree(q);
+    ld_ring = nullptr;
+    ld_count = nullptr;
+    ld_cap = 0;
+  }
   int dy_K = 0;
   double *dy_cur = nullptr, *dy_nxt = nullptr, *dy_ch = nullptr;
   double *dy_mvals = nullptr, *dy_mpart = nullptr, *dy_mout = nullptr;
@@ -294,6 +310,7 @@ struct Ens {
   ~Ens() {
     drop_graphs();
     drop_dyes();
+    drop_loads_ring();
     for (void* a : allocs) (void)hipFree(a);
   }
 };
@@ -700,7 +717,8 @@ struct Ctx {
   // it, the probe's counter
   // Slot 23: pucfem_sl_advect_traj / pucfem_sl_advect_vel_traj / pucfem_trajectory_probe (pucfem_trajectory.hpp): the
   // blocks' midpoint counts of the two passes (they share slots 14..21 with the operations above)
-  static constexpr int SMP_SLOTS = 24;
+  // Slot 24: pucfem_loads_apply (pucfem_loads.hpp): the caller's p and, behind it, a plane of zeros for p2
+  static constexpr int SMP_SLOTS = 25;
   void* smp_buf[SMP_SLOTS] = {};
   size_t smp_cap[SMP_SLOTS] = {};
   template <class T>
@@ -934,6 +952,7 @@ struct Ctx {
       drop_stroke(false);
       drop_advection();
       drop_trajectory();
+      drop_loads();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
       if (h_ctl) (void)hipHostFree(h_ctl);
@@ -1517,6 +1536,118 @@ struct Ctx {
   size_t force_dev_bytes() const {
     const size_t plane = sizeof(double) * 2 * (size_t)std::max<i64>(1, lp.n_own);
     return (u_rhs ? plane : 0) + (f_nodal ? plane : 0);
+  }
+
+  // ------------------------------------------------------------------ swimmer loads (pucfem_loads.hpp)
+  // The surface edge list (host, caller numbering: surf) and its device image, (triangle, local edge) pairs: mtri keeps
+  // the caller's triangle order and vertex order, so the pairs need no renumbering.  Everything here is allocated at
+  // a call's first need and freed by drop_loads (not in `allocs`): a context that never asks holds no new memory, and
+  // with the record off (ld_cap == 0) a step launches nothing new.
+  SurfaceEdges surf;
+  bool surf_valid = false;
+  int2* ld_edge = nullptr;
+  int32_t ld_nE = 0;
+  double *ld_part = nullptr, *ld_out = nullptr, *ld_eout = nullptr, *ld_ring = nullptr;
+  unsigned* ld_cnt = nullptr;
+  int64_t* ld_count = nullptr;
+  int32_t ld_cap = 0;  // record capacity (0: off), the context's and its ensemble's
+  const SurfaceEdges& surface() {
+    if (!has_mesh) throw Error(PUCFEM_ESTATE, "no mesh has been uploaded");
+    if (!surf_valid) {
+      surface_edges(mesh, surf);
+      surf_valid = true;
+    }
+    return surf;
+  }
+  // a built single-rank Stokes context; member >= 0 needs its ensemble (all checked before the device is asked for)
+  void loads_ready(int32_t member) const {
+    need_built();
+    if (scheme != PUCFEM_STOKES_COLOR && scheme != PUCFEM_STOKES_FOOD)
+      throw Error(PUCFEM_ESTATE, "swimmer loads need a Stokes context");
+    if (dist() || world != 1) throw Error(PUCFEM_ESTATE, "swimmer loads are single-rank");
+    if (member >= 0 && !ens) throw Error(PUCFEM_ESTATE, "no ensemble on this context: call pucfem_ens_create first");
+    need_dev();
+  }
+  int loads_nbe() const { return std::max(1, (ld_nE + BS - 1) / BS); }
+  int loads_nbt() const { return (int)std::max<i64>(1, std::min<i64>(LOADS_TRI_MAXB, (mesh.T + BS - 1) / BS)); }
+  int loads_grid() const { return loads_nbe() + loads_nbt(); }
+  template <class T>
+  T* loads_alloc(size_t count) {
+    void* q = nullptr;
+    const size_t b = sizeof(T) * std::max<size_t>(1, count);
+    HIPCHK(hipMalloc(&q, b));
+    HIPCHK(hipMemsetAsync(q, 0, b, st));
+    return (T*)q;
+  }
+  void loads_bufs() {
+    if (ld_edge) return;
+    const SurfaceEdges& S = surface();
+    std::vector<int2> h((size_t)S.size());
+    for (i64 e = 0; e < S.size(); ++e) {
+      const i32 t = S.tri[e];
+      const int k = mesh.tri[3 * (i64)t] == S.a[e] ? 0 : mesh.tri[3 * (i64)t + 1] == S.a[e] ? 1 : 2;
+      h[e] = int2{t, k};
+    }
+    ld_nE = (int32_t)S.size();
+    ld_edge = loads_alloc<int2>(h.size());
+    if (!h.empty()) h2d(ld_edge, h.data(), sizeof(int2) * h.size());
+    ld_part = loads_alloc<double>((size_t)LOADS_NV * loads_grid());
+    ld_out = loads_alloc<double>(ENS_VALS);
+    ld_eout = loads_alloc<double>((size_t)LOADS_EV * ld_nE);
+    ld_cnt = loads_alloc<unsigned>(1);
+  }
+  // algorithmic bytes of a launch that stores no per-edge values: the triangles' ids once, every node's coordinates
+  // and velocity once (each vector counted once per row, as everywhere), an edge's record and four pressures
+  double loads_launch_bytes() const {
+    return 12.0 * (double)mesh.T + 32.0 * (double)mesh.N + (8.0 + 32.0) * (double)ld_nE;
+  }
+  // k_loads on the current stream over nm members (1: a single context's fields, or one member's planes); eout null:
+  // no per-edge values stored
+  void loads_launch(int32_t nm, const double* u, i64 ustride, const double* pa, const double* pb, i64 pstride,
+                    const int32_t* mo, double* eout, double* part, const RedOut& r, const LoadsRec& rec) {
+    hipLaunchKernelGGL(k_loads, dim3(loads_grid(), nm), dim3(BS), 0, st, MeshDev{mx, my, mtri, mesh.T},
+                       (const int2*)ld_edge, ld_nE, (int32_t)loads_nbe(), u, (int64_t)ustride, pa, pb, (int64_t)pstride,
+                       mo, prm.nu, prm.center_x, prm.center_y, eout, (int64_t)LOADS_EV * ld_nE, part, r, rec);
+    KCHK();
+  }
+  // the context's own u and the last step's pressures (kept in the solves' y on the p_from_y path, where a periodic
+  // slave's value is its master's)
+  void loads_own(double* eout, const LoadsRec& rec) {
+    loads_bufs();
+    const RedOut r{ld_out, nullptr, ld_cnt, LOADS_NV, 0, 0u};
+    loads_launch(1, ux, 0, p_from_y ? yp : p, p_from_y ? yp2 : p2, 0, p_from_y ? dmaster_of : nullptr, eout, ld_part,
+                 r, rec);
+  }
+  // the record's part of a step, behind the step's final u and p2 on the main stream
+  void loads_step() {
+    if (ld_cap > 0) loads_own(nullptr, LoadsRec{ld_ring, ld_count, ld_cap});
+  }
+  void loads_record_set(int32_t cap) {
+    if (st) HIPCHK(hipStreamSynchronize(st));
+    for (void* q : {(void*)ld_ring, (void*)ld_count})
+      if (q) (void)hipFree(q);
+    ld_ring = nullptr;
+    ld_count = nullptr;
+    ld_cap = cap;
+    if (cap > 0) {
+      loads_bufs();
+      ld_ring = loads_alloc<double>((size_t)cap * LOADS_ROW);
+      ld_count = loads_alloc<int64_t>(1);
+    }
+  }
+  void drop_loads() {
+    surf_valid = false;
+    ld_cap = 0;
+    ld_nE = 0;
+    if (!ld_edge && !ld_ring) return;
+    if (st) (void)hipStreamSynchronize(st);
+    for (void* q : {(void*)ld_edge, (void*)ld_part, (void*)ld_out, (void*)ld_eout, (void*)ld_ring, (void*)ld_cnt,
+                    (void*)ld_count})
+      if (q) (void)hipFree(q);
+    ld_edge = nullptr;
+    ld_part = ld_out = ld_eout = ld_ring = nullptr;
+    ld_cnt = nullptr;
+    ld_count = nullptr;
   }
 
   // ------------------------------------------------------------------ time-dependent strokes (pucfem_stroke.hpp)
@@ -3953,6 +4084,7 @@ struct Ctx {
       }
       KCHK();
     }
+    loads_step();  // (the record's row, from the step's final u and pressures: nothing unless the record is on)
     its[0] = itv;
     its[1] = itp;
     its[2] = itp2;
@@ -5973,6 +6105,7 @@ int pucfem_mesh_upload(void* ctx, int64_t N, const double* xy, const int32_t* mk
     m.fp32 = coord_fp32 != 0;
     c.has_mesh = true;
     c.built = false;
+    c.surf_valid = false;
   });
 }
 
@@ -6052,6 +6185,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     if (!c.host_only) c.drop_stroke(false);
     if (!c.host_only) c.drop_advection();
     if (!c.host_only) c.drop_trajectory();
+    if (!c.host_only) c.drop_loads();
     build(c);
   });
 }
@@ -6235,9 +6369,10 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       // whose dye moves by MacCormack steps, and one with a body force: the same launches behind k_force_rhs, whose
       // by-value terms and dye pointers change between steps; and one with a stroke: the same launches behind
       // k_stroke_bc, so that the captured graphs stay the unstroked step's, launch for launch; and one with a
-      // midpoint trajectory on: the captured graphs hold the Euler launches)
+      // midpoint trajectory on: the captured graphs hold the Euler launches; and one whose loads record is on: the same
+      // launches in front of k_loads, so that the captured graphs stay the unrecorded step's)
       if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced() &&
-          !c.stroked() && !c.trj_any()) {
+          !c.stroked() && !c.trj_any() && c.ld_cap == 0) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -6438,6 +6573,42 @@ void ens_enqueue_dyes(Ctx& c, Ens& e, const RedOut& rs, bool dye_alt) {
   hipLaunchKernelGGL(k_ens_dye_copy, dim3(Ctx::grid_ew(count)), dim3(BS), 0, st, count, (const double*)e.dy_nxt,
                      e.dy_cur);
   KCHK();
+}
+// the ensemble's loads buffers, allocated at first use and kept
+void ens_loads_bufs(Ctx& c, Ens& e) {
+  c.loads_bufs();
+  if (e.ld_part) return;
+  const size_t sM = (size_t)e.M;
+  e.ld_part = e.alloc<double>(sM * LOADS_NV * c.loads_grid(), c.st);
+  e.ld_out = e.alloc<double>(sM * ENS_VALS, c.st);
+  e.ld_eout = e.alloc<double>(sM * LOADS_EV * (size_t)c.ld_nE, c.st);
+  e.ld_cnt = e.alloc<unsigned>(sM, c.st);
+}
+// k_loads over members m0 .. m0 + nm - 1 of their current u, p and p2: the values into the members' e.ld_out, with
+// `store` the per-edge values into their e.ld_eout; rec: the record (its ring and counts are the whole ensemble's, so
+// only with m0 = 0)
+void ens_loads(Ctx& c, Ens& e, int32_t m0, int32_t nm, bool store, const LoadsRec& rec) {
+  ens_loads_bufs(c, e);
+  const size_t m = (size_t)m0;
+  const RedOut r{e.ld_out + m * ENS_VALS, nullptr, e.ld_cnt + m, LOADS_NV, 0, 0u};
+  c.loads_launch(nm, e.u + m * 2 * e.n, 2 * e.n, e.p + m * e.n, e.p2 + m * e.n, e.n, nullptr,
+                 store ? e.ld_eout + m * LOADS_EV * (size_t)c.ld_nE : nullptr,
+                 e.ld_part + m * LOADS_NV * (size_t)c.loads_grid(), r, rec);
+}
+// the record's ring of the ensemble follows the context's setting (pucfem_set_loads_record may come before or after
+// pucfem_ens_create): a changed capacity makes a fresh ring, zero rows recorded
+void ens_loads_ring_fit(Ctx& c, Ens& e, bool reset) {
+  if (e.ld_cap == c.ld_cap && !reset) return;
+  HIPCHK(hipStreamSynchronize(c.st));
+  e.drop_graphs();  // (the ring's address and capacity are arguments of the captured launch)
+  e.drop_loads_ring();
+  if (c.ld_cap > 0) {
+    ens_loads_bufs(c, e);
+    e.ld_ring = c.loads_alloc<double>((size_t)e.M * c.ld_cap * LOADS_ROW);
+    e.ld_count = c.loads_alloc<int64_t>((size_t)e.M);
+    e.ld_cap = c.ld_cap;
+    HIPCHK(hipStreamSynchronize(c.st));
+  }
 }
 // One ensemble step: the dense small-mesh step's launches (Ctx::stokes_step in graph mode), each over every member,
 // in one chain on the context's stream.
@@ -6673,6 +6844,9 @@ void ens_enqueue_step(Ctx& c) {
   }
   hipLaunchKernelGGL(k_ens_record, dim3((M + 255) / 256), dim3(256), 0, st, M, (const double*)e.vals, e.ring, e.count);
   KCHK();
+  // with the loads record on: every member's row from its final u and pressures, one launch (Ctx::loads_step); the
+  // rows' indices come from the members' counts in device memory
+  if (e.ld_cap > 0) ens_loads(c, e, 0, M, false, LoadsRec{e.ld_ring, e.ld_count, e.ld_cap});
 }
 // the ensemble's vorticity buffers, allocated at first use and kept
 void ens_flow_bufs(Ctx& c, Ens& e) {
@@ -7479,6 +7653,8 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       e.chain_mcv = e.vel_n[ENS_ADV_MC] > 0;
       e.chain_trj = e.trj_chain();
     }
+    // (and for the loads record: k_loads behind the chain iff the record is on; a changed capacity drops the graphs)
+    ens_loads_ring_fit(c, e, false);
     if (!e.gexec) capture(1, e.graph, e.gexec);
     if (!e.gexec_k && c.gk > 1 && nsteps >= c.gk) capture(c.gk, e.graph_k, e.gexec_k);
     std::vector<double> h(stats ? 8 * sM * (size_t)nsteps : 0);
@@ -7962,6 +8138,157 @@ int pucfem_flow_info(void* ctx, int32_t member, double* out4) {
     out4[1] = 0.5 * h[1];
     out4[2] = 0.5 * h[2];
     out4[3] = std::sqrt(h[3]);
+  });
+}
+
+// ---- swimmer loads (pucfem_loads.hpp)
+int pucfem_host_surface_edges(void* ctx, int64_t* n, int32_t* tri, int32_t* a, int32_t* b, int32_t* opp) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(n != nullptr, "null count");
+    const SurfaceEdges& S = c.surface();
+    *n = S.size();
+    if (!tri && !a && !b && !opp) return;
+    require(tri && a && b && opp, "either every array or none");
+    std::copy(S.tri.begin(), S.tri.end(), tri);
+    std::copy(S.a.begin(), S.a.end(), a);
+    std::copy(S.b.begin(), S.b.end(), b);
+    std::copy(S.opp.begin(), S.opp.end(), opp);
+  });
+}
+
+namespace {
+// the values (and with eout the per-edge values) of the context (member -1) or a member, into host arrays
+void loads_read(Ctx& c, int32_t member, double* out10, double* eout) {
+  if (member < 0) {
+    c.loads_bufs();  // (ld_eout exists before it is named)
+    c.loads_own(eout ? c.ld_eout : nullptr, LoadsRec{nullptr, nullptr, 0});
+    c.d2h(out10, c.ld_out, sizeof(double) * LOADS_NV);
+    if (eout) c.d2h(eout, c.ld_eout, sizeof(double) * LOADS_EV * (size_t)c.ld_nE);
+    return;
+  }
+  Ens& e = *ens_of(c);
+  require(member < e.M, "member index out of range");
+  ens_loads(c, e, member, 1, eout != nullptr, LoadsRec{nullptr, nullptr, 0});
+  c.d2h(out10, e.ld_out + (size_t)member * ENS_VALS, sizeof(double) * LOADS_NV);
+  if (eout)
+    c.d2h(eout, e.ld_eout + (size_t)member * LOADS_EV * (size_t)c.ld_nE, sizeof(double) * LOADS_EV * (size_t)c.ld_nE);
+}
+}  // namespace
+
+int pucfem_swimmer_loads(void* ctx, int32_t member, double* out10) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out10 != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.loads_ready(member);
+    loads_read(c, member, out10, nullptr);
+  });
+}
+
+int pucfem_surface_traction(void* ctx, int32_t member, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.loads_ready(member);
+    double v[LOADS_NV];
+    loads_read(c, member, v, out);
+  });
+}
+
+int pucfem_loads_apply(void* ctx, const double* u, const double* p, double* out10, double* edges) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(u != nullptr && p != nullptr && out10 != nullptr, "null fields or output");
+    c.loads_ready(-1);
+    c.loads_bufs();
+    const i64 N = c.mesh.N;
+    // the caller's u as the step stores it and its p beside a plane of zeros (p2), in scratch: no field is touched
+    double* tu = c.u_scratch();
+    double* tp = c.smp_scratch<double>(24, 2 * (size_t)N);
+    c.put_all(2, 1, u, tu);
+    c.put_all(1, 1, p, tp);
+    HIPCHK(hipMemsetAsync(tp + N, 0, sizeof(double) * (size_t)N, c.st));
+    const RedOut r{c.ld_out, nullptr, c.ld_cnt, LOADS_NV, 0, 0u};
+    c.loads_launch(1, tu, 0, tp, tp + N, 0, nullptr, edges ? c.ld_eout : nullptr, c.ld_part, r,
+                   LoadsRec{nullptr, nullptr, 0});
+    c.d2h(out10, c.ld_out, sizeof(double) * LOADS_NV);
+    if (edges) c.d2h(edges, c.ld_eout, sizeof(double) * LOADS_EV * (size_t)c.ld_nE);
+  });
+}
+
+int pucfem_set_loads_record(void* ctx, int32_t capacity) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(capacity >= 0, "capacity < 0");
+    c.loads_ready(-1);
+    c.loads_record_set(capacity);
+    if (c.ens) ens_loads_ring_fit(c, *c.ens, true);
+  });
+}
+
+int pucfem_loads_record(void* ctx, int32_t member, int64_t first, int64_t count, double* out) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(member >= -1, "member index out of range");
+    require(first >= 0 && count >= 0, "first or count < 0");
+    c.loads_ready(member);
+    const double* ring = c.ld_ring;
+    const int64_t* cnt = c.ld_count;
+    i64 cap = c.ld_cap;
+    if (member >= 0) {
+      Ens& e = *ens_of(c);
+      require(member < e.M, "member index out of range");
+      cap = e.ld_cap;  // (0 until the ensemble's first step with the record on)
+      ring = cap ? e.ld_ring + (size_t)member * cap * LOADS_ROW : nullptr;
+      cnt = cap ? e.ld_count + member : nullptr;
+    }
+    int64_t done = 0;
+    if (cnt) c.d2h(&done, cnt, sizeof(int64_t));
+    const i64 held = std::min<i64>(done, cap);
+    require(first + count <= held, "rows out of range (pucfem_loads_info: rows held)");
+    if (count == 0) return;
+    require(out != nullptr, "null output");
+    std::vector<double> h((size_t)cap * LOADS_ROW);
+    c.d2h(h.data(), ring, sizeof(double) * h.size());
+    for (i64 k = 0; k < count; ++k) {  // (oldest first: row k of the rows held is step done - held + k)
+      const i64 slot = (done - held + first + k) % cap;
+      std::copy(h.begin() + slot * LOADS_ROW, h.begin() + (slot + 1) * LOADS_ROW, out + k * LOADS_ROW);
+    }
+  });
+}
+
+int pucfem_loads_info(void* ctx, int32_t member, int64_t* out4) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(out4 != nullptr, "null output");
+    require(member >= -1, "member index out of range");
+    c.loads_ready(member);
+    const int64_t* cnt = c.ld_count;
+    if (member >= 0) {
+      Ens& e = *ens_of(c);
+      require(member < e.M, "member index out of range");
+      cnt = e.ld_cap ? e.ld_count + member : nullptr;
+    }
+    int64_t done = 0;
+    if (cnt) c.d2h(&done, cnt, sizeof(int64_t));
+    out4[0] = c.surface().size();
+    out4[1] = c.mesh.T;
+    out4[2] = done;
+    out4[3] = c.ld_cap;
+  });
+}
+
+int pucfem_loads_probe(void* ctx, int32_t iters, double* out2) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
+    c.loads_ready(-1);
+    auto launch = [&] { c.loads_own(nullptr, LoadsRec{nullptr, nullptr, 0}); };
+    launch();  // (untimed: the first launch)
+    out2[0] = time_launches(c, iters, launch);
+    out2[1] = c.loads_launch_bytes();
   });
 }
 

@@ -114,6 +114,43 @@ void red_refine(const HostMesh& in, HostMesh& out, std::vector<i32>* edge_a, std
   });
 }
 
+// ----------------------------------------------------------------------------- swimmer surface
+void surface_edges(const HostMesh& m, SurfaceEdges& S) {
+  S = SurfaceEdges{};
+  // the candidates: (min, max, triangle, k) of every local edge with marker 2 at both ends (few: the surface and
+  // the odd interior edge between two surface nodes), then those whose (min, max) occurs once
+  struct Cand {
+    i32 lo, hi;
+    i64 t;
+    int k;
+  };
+  std::vector<Cand> cand;
+  for (i64 t = 0; t < m.T; ++t)
+    for (int k = 0; k < 3; ++k) {
+      const i32 a = m.tri[3 * t + k], b = m.tri[3 * t + (k + 1) % 3];
+      if (m.mk[a] == 2 && m.mk[b] == 2) cand.push_back({std::min(a, b), std::max(a, b), t, k});
+    }
+  std::sort(cand.begin(), cand.end(), [](const Cand& p, const Cand& q) {
+    return p.lo != q.lo ? p.lo < q.lo : p.hi != q.hi ? p.hi < q.hi : p.t != q.t ? p.t < q.t : p.k < q.k;
+  });
+  std::vector<std::pair<i64, int>> keep;
+  for (size_t i = 0; i < cand.size();) {
+    size_t j = i + 1;
+    while (j < cand.size() && cand[j].lo == cand[i].lo && cand[j].hi == cand[i].hi) ++j;
+    if (j - i == 1) keep.push_back({cand[i].t, cand[i].k});
+    i = j;
+  }
+  std::sort(keep.begin(), keep.end());
+  for (const auto& e : keep) {
+    const i64 t = e.first;
+    const int k = e.second;
+    S.tri.push_back((i32)t);
+    S.a.push_back(m.tri[3 * t + k]);
+    S.b.push_back(m.tri[3 * t + (k + 1) % 3]);
+    S.opp.push_back(m.tri[3 * t + (k + 2) % 3]);
+  }
+}
+
 // ----------------------------------------------------------------------------- ordering
 // sqrt(N)/2 strips of equal node count: a strip is ~2 node spacings high and 2 sqrt(N) nodes long,
 // so a stiffness neighbour lies within one strip of its row and a periodic master's columns (its

@@ -144,6 +144,16 @@ struct HostMesh {
 void red_refine(const HostMesh& in, HostMesh& out, std::vector<i32>* edge_a = nullptr,
                 std::vector<i32>* edge_b = nullptr);
 
+// The swimmer surface (pucfem_swimmer_loads, pucfem_loads.hpp): the mesh edges whose two end nodes carry marker 2 and
+// which lie in exactly one triangle, in ascending (triangle, local edge k) order; local edge k runs from vertex k to
+// vertex (k + 1) mod 3 and `opp` is the third vertex.  Caller numbering.  Red refinement keeps a boundary edge's
+// midpoint on the chord with marker 2 (red_refine), so every level doubles the count and keeps the polygon.
+struct SurfaceEdges {
+  std::vector<i32> tri, a, b, opp;
+  i64 size() const { return (i64)tri.size(); }
+};
+void surface_edges(const HostMesh& m, SurfaceEdges& S);
+
 // CSR pattern / matrix with column ids in the INTERNAL (new) numbering.
 struct Csr {
   i64 nrows = 0;

@@ -23,6 +23,8 @@ import shutil
 
 import numpy as np
 
+from ._lib import LOADS_KEYS
+
 
 class FrameRecorder:
     """Record (step, dye, velocity) every `interval` steps of a simulation (fp32 copies by default,
@@ -43,10 +45,13 @@ class FrameRecorder:
 
     dyes=True: each frame also appends the simulation's dye channels (``StokesSimulation.dyes``) to ``dyes``, the way
     the dye is recorded: a copy (K, N) of the channels, or in raster mode one image per channel (K, H, W), rasterised
-    as "dye0" .. in the frame's raster call.  dyes= may also name the channels to record ("dye0", 2, ...)."""
+    as "dye0" .. in the frame's raster call.  dyes= may also name the channels to record ("dye0", 2, ...).
+
+    loads=True: each frame also appends the swimmer's ten loads of the frame's state (``sim.swimmer_loads()``: one
+    launch, ten doubles copied) to ``loads``, in LOADS_KEYS' order.  Off by default."""
 
     def __init__(self, mesh, interval=50, dtype=np.float32, raster=None, window=None, vorticity=False,
-                 streamlines=None, dyes=False):
+                 streamlines=None, dyes=False, loads=False):
         self.mesh = mesh
         self.interval = int(interval)
         self.dtype = dtype
@@ -72,6 +77,8 @@ class FrameRecorder:
         # True: every channel of the simulation; else the recorded channels' indices
         self.dye_channels = dyes if isinstance(dyes, bool) else _dye_indices(dyes)
         self.dyes: list[np.ndarray] = []
+        self.record_swimmer_loads = bool(loads)
+        self.loads: list[np.ndarray] = []
 
     def _channels(self, sim):
         """The indices of the channels to record from `sim`."""
@@ -129,6 +136,9 @@ class FrameRecorder:
                         self.dyes.append(np.array(sim.dyes[self._channels(sim)], dtype=self.dtype, copy=True))
                 if self.streamlines is not None:
                     self.record_lines(sim)
+                if self.record_swimmer_loads:
+                    d = sim.swimmer_loads()
+                    self.loads.append(np.array([d[k] for k in LOADS_KEYS]))
         return stats
 
     def __len__(self):
@@ -158,7 +168,7 @@ def save_npz(rec: FrameRecorder, path):
     """The raw frames.  Raster frames: `vel` (frames, 2, H, W), `dye` (frames, H, W) and `window`
     (x0, y0, x1, y1) instead of the mesh.  A recorder with vorticity frames adds `vort` (frames, H, W) or
     (frames, N); one with streamlines `lines` (frames, lines, nsteps + 1, 2) and `lines_npts` (frames, lines); one
-    with dye channels `dyes` (frames, K, N) or (frames, K, H, W)."""
+    with dye channels `dyes` (frames, K, N) or (frames, K, H, W); one with loads `loads` (frames, 10)."""
     if getattr(rec, "raster", None) is not None:
         W, H = rec.raster
         d = dict(steps=np.array(rec.steps), window=np.array(rec.window or (0.0, 0.0, 1.0, 1.0), dtype=np.float64),
@@ -175,6 +185,8 @@ def save_npz(rec: FrameRecorder, path):
         d["lines_npts"] = np.stack(rec.lines_npts)
     if getattr(rec, "dyes", None):
         d["dyes"] = np.stack(rec.dyes)
+    if getattr(rec, "loads", None):
+        d["loads"] = np.stack(rec.loads)
     np.savez_compressed(path, **d)
 
 

@@ -417,6 +417,28 @@ def build_mass_and_convection_mass(mesh: Mesh):
     return ctx.host_csr(_lib.OP_MCONS)
 
 
+def surface_edges(mesh: Mesh):
+    """The swimmer surface of the mesh (pucfem_host_surface_edges, on the host: no device needed): the edges whose
+    two end nodes carry marker 2 and which lie in exactly one triangle, as int32 arrays tri, a, b, opp in ascending
+    (triangle, local edge) order."""
+    ctx = Context(_lib.HOST_ONLY)
+    try:
+        ctx.upload(mesh)
+        return ctx.surface_edges()
+    finally:
+        ctx.close()
+
+
+def swimmer_loads(u, p, mesh: Mesh, nu, center=(0.5, 0.5), edges=False):
+    """The swimmer's loads of the given fields on the device (pucfem_loads_apply): u (N, 2), the pressure p (N).
+    The dict of Context.swimmer_loads; with edges=True also the (E, 8) per-edge values."""
+    from .solver import loads_dict
+
+    ctx = _stokes_context(mesh, 0.05, nu, SquirmerBC(nu=nu, center=tuple(center)))
+    r = ctx.loads_apply(u, p, edges)
+    return (loads_dict(r[0]), r[1]) if edges else loads_dict(r)
+
+
 def clear_cache():
     for c in _cache.values():
         c.close()

@@ -22,6 +22,20 @@ SAMPLE_FIELDS = {"u": (_lib.F_U, 2), "u_star": (_lib.F_USTAR, 2), "p": (_lib.F_P
                  "c": (_lib.F_C, 1), "vorticity": (_lib.F_VORTICITY, 1)}
 FLOW_KEYS = ("max_vorticity", "enstrophy", "kinetic_energy", "max_speed")
 _SAMPLE_NCOMP = {f: n for f, n in SAMPLE_FIELDS.values()}
+LOADS_KEYS = _lib.LOADS_KEYS  # pucfem_swimmer_loads' ten values, in order
+LOADS_SUMS = (("force_x", 0, 2), ("force_y", 1, 3), ("torque", 4, 5), ("power", 6, 7))
+
+
+def loads_dict(v):
+    """The ten values of pucfem_swimmer_loads (last axis of v) by name, with the pressure and viscous parts' sums
+    force_x, force_y, torque and power.  The parts stay separate: the splitting scheme's pressure is its own."""
+    v = np.asarray(v, dtype=np.float64)
+    d = {k: (float(v[q]) if v.ndim == 1 else v[..., q].copy()) for q, k in enumerate(LOADS_KEYS)}
+    for name, a, b in LOADS_SUMS:
+        d[name] = d[LOADS_KEYS[a]] + d[LOADS_KEYS[b]]
+    return d
+
+
 ADVECTION_NAMES = ("sl", "maccormack")  # pucfem_set_advection's schemes, by PUCFEM_ADV_SL / PUCFEM_ADV_MACCORMACK
 
 
@@ -419,6 +433,7 @@ class Context:
                                           _lib.iptr(T), int(coord_fp32)))
         self.N = X.shape[0]
         self.T = T.shape[0]
+        self.coords = X  # (surface_traction's edge midpoints and lengths)
 
     def set_pairs(self, kind, pairs):
         P = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 2))
@@ -458,6 +473,7 @@ class Context:
                         dye_scheme={"semilagrange": 0, "implicit": 1}[tol.dye], dye_diffusivity=tol.dye_diffusivity,
                         assembly={"auto": 0, "device": 0, "host": 1}[tol.assembly], proj_shared=int(tol.proj_shared))
         self.precond = "mg" if mg else "jacobi"
+        self.center = (float(center[0]), float(center[1]))
         self._c(self.L.pucfem_build_operators(self.h, ct.byref(p)))
 
     # ---------------------------------------------------------------- fields / steps
@@ -845,6 +861,76 @@ class Context:
         o = (ct.c_double * 4)()
         self._c(self.L.pucfem_flow_info(self.h, -1 if member is None else int(member), o))
         return dict(zip(FLOW_KEYS, (float(v) for v in o)))
+
+    # ---------------------------------------------------------------- swimmer loads
+    def surface_edges(self):
+        """The swimmer surface's edge list (pucfem_host_surface_edges; works host-only): int32 arrays tri, a, b, opp
+        in the caller's numbering, in ascending (triangle, local edge) order."""
+        n = ct.c_int64(0)
+        self._c(self.L.pucfem_host_surface_edges(self.h, ct.byref(n), None, None, None, None))
+        out = [np.zeros(n.value, dtype=np.int32) for _ in range(4)]
+        self._c(self.L.pucfem_host_surface_edges(self.h, ct.byref(n), *(_lib.iptr(a) for a in out)))
+        return dict(zip(("tri", "a", "b", "opp"), out))
+
+    def swimmer_loads(self, member=None):
+        """Force and torque of the fluid on the swimmer, the power it delivers to the fluid and the viscous
+        dissipation, reduced on the device from the current u and the last step's p + p2 (pucfem_swimmer_loads; one
+        launch, ten doubles copied): the ten LOADS_KEYS values and, as their sums, force_x, force_y, torque and
+        power.  member: that member of the context's ensemble."""
+        o = (ct.c_double * 10)()
+        self._c(self.L.pucfem_swimmer_loads(self.h, -1 if member is None else int(member), o))
+        return loads_dict(np.array(o[:]))
+
+    def surface_traction(self, member=None):
+        """The per-edge parts of swimmer_loads around the body (pucfem_surface_traction): {name: (E,)} for the first
+        eight LOADS_KEYS, with `theta`, the angle of the edge midpoints about the centre, and `length`."""
+        E = self.surface_edges()
+        out = np.zeros((len(E["tri"]), 8))
+        self._c(self.L.pucfem_surface_traction(self.h, -1 if member is None else int(member), _lib.dptr(out)))
+        d = {k: out[:, q].copy() for q, k in enumerate(LOADS_KEYS[:8])}
+        X, c = self.coords, getattr(self, "center", (0.5, 0.5))
+        mid = 0.5 * (X[E["a"]] + X[E["b"]])
+        d["theta"] = np.arctan2(mid[:, 1] - c[1], mid[:, 0] - c[0])
+        d["length"] = np.hypot(*(X[E["b"]] - X[E["a"]]).T)
+        return d
+
+    def loads_apply(self, u, p, edges=False):
+        """The unit operation (pucfem_loads_apply): the ten values of the caller's u (N, 2) and pressure p (N), with
+        edges=True also the (E, 8) per-edge values."""
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if u.shape != (self.N, 2) or p.shape != (self.N,):
+            raise ValueError("u is (N, 2) and p is (N,)")
+        o = np.zeros(10)
+        e = np.zeros((len(self.surface_edges()["tri"]), 8)) if edges else None
+        self._c(self.L.pucfem_loads_apply(self.h, _lib.dptr(u), _lib.dptr(p), _lib.dptr(o),
+                                          _lib.dptr(e) if edges else None))
+        return (o, e) if edges else o
+
+    def record_loads(self, capacity):
+        """Switch the loads record on (a device ring of `capacity` rows, one per step and per ensemble member) or,
+        with 0, off (pucfem_set_loads_record).  Every call starts from zero rows."""
+        self._c(self.L.pucfem_set_loads_record(self.h, int(capacity)))
+
+    def loads_info(self, member=None):
+        o = (ct.c_int64 * 4)()
+        self._c(self.L.pucfem_loads_info(self.h, -1 if member is None else int(member), o))
+        return dict(edges=o[0], triangles=o[1], recorded=o[2], capacity=o[3])
+
+    def loads_history(self, member=None):
+        """(n, 11) the rows the record holds, oldest first: the row's number since the record was set, then the ten
+        LOADS_KEYS values after that step (pucfem_loads_record)."""
+        i = self.loads_info(member)
+        n = min(i["recorded"], i["capacity"])
+        out = np.zeros((n, 11))
+        self._c(self.L.pucfem_loads_record(self.h, -1 if member is None else int(member), 0, n, _lib.dptr(out)))
+        return out
+
+    def loads_probe(self, iters=10):
+        """Kernel time and algorithmic bytes of the loads launch (pucfem_loads_probe; tools/loads_bench.py)."""
+        o = (ct.c_double * 2)()
+        self._c(self.L.pucfem_loads_probe(self.h, int(iters), o))
+        return dict(ms=o[0], bytes=o[1])
 
     def comm_info(self):
         """Multi-rank data flow of the last step (pucfem_comm_info)."""
@@ -1248,6 +1334,25 @@ class StokesSimulation:
     def flow_info(self):
         """Context.flow_info of this run."""
         return self.ctx.flow_info()
+
+    def swimmer_loads(self):
+        """Context.swimmer_loads of this run: the force and torque on the swimmer, its power and the dissipation."""
+        return self.ctx.swimmer_loads()
+
+    def surface_traction(self):
+        """Context.surface_traction of this run: the per-edge pressure and viscous parts around the body."""
+        return self.ctx.surface_traction()
+
+    def record_loads(self, capacity):
+        """Context.record_loads: every later step appends its loads to a device ring of `capacity` rows (0: off)."""
+        self.ctx.record_loads(capacity)
+
+    def loads_history(self):
+        """Context.loads_history of this run: (n, 11), the rows held, oldest first."""
+        return self.ctx.loads_history()
+
+    def loads_info(self):
+        return self.ctx.loads_info()
 
     def sample(self, points, fields=("u", "c")):
         """The fields at arbitrary points (Context.sample): ({field: values}, triangle ids)."""
@@ -1949,6 +2054,33 @@ class StokesEnsemble:
         rows = [self.ctx.flow_info(m) for m in range(self.M)]
         return {k: np.array([r[k] for r in rows]) for k in FLOW_KEYS}
 
+    def swimmer_loads(self):
+        """Context.swimmer_loads of every member (one call each): {name: (M,) array}."""
+        rows = [self.ctx.swimmer_loads(m) for m in range(self.M)]
+        return {k: np.array([r[k] for r in rows]) for k in rows[0]}
+
+    def surface_traction(self, member=None):
+        """Context.surface_traction of every member: {name: (M, E) array}; theta and length are the mesh's, (E,).
+        member = m: that member's alone."""
+        if member is not None:
+            return self.ctx.surface_traction(member)
+        rows = [self.ctx.surface_traction(m) for m in range(self.M)]
+        d = {k: np.stack([r[k] for r in rows]) for k in LOADS_KEYS[:8]}
+        d["theta"], d["length"] = rows[0]["theta"], rows[0]["length"]
+        return d
+
+    def record_loads(self, capacity):
+        """Context.record_loads for every member: each later step appends one row per member (0: off).  The step
+        stays one captured graph; the rows' indices are counts in device memory."""
+        self.ctx.record_loads(capacity)
+
+    def loads_history(self):
+        """(M, n, 11): every member's rows held, oldest first (Context.loads_history per member)."""
+        return np.stack([self.ctx.loads_history(m) for m in range(self.M)])
+
+    def loads_info(self, member=0):
+        return self.ctx.loads_info(member)
+
     @property
     def tracers(self):
         return self.get(_lib.F_TRACERS)
@@ -2029,7 +2161,7 @@ class StokesEnsemble:
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
                    inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
                    dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
-                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None):
+                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None, loads=False):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
     'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
@@ -2039,7 +2171,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
     None per member (StokesEnsemble.set_stroke).  dye_trajectory, velocity_trajectory, tracer_trajectory: 'euler' or
     'midpoint', one name for all members or one per member; trajectory: StokesSimulation's keyword per member
     (StokesEnsemble.set_trajectory).  dyes (scheme 'color'): (K, N) dye channels for all members or (M, K, N)
-    (StokesEnsemble.dyes); each member's Result.dyes holds its channels after the last step."""
+    (StokesEnsemble.dyes); each member's Result.dyes holds its channels after the last step.  loads: every step records
+    every member's loads on the device (StokesEnsemble.record_loads); each member's Result.loads holds its rows."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -2050,8 +2183,11 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
                          velocity_trajectory=velocity_trajectory, tracer_trajectory=tracer_trajectory,
                          trajectory=trajectory, dyes=dyes)
     try:
+        if loads:
+            ens.record_loads(max(int(steps), 1))
         st = ens.step(steps) if steps else []
         u, p = ens.u, ens.get(_lib.F_P)
+        ld = ens.loads_history() if loads else None
         dy = ens.dyes if dyes is not None else None
         c = ens.c if scheme == "color" else None
         tr, ts, cs = (ens.tracers, ens.tracer_status, ens.capture_step) if scheme == "food" else (None, None, None)
@@ -2060,6 +2196,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
     res = []
     for m in range(ens.M):
         r = Result(scheme, steps, u=u[m], p=p[m], stats=[s[m] for s in st])
+        if ld is not None:
+            r.loads = ld[m]
         if scheme == "color":
             r.c = c[m]
             if dy is not None:
@@ -2185,11 +2323,12 @@ class Result:
     scalar: np.ndarray | None = None
     stats: list = field(default_factory=list)
     dyes: np.ndarray | None = None  # scheme 'color' with dyes=: the final dye channels (K, N)
+    loads: np.ndarray | None = None  # Stokes schemes with loads=True: (steps, 11), the row number and LOADS_KEYS per step
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
           tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
-          tracer_seed=0, force=None, buoyancy=None, stroke=None, trajectory="euler"):
+          tracer_seed=0, force=None, buoyancy=None, stroke=None, trajectory="euler", loads=False):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -2206,7 +2345,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     field or None, and the Buoyancy of the dye (StokesSimulation.force / buoyancy; its terms may name the dyes=).
     stroke (schemes 'color' and 'food'): a Stroke, the squirmer's boundary values per step (StokesSimulation.stroke).
     trajectory 'euler' | 'midpoint' (schemes 'color' and 'food'): the path of whatever the run transports -- the dye
-    on 'color', the velocity with inertia, the tracers on 'food' (StokesSimulation.dye_trajectory and its kin)."""
+    on 'color', the velocity with inertia, the tracers on 'food' (StokesSimulation.dye_trajectory and its kin).
+    loads (schemes 'color' and 'food'): every step records the swimmer's loads on the device
+    (StokesSimulation.record_loads); the result's `loads` holds the (steps, 11) rows."""
+    if loads and scheme not in ("color", "food"):
+        raise ValueError("loads belong to the Stokes schemes 'color' and 'food'")
     if trajectory_order(trajectory) != _lib.TRJ_EULER and scheme not in ("color", "food"):
         raise ValueError("trajectory belongs to the Stokes schemes 'color' and 'food'")
     if stroke is not None and scheme not in ("color", "food"):
@@ -2234,8 +2377,12 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
             sim.dyes = dyes
         if buoyancy is not None:  # (behind the channels its terms may name)
             sim.buoyancy = buoyancy
+        if loads:
+            sim.record_loads(max(int(steps), 1))
         st = sim.step(steps) if steps else []
         res = Result(scheme, steps, u=sim.u, p=sim.field(_lib.F_P), stats=st)
+        if loads:
+            res.loads = sim.loads_history()
         if dyes is not None:
             res.dyes = sim.dyes
         if scheme == "color":
