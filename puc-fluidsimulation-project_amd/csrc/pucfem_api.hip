@@ -1258,25 +1258,6 @@ struct Ctx {
     need_dev();
     state(has_cgrid && has_locator(), "the context has no point locator");
   }
-  // k_sl_multi over rows [row0, row0 + n) on the current stream: nch channels of leading dimension N
-  void dye_launch(i64 row0, i64 n, const double* vx, const double* vy, double dt, int nch, const double* cin,
-                  double* cout, int32_t* nf, int32_t* nfpart) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    with_loc([&](const auto& L) {
-      klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-              (int64_t)row0, (int64_t)n, vx, vy, dt, (int32_t)nch, cin, cout, (int64_t)mesh.N, nf, nfpart);
-    });
-    KCHK();
-  }
-  // the channels' part of a step, on the stream of the step's sl_launch, with the step's final u
-  void dyes_step() {
-    if (!ndye) return;
-    dye_launch(lp.r0, lp.n_own, ux, uy, prm.dt, ndye, dye_cur, dye_nxt, nullptr, dye_nfpart);
-    std::swap(dye_cur, dye_nxt);
-    dye_nb = nb_dye(lp.n_own);
-    ++dye_steps;
-  }
   void drop_dyes() {
     if (!dye_cur && !dye_nfpart) {
       ndye = 0;
@@ -1347,43 +1328,20 @@ struct Ctx {
     need_dev();
     state(has_cgrid && has_locator(), "the context has no point locator");
   }
-  // k_sl_vel over rows [row0, row0 + n) on the current stream: out = SL(f; u, dt), all three interleaved pairs
-  void vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* out2, int32_t* nf,
-                  int32_t* nfpart) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
-    const dbl2* f = reinterpret_cast<const dbl2*>(f2);
-    dbl2* out = reinterpret_cast<dbl2*>(out2);
-    with_loc([&](const auto& L) {
-      klaunch(-1, vel_launch_bytes(n), k_sl_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-              (int64_t)row0, (int64_t)n, u, dt, f, out, nf, nfpart);
-    });
-    KCHK();
-  }
-  // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity)
+  // the inertial part of a step, on the main stream in front of the viscous solve (f = u = the current velocity),
+  // into the same buffers and counts under every mode
   void inertia_step() {
     if (!inertia) return;
-    if (trj_vel == PUCFEM_TRJ_MIDPOINT) {  // (the fused launches, into the Euler step's buffers and counts)
-      if (adv_vel) {
-        trj_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, mcv_ch, u_adv, mcv_rec, nullptr, nullptr, adv_nfpart, mcv_cnt,
-                       trjv_mid);
-        mcv_nb = nb_dye(lp.n_own);
-        ++mcv_steps;
-      } else {
-        trj_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, nullptr, nullptr, nullptr, adv_nfpart, nullptr,
-                       trjv_mid, 1);
-      }
-      trjv_nb = nb_dye(lp.n_own);
-      ++trjv_steps;
-    } else if (adv_vel) {
-      mc_vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, mcv_ch, u_adv, mcv_rec, nullptr, nullptr, adv_nfpart, mcv_cnt);
-      mcv_nb = nb_dye(lp.n_own);
-      ++mcv_steps;
-    } else {
-      vel_launch(lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, nullptr, adv_nfpart);
-    }
-    adv_nb = nb_dye(lp.n_own);
+    const TransportMode m{adv_vel, trj_vel};
+    TransportWork w;
+    w.nfpart = adv_nfpart;
+    if (m.mc()) w.ch = mcv_ch, w.rec = mcv_rec, w.cnt = mcv_cnt;
+    if (m.mid()) w.mid = trjv_mid;
+    transport_pairs(m, lp.r0, lp.n_own, ux, prm.dt, ux, u_adv, w);
+    const int nb = nb_dye(lp.n_own);
+    if (m.mc()) mcv_nb = nb, ++mcv_steps;
+    if (m.mid()) trjv_nb = nb, ++trjv_steps;
+    adv_nb = nb;
     ++adv_steps;
     adv_valid = true;
   }
@@ -1754,73 +1712,6 @@ struct Ctx {
   double mcv_bytes1(i64 n) const { return vel_launch_bytes(n) + 16.0 * (double)n; }
   // (the pair form counts f as vel_launch_bytes does: the gathered vertices' lines are the rows' own, f = u)
   double mcv_bytes2(i64 n) const { return ((lat_sl ? 52.0 : 32.0) + 16.0 + 32.0) * (double)n; }
-  void mc_fwd(i64 row0, i64 n, const double* vx, const double* vy, double dt, const double* c0, double* ch0, int nch,
-              const double* cin, double* chout, int4* rec, int32_t* nfpart, double* nfd) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    with_loc([&](const auto& L) {
-      klaunch(-1, mc_bytes1(nch + (c0 ? 1 : 0), n), k_mc_fwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-              (int64_t)row0, (int64_t)n, vx, vy, dt, c0, ch0, (int32_t)nch, cin, chout, (int64_t)mesh.N, rec, nfpart,
-              nfd);
-    });
-    KCHK();
-  }
-  void mc_bwd(i64 row0, i64 n, const double* vx, const double* vy, double dt, const double* c0, const double* ch0,
-              double* out0, int nch, const double* cin, const double* ch, double* cout, const int4* rec,
-              int32_t* marks, int32_t* tri, int32_t* cnt) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    with_loc([&](const auto& L) {
-      klaunch(-1, mc_bytes2(nch + (c0 ? 1 : 0), n), k_mc_bwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-              (int64_t)row0, (int64_t)n, vx, vy, dt, c0, ch0, out0, (int32_t)nch, cin, ch, cout, (int64_t)mesh.N, rec,
-              marks, tri, cnt);
-    });
-    KCHK();
-  }
-  // both passes of the pair form on the current stream: out = MC(f; u, dt); ch, out and f are three buffers
-  void mc_vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* ch2, double* out2,
-                     int4* rec, int32_t* marks, int32_t* tri, int32_t* nfpart, int32_t* cnt, int pass = 3) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
-    const dbl2* f = reinterpret_cast<const dbl2*>(f2);
-    dbl2* ch = reinterpret_cast<dbl2*>(ch2);
-    dbl2* out = reinterpret_cast<dbl2*>(out2);
-    with_loc([&](const auto& L) {
-      if (pass & 1)
-        klaunch(-1, mcv_bytes1(n), k_mc_fwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-                (int64_t)row0, (int64_t)n, u, dt, f, ch, rec, nfpart);
-      if (pass & 2)
-        klaunch(-1, mcv_bytes2(n), k_mc_bwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-                (int64_t)row0, (int64_t)n, u, dt, f, (const dbl2*)ch, out, (const int4*)rec, marks, tri, cnt);
-    });
-    KCHK();
-  }
-  // the dye's part of a step, where sl_launch + dyes_step stand, on their stream, with the step's final u:
-  // c_full -> cnew, the channels dye_cur -> dye_nxt (swapped here, as dyes_step does), and the mixing sums of cnew
-  // into part_sl as the implicit dye forms them
-  void mc_dye_step(double* cnew) {
-    const i64 n = lp.n_own, N = mesh.N;
-    mc_fwd(lp.r0, n, ux, uy, prm.dt, c_full, mc_ch, ndye, dye_cur, mc_ch + N, mc_rec, ndye ? dye_nfpart : mc_nfpart,
-           mc_nfd);
-    mc_bwd(lp.r0, n, ux, uy, prm.dt, c_full, mc_ch, cnew, ndye, dye_cur, mc_ch + N, dye_nxt, mc_rec, nullptr, nullptr,
-           mc_cnt);
-    mc_nb = nb_dye(n);
-    ++mc_steps;
-    if (ndye) {
-      std::swap(dye_cur, dye_nxt);
-      dye_nb = mc_nb;
-      ++dye_steps;
-    }
-    hipLaunchKernelGGL(k_wsum, dim3(mc_nb), dim3(BS), 0, st, lp.r0, n, (const double*)cnew, (const double*)dwmix,
-                       part_sl);
-    KCHK();
-  }
-  // ... and its sums: sum wc, sum w (k_wsum's blocks), then the step record's not-found entry, pass 1's
-  void mc_dye_reduce() {
-    reduce_into(part_sl, mc_nb, 2, false, 2, SLB);
-    reduce_into(mc_nfd, mc_nb, 1, false, 4, SLB);
-  }
   // the three counts of a pass-2 launch, its nb blocks summed in block order
   void mc_counts(const int32_t* cnt, int nb, int64_t* out3) {
     out3[0] = out3[1] = out3[2] = 0;
@@ -1949,86 +1840,158 @@ struct Ctx {
     need_dev();
     state(has_tgrid, "the context has no tracer grid");
   }
-  // k_trj_fwd / k_trj_bwd over rows [row0, row0 + n) of a single-rank context (u2: the full mesh's pairs)
-  void trj_fwd(i64 row0, i64 n, const double* u2, double dt, const double* c0, double* ch0, int nch, const double* cin,
-               double* chout, int4* rec, int32_t* marks, int32_t* nfpart, double* nfd, int32_t* mid) {
+
+  // ------------------------------------------------------------------ the transport layer
+  // The one place that knows which kernels move a field under a mode, over rows [row0, row0 + n) of a single-rank
+  // context on the current stream (u2: the full mesh's interleaved pairs):
+  //   (SL, Euler)     k_sl_multi / k_sl_vel                 one pass
+  //   (MC, Euler)     k_mc_fwd, k_mc_bwd (_vel)             two passes
+  //   (SL, midpoint)  k_trj_fwd (_vel)                      one pass, straight into the result
+  //   (MC, midpoint)  k_trj_fwd, k_trj_bwd (_vel)           two passes
+  // The step (dye_transport_step, inertia_step), the unit entry points and the probes all launch through
+  // transport_fields / transport_pairs; a new scheme or order is added to these two (and to ens_transport, their
+  // ensemble twin).  c itself under (SL, Euler) is not here: it stays on sl_launch, whose k_sl fuses the mixing sums
+  // and is a different kernel.
+  struct TransportMode {
+    int scheme = PUCFEM_ADV_SL, order = PUCFEM_TRJ_EULER;
+    bool mc() const { return scheme == PUCFEM_ADV_MACCORMACK; }
+    bool mid() const { return order == PUCFEM_TRJ_MIDPOINT; }
+  };
+  // a launch's work buffers; null where the mode (or the caller) has no use for one
+  struct TransportWork {
+    double* ch = nullptr;        // two-pass: pass 1's fields (c0's first where there is one, then the channels'; pairs)
+    int4* rec = nullptr;         // two-pass: pass 1's triangle per row
+    int32_t* marks = nullptr;    // per row: the not-found flag (SL, Euler) or the mode's marks
+    int32_t* tri = nullptr;      // two-pass: pass 2's triangle per row
+    int32_t* nfpart = nullptr;   // per block: the not-found rows (pass 1's)
+    double* nfd = nullptr;       // ... as doubles (plain fields, beside a c0)
+    int32_t* cnt = nullptr;      // two-pass: pass 2's three counts per block
+    int32_t* mid = nullptr;      // midpoint: the blocks' midpoint-not-found rows, pass 1 then pass 2 (2 x SLB)
+  };
+  // plain fields: c0 -> out0 (optional; not under (SL, Euler), where k_sl_multi moves the channels only) and nch
+  // channels cin -> cout of leading dimension N.  pass & 1: the first pass (the whole of a one-pass mode), pass & 2:
+  // the second
+  void transport_fields(TransportMode m, i64 row0, i64 n, const double* u2, double dt, const double* c0, double* out0,
+                        int nch, const double* cin, double* cout, const TransportWork& w, int pass = 3) {
     const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
+    const dim3 nb(nb_dye(n));
+    const double *vx = u2, *vy = u2 + 1, hdt = 0.5 * dt;
     const dbl2* u = reinterpret_cast<const dbl2*>(u2);
-    const double hdt = 0.5 * dt;
+    const int nf = nch + (c0 ? 1 : 0);
+    const int64_t N = mesh.N;
+    double* ch0 = c0 ? w.ch : nullptr;            // (two-pass) c0's intermediate field ...
+    double* chn = c0 && w.ch ? w.ch + N : w.ch;  // ... and the channels'
     with_loc([&](const auto& L) {
-      klaunch(-1, trj_bytes1(nch + (c0 ? 1 : 0), n, rec != nullptr), k_trj_fwd<std::decay_t<decltype(L)>>, dim3(nb),
-              dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, c0, ch0, (int32_t)nch, cin, chout,
-              (int64_t)mesh.N, rec, marks, nfpart, nfd, mid);
+      using Loc = std::decay_t<decltype(L)>;
+      if (m.mid()) {
+        if ((pass & 1) && m.mc())
+          klaunch(-1, trj_bytes1(nf, n, true), k_trj_fwd<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u,
+                  dt, hdt, c0, ch0, (int32_t)nch, cin, chn, N, w.rec, w.marks, w.nfpart, w.nfd, w.mid);
+        else if (pass & 1)
+          klaunch(-1, trj_bytes1(nf, n, false), k_trj_fwd<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n,
+                  u, dt, hdt, c0, out0, (int32_t)nch, cin, cout, N, (int4*)nullptr, w.marks, w.nfpart, w.nfd, w.mid);
+        if ((pass & 2) && m.mc())
+          klaunch(-1, trj_bytes2(nf, n), k_trj_bwd<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt,
+                  hdt, c0, (const double*)ch0, out0, (int32_t)nch, cin, (const double*)chn, cout, N,
+                  (const int4*)w.rec, w.marks, w.tri, w.cnt, w.mid + SLB);
+      } else if (m.mc()) {
+        if (pass & 1)
+          klaunch(-1, mc_bytes1(nf, n), k_mc_fwd<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, vx, vy, dt,
+                  c0, ch0, (int32_t)nch, cin, chn, N, w.rec, w.nfpart, w.nfd);
+        if (pass & 2)
+          klaunch(-1, mc_bytes2(nf, n), k_mc_bwd<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, vx, vy, dt,
+                  c0, (const double*)ch0, out0, (int32_t)nch, cin, (const double*)chn, cout, N, (const int4*)w.rec,
+                  w.marks, w.tri, w.cnt);
+      } else if (pass & 1) {
+        klaunch(-1, dye_launch_bytes(nch, n), k_sl_multi<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, vx,
+                vy, dt, (int32_t)nch, cin, cout, N, w.marks, w.nfpart);
+      }
     });
     KCHK();
   }
-  void trj_bwd(i64 row0, i64 n, const double* u2, double dt, const double* c0, const double* ch0, double* out0, int nch,
-               const double* cin, const double* ch, double* cout, const int4* rec, int32_t* marks, int32_t* tri,
-               int32_t* cnt, int32_t* mid) {
+  // interleaved pairs: out = transport(f; u, dt); f, out and (two-pass) w.ch are three buffers
+  void transport_pairs(TransportMode m, i64 row0, i64 n, const double* u2, double dt, const double* f2, double* out2,
+                       const TransportWork& w, int pass = 3) {
     const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
-    const dbl2* u = reinterpret_cast<const dbl2*>(u2);
-    const double hdt = 0.5 * dt;
-    with_loc([&](const auto& L) {
-      klaunch(-1, trj_bytes2(nch + (c0 ? 1 : 0), n), k_trj_bwd<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L,
-              cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, c0, ch0, out0, (int32_t)nch, cin, ch, cout, (int64_t)mesh.N,
-              rec, marks, tri, cnt, mid);
-    });
-    KCHK();
-  }
-  // the pair form: pass & 1 k_trj_fwd_vel (f -> ch; the whole of a one-pass step), pass & 2 k_trj_bwd_vel (-> out)
-  void trj_vel_launch(i64 row0, i64 n, const double* u2, double dt, const double* f2, double* ch2, double* out2,
-                      int4* rec, int32_t* marks, int32_t* tri, int32_t* nfpart, int32_t* cnt, int32_t* mid,
-                      int pass = 3) {
-    const MeshDev M{mx, my, mtri, mesh.T};
-    const int nb = nb_dye(n);
+    const dim3 nb(nb_dye(n));
     const dbl2* u = reinterpret_cast<const dbl2*>(u2);
     const dbl2* f = reinterpret_cast<const dbl2*>(f2);
-    dbl2* ch = reinterpret_cast<dbl2*>(ch2);
+    dbl2* ch = reinterpret_cast<dbl2*>(w.ch);
     dbl2* out = reinterpret_cast<dbl2*>(out2);
     const double hdt = 0.5 * dt;
     with_loc([&](const auto& L) {
-      if (pass & 1)
-        klaunch(-1, trjv_bytes1(n, rec != nullptr), k_trj_fwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L,
-                cgrid, (int64_t)row0, (int64_t)n, u, dt, hdt, f, ch, rec, marks, nfpart, mid);
-      if (pass & 2)
-        klaunch(-1, trjv_bytes2(n), k_trj_bwd_vel<std::decay_t<decltype(L)>>, dim3(nb), dim3(BS), M, L, cgrid,
-                (int64_t)row0, (int64_t)n, u, dt, hdt, f, (const dbl2*)ch, out, (const int4*)rec, marks, tri, cnt,
-                mid + SLB);
+      using Loc = std::decay_t<decltype(L)>;
+      if (m.mid()) {
+        if ((pass & 1) && m.mc())
+          klaunch(-1, trjv_bytes1(n, true), k_trj_fwd_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u,
+                  dt, hdt, f, ch, w.rec, w.marks, w.nfpart, w.mid);
+        else if (pass & 1)
+          klaunch(-1, trjv_bytes1(n, false), k_trj_fwd_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n,
+                  u, dt, hdt, f, out, (int4*)nullptr, w.marks, w.nfpart, w.mid);
+        if ((pass & 2) && m.mc())
+          klaunch(-1, trjv_bytes2(n), k_trj_bwd_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt,
+                  hdt, f, (const dbl2*)ch, out, (const int4*)w.rec, w.marks, w.tri, w.cnt, w.mid + SLB);
+      } else if (m.mc()) {
+        if (pass & 1)
+          klaunch(-1, mcv_bytes1(n), k_mc_fwd_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt, f,
+                  ch, w.rec, w.nfpart);
+        if (pass & 2)
+          klaunch(-1, mcv_bytes2(n), k_mc_bwd_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt, f,
+                  (const dbl2*)ch, out, (const int4*)w.rec, w.marks, w.tri, w.cnt);
+      } else if (pass & 1) {
+        klaunch(-1, vel_launch_bytes(n), k_sl_vel<Loc>, nb, dim3(BS), M, L, cgrid, (int64_t)row0, (int64_t)n, u, dt, f,
+                out, w.marks, w.nfpart);
+      }
     });
     KCHK();
   }
-  // the dye's part of a step with the midpoint on, where sl_launch + dyes_step or mc_dye_step stand (their stream,
-  // their buffers, the step's final u): c_full -> cnew, the channels dye_cur -> dye_nxt (swapped here), k_wsum's
-  // mixing sums of cnew into part_sl
-  void trj_dye_step(double* cnew) {
-    const i64 n = lp.n_own, N = mesh.N;
-    int32_t* nfp = ndye ? dye_nfpart : trjd_nfpart;
-    if (adv_dye) {
-      trj_fwd(lp.r0, n, ux, prm.dt, c_full, mc_ch, ndye, dye_cur, mc_ch + N, mc_rec, nullptr, nfp, trjd_nfd, trjd_mid);
-      trj_bwd(lp.r0, n, ux, prm.dt, c_full, mc_ch, cnew, ndye, dye_cur, mc_ch + N, dye_nxt, mc_rec, nullptr, nullptr,
-              mc_cnt, trjd_mid + SLB);
-      mc_nb = nb_dye(n);
-      ++mc_steps;
+  // the dye's part of a step, on the stream of the step's tail, with the step's final u: c_full -> cnew and the
+  // channels dye_cur -> dye_nxt (swapped here: a launch cannot write a set that other rows still gather from).
+  // (SL, Euler): sl_launch with the fused reduction rs, then the channels' launch; every other mode moves c and the
+  // channels together and leaves k_wsum's mixing sums of cnew in part_sl, as the implicit dye forms them
+  void dye_transport_step(double* cnew, const RedOut& rs) {
+    const i64 n = lp.n_own;
+    const TransportMode m{adv_dye, trj_dye};
+    const int nb = nb_dye(n);
+    const bool fused = m.mc() || m.mid();
+    TransportWork w;
+    w.nfpart = dye_nfpart;
+    if (fused) {
+      if (!ndye) w.nfpart = m.mid() ? trjd_nfpart : mc_nfpart;
+      w.nfd = m.mid() ? trjd_nfd : mc_nfd;
+      if (m.mc()) w.ch = mc_ch, w.rec = mc_rec, w.cnt = mc_cnt;
+      if (m.mid()) w.mid = trjd_mid;
+      transport_fields(m, lp.r0, n, ux, prm.dt, c_full, cnew, ndye, dye_cur, dye_nxt, w);
+      if (m.mc()) mc_nb = nb, ++mc_steps;
+      if (m.mid()) trjd_nb = nb, ++trjd_steps;
     } else {
-      trj_fwd(lp.r0, n, ux, prm.dt, c_full, cnew, ndye, dye_cur, dye_nxt, nullptr, nullptr, nfp, trjd_nfd, trjd_mid);
+      sl_launch(nb_sl(n), lp.r0, n, ux, uy, prm.dt, c_full, cnew, dwmix, nullptr, rs);
+      KCHK();
+      if (ndye) transport_fields(m, lp.r0, n, ux, prm.dt, nullptr, nullptr, ndye, dye_cur, dye_nxt, w);
     }
-    trjd_nb = nb_dye(n);
-    ++trjd_steps;
     if (ndye) {
       std::swap(dye_cur, dye_nxt);
-      dye_nb = trjd_nb;
+      dye_nb = nb;
       ++dye_steps;
     }
-    hipLaunchKernelGGL(k_wsum, dim3(trjd_nb), dim3(BS), 0, st, lp.r0, n, (const double*)cnew, (const double*)dwmix,
-                       part_sl);
-    KCHK();
+    if (fused) {
+      hipLaunchKernelGGL(k_wsum, dim3(nb), dim3(BS), 0, st, lp.r0, n, (const double*)cnew, (const double*)dwmix,
+                         part_sl);
+      KCHK();
+    }
   }
-  // ... and its sums, as mc_dye_reduce: sum wc, sum w, then the step record's not-found entry (the final locate's)
-  void trj_dye_reduce() {
-    reduce_into(part_sl, trjd_nb, 2, false, 2, SLB);
-    reduce_into(trjd_nfd, trjd_nb, 1, false, 4, SLB);
+  // ... and its sums into the step record: sum wc, sum w and the not-found rows (the final locate's; pass 1's under
+  // MacCormack).  (SL, Euler): k_sl's three partials, unless rs reduced them in the launch (done: red_done follows)
+  void dye_transport_reduce(const RedOut& rs, bool done) {
+    const TransportMode m{adv_dye, trj_dye};
+    if (m.mc() || m.mid()) {
+      reduce_into(part_sl, nb_dye(lp.n_own), 2, false, 2, SLB);
+      reduce_into(m.mid() ? trjd_nfd : mc_nfd, nb_dye(lp.n_own), 1, false, 4, SLB);
+    } else if (!rs.out) {
+      reduce_into(part_sl, nb_sl(lp.n_own), 3, false, 2, SLB);
+    } else if (done) {
+      red_done(vals + 2, 3, false);
+    }
   }
   // the rows of the last launch whose midpoint was not found (pass 1's and, with pass2, pass 2's), in block order
   int64_t trj_mid_rows(const int32_t* mid, int nb, bool pass2) {
@@ -3913,22 +3876,11 @@ struct Ctx {
   }
   // the semi-Lagrangian part of the tail (launched on st_sl: the caller swapped the streams) and the step record
   void dye_tail_sl(double* rec) {
-    const int nb = nb_sl(lp.n_own);
     const RedOut rs = ro(vals + 2, CNT_DYE_SL, 3, SLB);
-    const bool trj = trj_dye == PUCFEM_TRJ_MIDPOINT;
-    if (trj) {
-      trj_dye_step(c_new);  // (c and the channels, one or two fused launches; before ev_sl is recorded, as below)
-    } else if (adv_dye) {
-      mc_dye_step(c_new);  // (c and the channels; before ev_sl is recorded, as below)
-    } else {
-      sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, rs);
-      KCHK();
-      dyes_step();  // (before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
-    }
+    // (c and the channels, before ev_sl is recorded: sl_join also orders the next write of u after the channels' reads)
+    dye_transport_step(c_new, rs);
     std::swap(c_full, c_new);
-    if (trj) trj_dye_reduce();
-    else if (adv_dye) mc_dye_reduce();
-    else if (!rs.out) reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
+    dye_transport_reduce(rs, false);  // sum wc, sum w, not-found
     const int nbm = nb_rows(lp.n_own);
     algo_bytes += 16.0 * (double)lp.n_own;  // c, w
     const RedOut rm = ro(vals + 5, CNT_DYE_MIX, 1);
@@ -4039,15 +3991,9 @@ struct Ctx {
         its[1] = itp;
         its[2] = itp2;
         return;
-      } else if (trj_dye == PUCFEM_TRJ_MIDPOINT) {
-        trj_dye_step(c_new);
-      } else if (adv_dye) {
-        mc_dye_step(c_new);
       } else {
-        sl_ro = ro(vals + 2, CNT_SL, 3, SLB);
-        sl_launch(nb, lp.r0, lp.n_own, ux, uy, prm.dt, c_full, c_new, dwmix, nullptr, sl_ro);
-        KCHK();
-        dyes_step();
+        if (!adv_dye && trj_dye == PUCFEM_TRJ_EULER) sl_ro = ro(vals + 2, CNT_SL, 3, SLB);
+        dye_transport_step(c_new, sl_ro);
       }
       KCHK();
       // fixed buffers inside a captured graph: k_mix2 copies the new values back instead of a swap
@@ -4057,10 +4003,9 @@ struct Ctx {
       } else if (!mix_copy) {
         std::swap(c_full, c_new);
       }
-      if (trj_dye == PUCFEM_TRJ_MIDPOINT && !dye_impl) trj_dye_reduce();
-      else if (adv_dye && !dye_impl) mc_dye_reduce();
-      else if (sl_ro.out) red_done(vals + 2, 3, false);
-      else reduce_into(part_sl, nb, 3, false, 2, SLB);  // sum wc, sum w, not-found
+      // sum wc, sum w, not-found (the implicit dye: k_wsum's partials, no fused reduction)
+      if (dye_impl) reduce_into(part_sl, nb, 3, false, 2, SLB);
+      else dye_transport_reduce(sl_ro, true);
       sl_ro = RedOut{};
       const int nbm = nb_rows(lp.n_own);
       algo_bytes += 16.0 * (double)lp.n_own;
@@ -5925,6 +5870,167 @@ double time_launches(Ctx& c, int iters, F&& launch) {
   return (double)ms / iters;
 }
 
+// a probe's figures: every pass launched once untimed (the first launches), then `iters` launches of each pass timed
+// on their own.  pass(mask) launches the passes in mask (1, 2 or 3)
+template <class F>
+void time_passes(Ctx& c, int iters, int npass, double* ms, F&& pass) {
+  pass(npass == 2 ? 3 : 1);
+  for (int k = 0; k < npass; ++k) ms[k] = time_launches(c, iters, [&] { pass(1 << k); });
+}
+
+// ---- the transport layer's unit operations and probes (Ctx::transport_fields / transport_pairs)
+// Their scratch, slots 14 .. 23 of smp_scratch, by name (22 is pucfem_stroke_apply's).  tot: the doubles of one set
+// of fields, nch x N or, for pairs, 2 N.
+struct TransportSlots {
+  Ctx& c;
+  size_t tot;
+  size_t N() const { return (size_t)c.mesh.N; }
+  double* in() { return c.smp_scratch<double>(14, tot); }
+  double* out() { return c.smp_scratch<double>(15, tot); }
+  int32_t* nfpart() { return c.smp_scratch<int32_t>(16, (size_t)SLB); }
+  double* ch() { return c.smp_scratch<double>(17, tot); }
+  int4* rec() { return c.smp_scratch<int4>(18, N()); }
+  int32_t* marks() { return c.smp_scratch<int32_t>(19, N()); }
+  int32_t* tri() { return c.smp_scratch<int32_t>(20, N()); }
+  int32_t* cnt() { return c.smp_scratch<int32_t>(21, 3 * (size_t)SLB); }
+  int32_t* mid() { return c.smp_scratch<int32_t>(23, 2 * (size_t)SLB); }
+  // the work buffers mode m uses; rows: with the per-row outputs (marks, tri)
+  Ctx::TransportWork work(Ctx::TransportMode m, bool rows) {
+    Ctx::TransportWork w;
+    w.nfpart = nfpart();
+    if (rows) w.marks = marks();
+    if (m.mc()) w.ch = ch(), w.rec = rec(), w.cnt = cnt(), w.tri = rows ? tri() : nullptr;
+    if (m.mid()) w.mid = mid();
+    return w;
+  }
+};
+
+// marks and tri of a unit operation back to the caller (T1 belongs to the two-pass scheme: -1 under a one-pass one)
+void transport_rows_out(Ctx& c, Ctx::TransportMode m, const Ctx::TransportWork& w, int32_t* marks, int32_t* tri) {
+  if (marks) c.get_all(1, 1, marks, w.marks);
+  if (tri && m.mc()) c.get_all(1, 1, tri, w.tri);
+  else if (tri) std::fill(tri, tri + c.mesh.N, -1);
+}
+
+// cout = transport(cin; u, dt) for nch plain fields on the whole mesh.  dnf: the rows' marks go through c.dnotfound
+// (the first-order entry point's not-found flags)
+void advect_fields_unit(Ctx& c, Ctx::TransportMode m, int32_t nch, const double* cin, const double* u, double dt,
+                        double* cout, int32_t* marks, int32_t* tri, bool dnf = false) {
+  c.dye_ready();
+  require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+  require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
+  TransportSlots s{c, (size_t)nch * (size_t)c.mesh.N};
+  double *tu = c.u_scratch(), *din = s.in(), *dout = s.out();
+  Ctx::TransportWork w = s.work(m, !dnf);
+  if (dnf) w.marks = c.dnotfound;
+  c.put_all(1, nch, cin, din);
+  c.put_all(2, 1, u, tu);
+  c.transport_fields(m, 0, c.mesh.N, tu, dt, nullptr, nullptr, nch, din, dout, w);
+  c.get_all(1, nch, cout, dout);
+  transport_rows_out(c, m, w, marks, tri);
+}
+
+// f_out = transport(f; u, dt) for one field of interleaved pairs
+void advect_pairs_unit(Ctx& c, Ctx::TransportMode m, const double* f, const double* u, double dt, double* f_out,
+                       int32_t* marks, int32_t* tri, bool dnf = false) {
+  c.inertia_ready();
+  require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
+  TransportSlots s{c, 2 * (size_t)c.mesh.N};
+  double *tu = c.u_scratch(), *din = s.in(), *dout = s.out();
+  Ctx::TransportWork w = s.work(m, !dnf);
+  if (dnf) w.marks = c.dnotfound;
+  c.put_all(2, 1, f, din);
+  c.put_all(2, 1, u, tu);
+  c.transport_pairs(m, 0, c.mesh.N, tu, dt, din, dout, w);
+  c.get_all(2, 1, f_out, dout);
+  transport_rows_out(c, m, w, marks, tri);
+}
+
+// ms per launch of mode m's passes (ms[1] only under a two-pass scheme) with the context's own u and dt: nch >= 1
+// plain fields of zeros, or (nch = 0) the pairs f = u
+void transport_probe(Ctx& c, Ctx::TransportMode m, int nch, int iters, double* ms) {
+  const i64 N = c.mesh.N;
+  TransportSlots s{c, nch ? (size_t)nch * (size_t)N : 2 * (size_t)N};
+  const Ctx::TransportWork w = s.work(m, false);
+  double *din = nch ? s.in() : nullptr, *dout = s.out();
+  if (nch) HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * s.tot, c.st));
+  time_passes(c, iters, m.mc() ? 2 : 1, ms, [&](int pass) {
+    if (nch) c.transport_fields(m, 0, N, c.ux, c.prm.dt, nullptr, nullptr, nch, din, dout, w, pass);
+    else c.transport_pairs(m, 0, N, c.ux, c.prm.dt, c.ux, dout, w, pass);
+  });
+}
+
+// One transported field of the ensemble -- the velocity of the inertial step, or the dye -- as its MacCormack and
+// midpoint launches see it: the members' flags and how many members are on each, the three flag values that leave the
+// first-order kernel, the MacCormack set's ch and records, the partials, ticket counters and value slots.  The
+// ensemble twin of Ctx::transport_fields / transport_pairs: a new scheme or order is added to ens_transport below
+// (and, with channels, to ens_enqueue_dyes, which takes its reductions from the dye's descriptor).
+struct EnsTransport {
+  const int32_t* on;                 // the members' flags as the kernels read them
+  const int* n;                      // members per flag value
+  int32_t f_mc, f_sl_mid, f_mc_mid;  // the flag values (ENS_ADV_* / ENS_DYE_*)
+  double* ch;                        // the MacCormack set: pass 1's field ...
+  int4* rec;                         // ... and triangles
+  double *mc_part, *trj_part;        // the launches' partials
+  unsigned *mc_cnt, *trj_cnt;        // their ticket counters: pass 1's M, then pass 2's
+  double *v_nf, *v_mc;               // the members' vals: not-found rows; pass 2's rows without T2, clamped values
+  double* t;                         // the members' trj_vals, the field's four slots (null: no part was ever on)
+  size_t sM;
+  int nb_sl;
+  RedOut mc1() const { return {v_nf, nullptr, mc_cnt, 1, 0, 0u}; }
+  RedOut mc2() const { return {v_mc, nullptr, mc_cnt + sM, 2, 0, 0u}; }
+  RedOut trj1() const { return {v_nf, t ? t + ENS_T_MID1 : nullptr, trj_cnt, 2, 0, 0u}; }
+  RedOut trj2() const { return {t + ENS_T_MC, nullptr, trj_cnt + sM, 3, 0, 0u}; }
+  double* mc_part2() const { return mc_part + sM * nb_sl; }
+  double* trj_part2() const { return trj_part + sM * 2 * nb_sl; }
+  bool any_mid() const { return n[f_sl_mid] + n[f_mc_mid] > 0; }
+};
+EnsTransport ens_vel_transport(Ens& e) {
+  const size_t sM = (size_t)e.M;
+  return {e.adv_on_dev, e.vel_n, ENS_ADV_MC, ENS_ADV_SL_MID, ENS_ADV_MC_MID, e.mcv_ch, e.mcv_rec, e.mcv_part, e.trj_part_v,
+          e.mcv_cnt, e.trj_cnt ? e.trj_cnt + 2 * sM : nullptr, e.vals + ENS_V_VEL_NF, e.vals + ENS_V_VEL_MC,
+          e.trj_vals ? e.trj_vals + ENS_TRJ_VEL : nullptr, sM, e.nb_sl};
+}
+EnsTransport ens_dye_transport(Ens& e) {
+  return {e.mc_on_dev, e.dye_n, ENS_DYE_MC, ENS_DYE_SL_MID, ENS_DYE_MC_MID, e.mc_ch, e.mc_rec, e.mc_part, e.trj_part_d,
+          e.mc_cnt, e.trj_cnt, e.vals + ENS_V_DYE_NF, e.vals + ENS_V_DYE_MC,
+          e.trj_vals ? e.trj_vals + ENS_TRJ_DYE : nullptr, (size_t)e.M, e.nb_sl};
+}
+// out = transport(f; u, dt) of the members whose flag left the first-order kernel (which skipped them): MacCormack's
+// two passes, the midpoint trace in one pass straight into out, and with both pass 1 into the set's ch and records,
+// pass 2 into out.  F: dbl2 (the velocity, Ctx::inertia_step per member) or double (the dye without channels,
+// Ctx::dye_transport_step per member).  Pass 1's not-found count goes into v_nf; the sums are the caller's
+template <class F>
+void ens_transport(Ctx& c, Ens& e, const EnsTransport& t, const F* f, F* out) {
+  const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
+  const dim3 grid(e.nb_sl, e.M);
+  const int64_t n = e.n;
+  const double *u = e.u, dt = c.prm.dt, hdt = 0.5 * c.prm.dt;
+  F* ch = reinterpret_cast<F*>(t.ch);
+  hipStream_t st = c.st;
+  if (t.n[t.f_mc] > 0) {
+    hipLaunchKernelGGL(k_ens_mc_fwd<F>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, n, u, dt, t.on, t.f_mc, f, ch,
+                       t.rec, t.mc_part, t.mc1());
+    KCHK();
+    hipLaunchKernelGGL(k_ens_mc_bwd<F>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, n, u, dt, t.on, t.f_mc, f,
+                       (const F*)ch, out, (const int4*)t.rec, t.mc_part2(), t.mc2());
+    KCHK();
+  }
+  if (t.n[t.f_sl_mid] > 0) {
+    hipLaunchKernelGGL(k_ens_trj_fwd<F>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, n, u, dt, hdt, t.on, t.f_sl_mid, f,
+                       out, (int4*)nullptr, t.trj_part, t.trj1());
+    KCHK();
+  }
+  if (t.n[t.f_mc_mid] > 0) {
+    hipLaunchKernelGGL(k_ens_trj_fwd<F>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, n, u, dt, hdt, t.on, t.f_mc_mid, f,
+                       ch, t.rec, t.trj_part, t.trj1());
+    KCHK();
+    hipLaunchKernelGGL(k_ens_trj_bwd<F>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, n, u, dt, hdt, t.on, t.f_mc_mid, f,
+                       (const F*)ch, out, (const int4*)t.rec, t.trj_part2(), t.trj2(), t.v_mc);
+    KCHK();
+  }
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -6527,10 +6633,9 @@ Ens* ens_of(Ctx& c) {
 // with-channels form of the launches ens_enqueue_step makes without channels -- the same buffers, partials, ticket
 // counters and value slots for c, the channels beside it -- then the channels' next set copied into their current
 // set.  Every member is on exactly one flag, so every plane of the next set is written.  rs: k_ens_sl's reduction.
-void ens_enqueue_dyes(Ctx& c, Ens& e, const RedOut& rs, bool dye_alt) {
+void ens_enqueue_dyes(Ctx& c, Ens& e, const EnsTransport& t, const RedOut& rs, bool dye_alt) {
   const i64 n = e.n;
   const int32_t M = e.M, K = e.dy_K;
-  const size_t sM = (size_t)M;
   hipStream_t st = c.st;
   const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
   const dim3 grid(e.nb_sl, M);
@@ -6541,32 +6646,30 @@ void ens_enqueue_dyes(Ctx& c, Ens& e, const RedOut& rs, bool dye_alt) {
                      dt, hdt, on, ENS_DYE_SL, K, cc, dy, e.cn, e.dy_nxt, (int4*)nullptr, wm, e.part_sl, rs);
   KCHK();
   if (e.dye_n[ENS_DYE_MC] > 0) {
-    const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
     hipLaunchKernelGGL(k_ens_dye_fwd<false>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
                        (const double*)e.u, dt, hdt, on, ENS_DYE_MC, K, cc, dy, e.mc_ch, e.dy_ch, e.mc_rec, nowm,
-                       e.mc_part, r1);
+                       e.mc_part, t.mc1());
     KCHK();
-    const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
     hipLaunchKernelGGL(k_ens_dye_bwd<false>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
                        (const double*)e.u, dt, hdt, on, ENS_DYE_MC, K, cc, (const double*)e.mc_ch, dy,
-                       (const double*)e.dy_ch, e.cn, e.dy_nxt, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2,
+                       (const double*)e.dy_ch, e.cn, e.dy_nxt, (const int4*)e.mc_rec, t.mc_part2(), t.mc2(),
                        (double*)nullptr);
     KCHK();
   }
-  const RedOut t1{e.vals + 4, e.trj_vals + ENS_TRJ_DYE, e.trj_cnt, 2, 0, 0u};
   if (e.dye_n[ENS_DYE_SL_MID] > 0) {
     hipLaunchKernelGGL(k_ens_dye_fwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
-                       dt, hdt, on, ENS_DYE_SL_MID, K, cc, dy, e.cn, e.dy_nxt, (int4*)nullptr, nowm, e.trj_part_d, t1);
+                       dt, hdt, on, ENS_DYE_SL_MID, K, cc, dy, e.cn, e.dy_nxt, (int4*)nullptr, nowm, e.trj_part_d,
+                       t.trj1());
     KCHK();
   }
   if (e.dye_n[ENS_DYE_MC_MID] > 0) {
     hipLaunchKernelGGL(k_ens_dye_fwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
-                       dt, hdt, on, ENS_DYE_MC_MID, K, cc, dy, e.mc_ch, e.dy_ch, e.mc_rec, nowm, e.trj_part_d, t1);
+                       dt, hdt, on, ENS_DYE_MC_MID, K, cc, dy, e.mc_ch, e.dy_ch, e.mc_rec, nowm, e.trj_part_d,
+                       t.trj1());
     KCHK();
-    const RedOut t2{e.trj_vals + ENS_TRJ_DYE + 1, nullptr, e.trj_cnt + sM, 3, 0, 0u};
     hipLaunchKernelGGL(k_ens_dye_bwd<true>, grid, dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n, (const double*)e.u,
                        dt, hdt, on, ENS_DYE_MC_MID, K, cc, (const double*)e.mc_ch, dy, (const double*)e.dy_ch, e.cn,
-                       e.dy_nxt, (const int4*)e.mc_rec, e.trj_part_d + sM * 2 * e.nb_sl, t2, e.vals + 11);
+                       e.dy_nxt, (const int4*)e.mc_rec, t.trj_part2(), t.trj2(), t.v_mc);
     KCHK();
   }
   const int64_t count = (int64_t)M * K * n;
@@ -6631,57 +6734,14 @@ void ens_enqueue_step(Ctx& c) {
     KCHK();
   }
   if (adv) {
-    const RedOut ra{e.vals + 10, nullptr, e.cnt_adv, 1, 0, 0u};
+    const RedOut ra{e.vals + ENS_V_VEL_NF, nullptr, e.cnt_adv, 1, 0, 0u};
     hipLaunchKernelGGL(k_ens_sl_vel, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
                        c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, e.ua,
                        e.part_adv, ra);
     KCHK();
-    // with at least one inertial member's velocity scheme on: u_a = MC(u^n; u^n, dt) of those members (flag ENS_ADV_MC,
-    // which k_ens_sl_vel skips) into their planes of ua -- Ctx::inertia_step's mc_vel_launch
-    if (e.vel_n[ENS_ADV_MC] > 0) {
-      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
-      const dbl2* f = reinterpret_cast<const dbl2*>(e.u);
-      const size_t sM = (size_t)M;
-      const RedOut r1{e.vals + 10, nullptr, e.mcv_cnt, 1, 0, 0u};
-      hipLaunchKernelGGL(k_ens_mc_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                         (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC, f,
-                         reinterpret_cast<dbl2*>(e.mcv_ch), e.mcv_rec, e.mcv_part, r1);
-      KCHK();
-      const RedOut r2{e.vals + 13, nullptr, e.mcv_cnt + sM, 2, 0, 0u};
-      hipLaunchKernelGGL(k_ens_mc_bwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                         (const double*)e.u, c.prm.dt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC, f,
-                         reinterpret_cast<const dbl2*>(e.mcv_ch), reinterpret_cast<dbl2*>(e.ua),
-                         (const int4*)e.mcv_rec, e.mcv_part + sM * e.nb_sl, r2);
-      KCHK();
-    }
-    // with at least one inertial member's velocity part on: u_a along the midpoint trace of those members (flags
-    // ENS_ADV_SL_MID / ENS_ADV_MC_MID, which the launches above skip) -- Ctx::inertia_step's trj_vel_launch.  One pass
-    // straight into their planes of ua; with MacCormack pass 1 into the set's ch and records, pass 2 into ua
-    if (e.vel_n[ENS_ADV_SL_MID] > 0 || e.vel_n[ENS_ADV_MC_MID] > 0) {
-      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
-      const dbl2* f = reinterpret_cast<const dbl2*>(e.u);
-      const size_t sM = (size_t)M;
-      const double hdt = 0.5 * c.prm.dt;
-      const RedOut r1{e.vals + 10, e.trj_vals + ENS_TRJ_VEL, e.trj_cnt + 2 * sM, 2, 0, 0u};
-      if (e.vel_n[ENS_ADV_SL_MID] > 0) {
-        hipLaunchKernelGGL(k_ens_trj_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_SL_MID, f,
-                           reinterpret_cast<dbl2*>(e.ua), (int4*)nullptr, e.trj_part_v, r1);
-        KCHK();
-      }
-      if (e.vel_n[ENS_ADV_MC_MID] > 0) {
-        hipLaunchKernelGGL(k_ens_trj_fwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC_MID, f,
-                           reinterpret_cast<dbl2*>(e.mcv_ch), e.mcv_rec, e.trj_part_v, r1);
-        KCHK();
-        const RedOut r2{e.trj_vals + ENS_TRJ_VEL + 1, nullptr, e.trj_cnt + 3 * sM, 3, 0, 0u};
-        hipLaunchKernelGGL(k_ens_trj_bwd<dbl2>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                           (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.adv_on_dev, ENS_ADV_MC_MID, f,
-                           reinterpret_cast<const dbl2*>(e.mcv_ch), reinterpret_cast<dbl2*>(e.ua),
-                           (const int4*)e.mcv_rec, e.trj_part_v + sM * 2 * e.nb_sl, r2, e.vals + 13);
-        KCHK();
-      }
-    }
+    // the inertial members whose velocity moves by MacCormack, along the midpoint trace or both (flags ENS_ADV_MC,
+    // ENS_ADV_SL_MID, ENS_ADV_MC_MID, which k_ens_sl_vel skips): u_a of those members into their planes of ua
+    ens_transport(c, e, ens_vel_transport(e), reinterpret_cast<const dbl2*>(e.u), reinterpret_cast<dbl2*>(e.ua));
   }
   // with at least one member forced: r = base + dt * f of those members behind it (Ctx::force_step), and the viscous
   // product stages r for them.  c holds c^n: k_ens_mix2 of the previous step wrote it earlier in this chain
@@ -6704,7 +6764,7 @@ void ens_enqueue_step(Ctx& c) {
   KCHK();
   // max |div| into vals slot `slot`; with rhs the pressure right-hand side and its sum (slot 9)
   auto div = [&](const double* u, int slot, bool rhs) {
-    const RedOut r{e.vals + slot, rhs ? e.vals + 9 : nullptr, e.cnt, rhs ? 2 : 1, 0, 1u};
+    const RedOut r{e.vals + slot, rhs ? e.vals + ENS_V_BSUM : nullptr, e.cnt, rhs ? 2 : 1, 0, 1u};
     with_c16(A, [&](auto c16) {
       hipLaunchKernelGGL(k_ens_div<decltype(c16)::value>, dim3(e.nb_div, M), dim3(BS), 0, st, A.view(),
                          (const double*)c.dGx, (const double*)c.dGy, u, (const double*)c.das1, (const double*)c.dmp,
@@ -6718,7 +6778,7 @@ void ens_enqueue_step(Ctx& c) {
                        (const int32_t*)c.dmaster_of, (const double*)e.vals, 1.0 / (double)c.n_free, pout);
     KCHK();
   };
-  div(e.us, 0, true);
+  div(e.us, ENS_V_DIV_STAR, true);
   pres(e.p);
   const int nbg = (int)std::max<i64>(1, std::min<i64>(1024, (A.nslices * 64 + BS - 1) / BS));
   with_c16(A, [&](auto c16) {
@@ -6728,7 +6788,7 @@ void ens_enqueue_step(Ctx& c) {
                        (const int32_t*)c.dspos, (const double*)e.dval, (int64_t)e.dstride);
   });
   KCHK();
-  div(e.u, 8, true);  // (its maximum is not recorded: the scratch slot)
+  div(e.u, ENS_V_SCRATCH, true);  // (its maximum is not recorded)
   pres(e.p2);
   with_c16(A, [&](auto c16) {
     hipLaunchKernelGGL(k_ens_grad_proj1<decltype(c16)::value>, dim3(c.nb_mg(A.nslices), M), dim3(BS), 0, st, A.view(),
@@ -6736,70 +6796,34 @@ void ens_enqueue_step(Ctx& c) {
                        (const uint8_t*)c.ddir, e.u);
   });
   KCHK();
-  div(e.u, 1, false);
+  div(e.u, ENS_V_FINAL_DIV, false);
   if (c.scheme == PUCFEM_STOKES_COLOR) {
-    const RedOut rs{e.vals + 2, nullptr, e.cnt + M, 3, 0, 0u};
+    const RedOut rs{e.vals + ENS_V_SL, nullptr, e.cnt + M, 3, 0, 0u};
     // (a member whose dye flag is not 0 moves its dye below: by MacCormack, along the midpoint trace, or both)
     const bool dye_alt = e.dye_n[ENS_DYE_MC] + e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0;
     // with dye channels (pucfem_ens_set_dyes): the with-channels kernels move c and the channels of every member from
     // one locate per pass and row, in place of the launches below up to the sums
+    const EnsTransport td = ens_dye_transport(e);
     if (e.dy_K > 0)
-      ens_enqueue_dyes(c, e, rs, dye_alt);
+      ens_enqueue_dyes(c, e, td, rs, dye_alt);
     else
       hipLaunchKernelGGL(k_ens_sl, dim3(e.nb_sl, M), dim3(BS), 0, st, MeshDev{c.mx, c.my, c.mtri, c.mesh.T}, c.lgrid,
                          c.cgrid, (int64_t)n, (const double*)e.u, c.prm.dt, (const double*)e.c, e.cn,
                          (const double*)c.dwmix, e.part_sl, rs,
                          dye_alt ? (const int32_t*)e.mc_on_dev : (const int32_t*)nullptr);
     KCHK();
-    // with at least one member's dye scheme on: cn = MC(c; u, dt) of those members (which k_ens_sl skipped), pass 1's
-    // not-found count into slot 4 and the single path's k_wsum sums into slots 2 and 3 -- Ctx::mc_dye_step /
-    // mc_dye_reduce
+    // the members whose dye left k_ens_sl: cn by MacCormack, along the midpoint trace or both, the final locate's
+    // not-found count (pass 1's under MacCormack) into ENS_V_DYE_NF and the single path's k_wsum sums into ENS_V_SL
+    // (Ctx::dye_transport_step / dye_transport_reduce)
     if (dye_alt) {
-      const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
-      const size_t sM = (size_t)M;
-      if (e.dy_K == 0 && e.dye_n[ENS_DYE_MC] > 0) {
-        const RedOut r1{e.vals + 4, nullptr, e.mc_cnt, 1, 0, 0u};
-        hipLaunchKernelGGL(k_ens_mc_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                           (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c, e.mc_ch,
-                           e.mc_rec, e.mc_part, r1);
-        KCHK();
-        const RedOut r2{e.vals + 11, nullptr, e.mc_cnt + sM, 2, 0, 0u};
-        hipLaunchKernelGGL(k_ens_mc_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                           (const double*)e.u, c.prm.dt, (const int32_t*)e.mc_on_dev, 1, (const double*)e.c,
-                           (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec, e.mc_part + sM * e.nb_sl, r2);
-        KCHK();
-      }
-      // with at least one member's dye part on: cn along the midpoint trace of those members (flags ENS_DYE_SL_MID /
-      // ENS_DYE_MC_MID) -- Ctx::trj_dye_step.  One pass straight into cn; with MacCormack pass 1 into the set's ch and
-      // records, pass 2 into cn.  The final locate's count into slot 4, the sums by k_ens_wsum below
-      if (e.dy_K == 0 && e.dye_n[ENS_DYE_SL_MID] + e.dye_n[ENS_DYE_MC_MID] > 0) {
-        const double hdt = 0.5 * c.prm.dt;
-        const RedOut t1{e.vals + 4, e.trj_vals + ENS_TRJ_DYE, e.trj_cnt, 2, 0, 0u};
-        if (e.dye_n[ENS_DYE_SL_MID] > 0) {
-          hipLaunchKernelGGL(k_ens_trj_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_SL_MID,
-                             (const double*)e.c, e.cn, (int4*)nullptr, e.trj_part_d, t1);
-          KCHK();
-        }
-        if (e.dye_n[ENS_DYE_MC_MID] > 0) {
-          hipLaunchKernelGGL(k_ens_trj_fwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_MC_MID,
-                             (const double*)e.c, e.mc_ch, e.mc_rec, e.trj_part_d, t1);
-          KCHK();
-          const RedOut t2{e.trj_vals + ENS_TRJ_DYE + 1, nullptr, e.trj_cnt + sM, 3, 0, 0u};
-          hipLaunchKernelGGL(k_ens_trj_bwd<double>, dim3(e.nb_sl, M), dim3(BS), 0, st, Mh, c.lgrid, c.cgrid, (int64_t)n,
-                             (const double*)e.u, c.prm.dt, hdt, (const int32_t*)e.mc_on_dev, ENS_DYE_MC_MID,
-                             (const double*)e.c, (const double*)e.mc_ch, e.cn, (const int4*)e.mc_rec,
-                             e.trj_part_d + sM * 2 * e.nb_sl, t2, e.vals + 11);
-          KCHK();
-        }
-      }
-      const RedOut rw{e.vals + 2, nullptr, e.mc_cnt + 2 * sM, 2, 0, 0u};
+      if (e.dy_K == 0) ens_transport(c, e, td, (const double*)e.c, e.cn);
+      const RedOut rw{e.vals + ENS_V_SL, nullptr, e.mc_cnt + 2 * (size_t)M, 2, 0, 0u};
+
       hipLaunchKernelGGL(k_ens_wsum, dim3(e.nb_ws, M), dim3(BS), 0, st, (int64_t)n, (const int32_t*)e.mc_on_dev,
                          (const double*)e.cn, (const double*)c.dwmix, e.mc_part_ws, rw);
       KCHK();
     }
-    const RedOut rm{e.vals + 5, nullptr, e.cnt + 2 * (size_t)M, 1, 0, 0u};
+    const RedOut rm{e.vals + ENS_V_MIX, nullptr, e.cnt + 2 * (size_t)M, 1, 0, 0u};
     hipLaunchKernelGGL(k_ens_mix2, dim3(e.nb_mix, M), dim3(BS), 0, st, (int64_t)n, (const double*)e.cn,
                        (const double*)c.dwmix, (const double*)e.vals, e.part_mx, rm, e.c);
     KCHK();
@@ -6807,14 +6831,14 @@ void ens_enqueue_step(Ctx& c) {
     // with at least one member's diffusion on: the BROWN instantiation of the same launch (which members walk, and
     // with what amplitude and key, the kernel reads from device memory)
     const MeshDev Mh{c.mx, c.my, c.mtri, c.mesh.T};
-    const RedOut rt{e.vals + 6, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
+    const RedOut rt{e.vals + ENS_V_EATEN, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
     auto launch = [&](auto brown, auto eb) {
       constexpr bool B = decltype(brown)::value;
       if (e.trjt_any > 0) {
         // with at least one member's tracer part on: the MID instantiation of the same launch (which members take the
         // midpoint the kernel reads from device memory); the members' fell-back counts beside the eaten counts
         const EnsMid em{(const int32_t*)e.trj_trc_dev, 0.5 * c.prm.dt, e.trj_vals + ENS_TRJ_FELL};
-        const RedOut rm{e.vals + 6, e.trj_vals + ENS_TRJ_FELL, e.cnt + 3 * (size_t)M, 2, 0, 0u};
+        const RedOut rm{e.vals + ENS_V_EATEN, e.trj_vals + ENS_TRJ_FELL, e.cnt + 3 * (size_t)M, 2, 0, 0u};
         if (e.nb_tr > 1)
           hipLaunchKernelGGL((k_ens_tracer_cloud<B, true>), dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
                              (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
@@ -7032,6 +7056,17 @@ int pucfem_ens_info(void* ctx, int64_t* out4) {
 namespace {
 // the members' inertia flags as the kernels read them: ENS_ADV_MC where the member's velocity scheme is MacCormack,
 // ENS_ADV_SL_MID / ENS_ADV_MC_MID where its velocity part is on (pucfem_ens_set_trajectory)
+// a member's (scheme, order) as one of the four flag values {SL, MC, SL_MID, MC_MID} of its field; counts the
+// MacCormack members into mc_any and the members per flag into n
+int32_t ens_mode_flag(const std::vector<int32_t>& scheme, const std::vector<int32_t>& order, size_t m,
+                      const int32_t (&flag)[4], int& mc_any, int* n) {
+  const bool mc = !scheme.empty() && scheme[m] != PUCFEM_ADV_SL;
+  const bool mid = !order.empty() && order[m] == PUCFEM_TRJ_MIDPOINT;
+  const int32_t f = flag[(mid ? 2 : 0) + (mc ? 1 : 0)];
+  mc_any += mc ? 1 : 0;
+  ++n[f];
+  return f;
+}
 void ens_adv_upload(Ctx& c, Ens& e) {
   const size_t sM = (size_t)e.M;
   e.adv_any = (int)std::count(e.adv_on.begin(), e.adv_on.end(), 1);
@@ -7040,13 +7075,9 @@ void ens_adv_upload(Ctx& c, Ens& e) {
   if (!e.adv_on_dev) return;
   std::vector<int32_t> f(sM, ENS_ADV_OFF);
   for (size_t m = 0; m < sM; ++m)
-    if (e.adv_on[m]) {
-      const bool mc = !e.mc_vel.empty() && e.mc_vel[m] != PUCFEM_ADV_SL;
-      const bool mid = !e.trj_vel.empty() && e.trj_vel[m] == PUCFEM_TRJ_MIDPOINT;
-      f[m] = mid ? (mc ? ENS_ADV_MC_MID : ENS_ADV_SL_MID) : (mc ? ENS_ADV_MC : ENS_ADV_SL);
-      e.mc_vel_any += mc ? 1 : 0;
-      ++e.vel_n[f[m]];
-    }
+    if (e.adv_on[m])
+      f[m] = ens_mode_flag(e.mc_vel, e.trj_vel, m, {ENS_ADV_SL, ENS_ADV_MC, ENS_ADV_SL_MID, ENS_ADV_MC_MID}, e.mc_vel_any,
+                           e.vel_n);
   c.h2d(e.adv_on_dev, f.data(), sizeof(int32_t) * sM);
   HIPCHK(hipStreamSynchronize(c.st));
 }
@@ -7067,13 +7098,9 @@ void ens_dye_upload(Ctx& c, Ens& e) {
   e.mc_dye_any = 0;
   for (int& k : e.dye_n) k = 0;
   std::vector<int32_t> f(sM, ENS_DYE_SL);
-  for (size_t m = 0; m < sM; ++m) {
-    const bool mc = !e.mc_dye.empty() && e.mc_dye[m] != PUCFEM_ADV_SL;
-    const bool mid = !e.trj_dye.empty() && e.trj_dye[m] == PUCFEM_TRJ_MIDPOINT;
-    f[m] = mid ? (mc ? ENS_DYE_MC_MID : ENS_DYE_SL_MID) : (mc ? ENS_DYE_MC : ENS_DYE_SL);
-    e.mc_dye_any += mc ? 1 : 0;
-    ++e.dye_n[f[m]];
-  }
+  for (size_t m = 0; m < sM; ++m)
+    f[m] = ens_mode_flag(e.mc_dye, e.trj_dye, m, {ENS_DYE_SL, ENS_DYE_MC, ENS_DYE_SL_MID, ENS_DYE_MC_MID}, e.mc_dye_any,
+                         e.dye_n);
   if (!e.mc_on_dev) return;
   c.h2d(e.mc_on_dev, f.data(), sizeof(int32_t) * sM);
   HIPCHK(hipStreamSynchronize(c.st));
@@ -7107,7 +7134,7 @@ int pucfem_ens_set_inertia(void* ctx, int32_t member, int32_t on) {
       changed = true;
       if (v) {  // (switched on: its counts start again, as pucfem_set_inertia's do)
         e.adv_steps[m] = 0;
-        HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 10, 0, sizeof(double), c.st));
+        HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + ENS_V_VEL_NF, 0, sizeof(double), c.st));
         e.adv_stale = true;
       }
     }
@@ -7131,7 +7158,7 @@ int pucfem_ens_inertia_info(void* ctx, int32_t member, int64_t* out4) {
     }
     out4[0] = have ? e.adv_on[m] : 0;
     out4[1] = have ? e.adv_steps[m] : 0;
-    out4[2] = have ? (int64_t)std::llround(e.adv_vals[ENS_VALS * m + 10]) : 0;
+    out4[2] = have ? (int64_t)std::llround(e.adv_vals[ENS_VALS * m + ENS_V_VEL_NF]) : 0;
     out4[3] = (int64_t)e.adv_bytes;
   });
 }
@@ -7151,45 +7178,42 @@ int pucfem_ens_set_advection(void* ctx, int32_t member, int32_t what, int32_t sc
     const size_t sM = (size_t)e.M, sn = (size_t)e.n;
     const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
     const size_t before = e.bytes;
+    // one field: its set's buffers at the first switch-on, the members' schemes, and for a member switched on its
+    // counts anew (as pucfem_set_advection's do)
+    auto part = [&](std::vector<int32_t>& sch, std::vector<int64_t>& steps, int slot, auto&& bufs) {
+      if (sch.empty()) {
+        if (!scheme) return false;  // (nothing was ever on: nothing is allocated until now)
+        bufs();
+        sch.assign(sM, 0);
+        steps.assign(sM, 0);
+      }
+      bool changed = false;
+      for (size_t m = m0; m < m1; ++m) {
+        if (sch[m] == scheme) continue;
+        sch[m] = scheme;
+        changed = true;
+        if (scheme) {
+          steps[m] = 0;
+          HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + slot, 0, 2 * sizeof(double), c.st));
+        }
+      }
+      return changed;
+    };
     bool up_dye = false, up_vel = false;
-    if (what & PUCFEM_ADV_DYE) {
-      if (e.mc_dye.empty() && scheme) {  // (nothing was ever on: nothing is allocated until now)
+    if (what & PUCFEM_ADV_DYE)
+      up_dye = part(e.mc_dye, e.mc_steps, ENS_V_DYE_MC, [&] {
         e.mc_ch = e.alloc<double>(sM * sn, c.st);
         e.mc_rec = e.alloc<int4>(sM * sn, c.st);
         e.mc_part = e.alloc<double>(sM * 3 * e.nb_sl, c.st);
         ens_dye_flag_bufs(c, e);
-        e.mc_dye.assign(sM, 0);
-        e.mc_steps.assign(sM, 0);
-      }
-      for (size_t m = m0; m < m1 && !e.mc_dye.empty(); ++m) {
-        if (e.mc_dye[m] == scheme) continue;
-        e.mc_dye[m] = scheme;
-        up_dye = true;
-        if (scheme) {  // (switched on: its counts start again, as pucfem_set_advection's do)
-          e.mc_steps[m] = 0;
-          HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 11, 0, 2 * sizeof(double), c.st));
-        }
-      }
-    }
-    if (what & PUCFEM_ADV_VELOCITY) {
-      if (e.mc_vel.empty() && scheme) {
+      });
+    if (what & PUCFEM_ADV_VELOCITY)
+      up_vel = part(e.mc_vel, e.mcv_steps, ENS_V_VEL_MC, [&] {
         e.mcv_ch = e.alloc<double>(sM * 2 * sn, c.st);
         e.mcv_rec = e.alloc<int4>(sM * sn, c.st);
         e.mcv_part = e.alloc<double>(sM * 3 * e.nb_sl, c.st);
         e.mcv_cnt = e.alloc<unsigned>(2 * sM, c.st);
-        e.mc_vel.assign(sM, 0);
-        e.mcv_steps.assign(sM, 0);
-      }
-      for (size_t m = m0; m < m1 && !e.mc_vel.empty(); ++m) {
-        if (e.mc_vel[m] == scheme) continue;
-        e.mc_vel[m] = scheme;
-        up_vel = true;
-        if (scheme) {
-          e.mcv_steps[m] = 0;
-          HIPCHK(hipMemsetAsync(e.vals + ENS_VALS * m + 13, 0, 2 * sizeof(double), c.st));
-        }
-      }
-    }
+      });
     e.mc_bytes += e.bytes - before;
     if (up_dye) ens_dye_upload(c, e);
     if (up_dye) ens_dye_ch_fit(c, e);  // (with dye channels: the set's ch of the channels)
@@ -7220,14 +7244,14 @@ int pucfem_ens_advection_info(void* ctx, int32_t member, int64_t* out11) {
     out11[3] = vel ? e.mcv_steps[m] : 0;
     // (the counts of the member's last MacCormack launch while its scheme is on; 0 before the first and once it is off)
     if (out11[0] && out11[2] > 0) {
-      out11[4] = val(4);
-      out11[5] = val(11);
-      out11[6] = val(12);
+      out11[4] = val(ENS_V_DYE_NF);
+      out11[5] = val(ENS_V_DYE_MC);
+      out11[6] = val(ENS_V_DYE_MC + 1);
     }
     if (out11[1] && out11[3] > 0 && !e.adv_on.empty() && e.adv_on[m]) {
-      out11[7] = val(10);
-      out11[8] = val(13);
-      out11[9] = val(14);
+      out11[7] = val(ENS_V_VEL_NF);
+      out11[8] = val(ENS_V_VEL_MC);
+      out11[9] = val(ENS_V_VEL_MC + 1);
     }
     out11[10] = (int64_t)e.mc_bytes;
   });
@@ -7322,8 +7346,8 @@ int pucfem_ens_trajectory_info(void* ctx, int32_t member, int64_t* out10) {
     out10[4] = vel ? e.trjv_steps[m] : 0;
     out10[5] = trc ? e.trjt_steps[m] : 0;
     // (of the member's last launch with the part on, as pucfem_trajectory_info: with MacCormack both passes count)
-    out10[6] = val(ENS_TRJ_DYE) + (!e.mc_dye.empty() && e.mc_dye[m] ? val(ENS_TRJ_DYE + 3) : 0);
-    out10[7] = val(ENS_TRJ_VEL) + (!e.mc_vel.empty() && e.mc_vel[m] ? val(ENS_TRJ_VEL + 3) : 0);
+    out10[6] = val(ENS_TRJ_DYE + ENS_T_MID1) + (!e.mc_dye.empty() && e.mc_dye[m] ? val(ENS_TRJ_DYE + ENS_T_MID2) : 0);
+    out10[7] = val(ENS_TRJ_VEL + ENS_T_MID1) + (!e.mc_vel.empty() && e.mc_vel[m] ? val(ENS_TRJ_VEL + ENS_T_MID2) : 0);
     out10[8] = val(ENS_TRJ_FELL);
     out10[9] = (int64_t)e.trj_bytes;
   });
@@ -7510,7 +7534,7 @@ int pucfem_ens_dyes_info(void* ctx, int32_t member, int64_t* out4) {
     out4[2] = 0;
     if (e.dy_K > 0 && e.dy_steps[m] > 0) {  // (the count of the member's last dye launch: pass 1's, slot 4)
       double v = 0.0;
-      c.d2h(&v, e.vals + ENS_VALS * m + 4, sizeof(double));
+      c.d2h(&v, e.vals + ENS_VALS * m + ENS_V_DYE_NF, sizeof(double));
       out4[2] = (int64_t)std::llround(v);
     }
     out4[3] = (int64_t)e.dy_bytes;
@@ -7679,22 +7703,19 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     }
     HIPCHK(hipStreamSynchronize(c.st));
     e.steps += nsteps;
-    if (e.adv_any > 0) {
-      for (size_t m = 0; m < sM; ++m)
-        if (e.adv_on[m]) e.adv_steps[m] += nsteps;
-      e.adv_stale = true;
-    }
-    for (size_t m = 0; m < sM && e.mc_dye_any > 0; ++m)
-      if (e.mc_dye[m]) e.mc_steps[m] += nsteps;
-    for (size_t m = 0; m < sM && e.mc_vel_any > 0; ++m)
-      if (e.mc_vel[m] && e.adv_on[m]) e.mcv_steps[m] += nsteps;
-    if (e.mc_dye_any > 0 || e.mc_vel_any > 0) e.adv_stale = true;
-    for (size_t m = 0; m < sM && !e.trj_dye.empty(); ++m)
-      if (e.trj_dye[m] == PUCFEM_TRJ_MIDPOINT) e.trjd_steps[m] += nsteps;
-    for (size_t m = 0; m < sM && !e.trj_vel.empty() && e.adv_any > 0; ++m)
-      if (e.trj_vel[m] == PUCFEM_TRJ_MIDPOINT && e.adv_on[m]) e.trjv_steps[m] += nsteps;
-    for (size_t m = 0; m < sM && !e.trj_trc.empty(); ++m)
-      if (e.trj_trc[m] == PUCFEM_TRJ_MIDPOINT) e.trjt_steps[m] += nsteps;
+    // the members' step counts: a setting that was never switched on has empty vectors; the velocity's count only
+    // while the member's inertia is on
+    auto count = [&](std::vector<int64_t>& steps, const std::vector<int32_t>& setting, int32_t on, bool inertial) {
+      for (size_t m = 0; m < setting.size(); ++m)
+        if (setting[m] == on && (!inertial || (!e.adv_on.empty() && e.adv_on[m]))) steps[m] += nsteps;
+    };
+    count(e.adv_steps, e.adv_on, 1, false);
+    count(e.mc_steps, e.mc_dye, PUCFEM_ADV_MACCORMACK, false);
+    count(e.mcv_steps, e.mc_vel, PUCFEM_ADV_MACCORMACK, true);
+    if (e.adv_any > 0 || e.mc_dye_any > 0 || e.mc_vel_any > 0) e.adv_stale = true;
+    count(e.trjd_steps, e.trj_dye, PUCFEM_TRJ_MIDPOINT, false);
+    count(e.trjv_steps, e.trj_vel, PUCFEM_TRJ_MIDPOINT, true);
+    count(e.trjt_steps, e.trj_trc, PUCFEM_TRJ_MIDPOINT, false);
     if (e.trj_vals) e.trj_stale = e.adv_stale = true;
     for (size_t m = 0; m < sM && e.force_any > 0; ++m)
       if (e.fmask[m]) e.fsteps[m] += nsteps;
@@ -8649,23 +8670,7 @@ int pucfem_dyes_mixing(void* ctx, double* out) {
 
 int pucfem_sl_advect_multi(void* ctx, int32_t nch, const double* cin, const double* u, double dt, double* cout,
                            int32_t* notfound) {
-  return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
-    c.dye_ready();
-    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
-    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    const size_t tot = (size_t)nch * (size_t)N;
-    double *tx = c.u_scratch(), *ty = tx + 1;
-    double* din = c.smp_scratch<double>(14, tot);
-    double* dout = c.smp_scratch<double>(15, tot);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    c.put_all(1, nch, cin, din);
-    c.put_all(2, 1, u, tx);
-    c.dye_launch(0, N, tx, ty, dt, nch, din, dout, c.dnotfound, dpart);
-    c.get_all(1, nch, cout, dout);
-    if (notfound) c.get_all(1, 1, notfound, c.dnotfound);
-  });
+  return guard(ctx, [&] { advect_fields_unit(*C(ctx), {}, nch, cin, u, dt, cout, notfound, nullptr, true); });
 }
 
 int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2) {
@@ -8674,16 +8679,8 @@ int pucfem_dyes_probe(void* ctx, int32_t nch, int32_t iters, double* out2) {
     c.dye_ready();
     require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
     require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
-    const i64 N = c.mesh.N;
-    const size_t tot = (size_t)nch * (size_t)N;
-    double* din = c.smp_scratch<double>(14, tot);
-    double* dout = c.smp_scratch<double>(15, tot);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
-    auto launch = [&] { c.dye_launch(0, N, c.ux, c.uy, c.prm.dt, nch, din, dout, nullptr, dpart); };
-    launch();  // (untimed: the first launch)
-    out2[0] = time_launches(c, iters, launch);
-    out2[1] = c.dye_launch_bytes(nch, N);
+    transport_probe(c, {}, nch, iters, out2);
+    out2[1] = c.dye_launch_bytes(nch, c.mesh.N);
   });
 }
 
@@ -8708,21 +8705,7 @@ int pucfem_inertia_info(void* ctx, int64_t* out4) {
 }
 
 int pucfem_sl_advect_vel(void* ctx, const double* f, const double* u, double dt, double* f_out, int32_t* notfound) {
-  return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
-    c.inertia_ready();
-    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    double* tu = c.u_scratch();
-    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
-    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    c.put_all(2, 1, f, din);
-    c.put_all(2, 1, u, tu);
-    c.vel_launch(0, N, tu, dt, din, dout, c.dnotfound, dpart);
-    c.get_all(2, 1, f_out, dout);
-    if (notfound) c.get_all(1, 1, notfound, c.dnotfound);
-  });
+  return guard(ctx, [&] { advect_pairs_unit(*C(ctx), {}, f, u, dt, f_out, notfound, nullptr, true); });
 }
 
 int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2) {
@@ -8730,13 +8713,8 @@ int pucfem_inertia_probe(void* ctx, int32_t iters, double* out2) {
     Ctx& c = *C(ctx);
     c.inertia_ready();
     require(iters >= 1 && out2 != nullptr, "iters < 1 or null output");
-    const i64 N = c.mesh.N;
-    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    auto launch = [&] { c.vel_launch(0, N, c.ux, c.prm.dt, c.ux, dout, nullptr, dpart); };
-    launch();  // (untimed: the first launch)
-    out2[0] = time_launches(c, iters, launch);
-    out2[1] = c.vel_launch_bytes(N);
+    transport_probe(c, {}, 0, iters, out2);
+    out2[1] = c.vel_launch_bytes(c.mesh.N);
   });
 }
 
@@ -9169,53 +9147,14 @@ int pucfem_advection_info(void* ctx, int64_t* out11) {
 int pucfem_sl_advect_mc(void* ctx, int32_t nch, const double* cin, const double* u, double dt, double* cout,
                         int32_t* marks, int32_t* tri) {
   return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
-    c.dye_ready();
-    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
-    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    const size_t tot = (size_t)nch * (size_t)N;
-    double *tx = c.u_scratch(), *ty = tx + 1;
-    double* din = c.smp_scratch<double>(14, tot);
-    double* dout = c.smp_scratch<double>(15, tot);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    double* dch = c.smp_scratch<double>(17, tot);
-    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
-    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
-    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    c.put_all(1, nch, cin, din);
-    c.put_all(2, 1, u, tx);
-    c.mc_fwd(0, N, tx, ty, dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr);
-    c.mc_bwd(0, N, tx, ty, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt);
-    c.get_all(1, nch, cout, dout);
-    if (marks) c.get_all(1, 1, marks, dmark);
-    if (tri) c.get_all(1, 1, tri, dtri);
+    advect_fields_unit(*C(ctx), {PUCFEM_ADV_MACCORMACK, PUCFEM_TRJ_EULER}, nch, cin, u, dt, cout, marks, tri);
   });
 }
 
 int pucfem_sl_advect_vel_mc(void* ctx, const double* f, const double* u, double dt, double* f_out, int32_t* marks,
                             int32_t* tri) {
   return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
-    c.inertia_ready();
-    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    double* tu = c.u_scratch();
-    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
-    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
-    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
-    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
-    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    c.put_all(2, 1, f, din);
-    c.put_all(2, 1, u, tu);
-    c.mc_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt);
-    c.get_all(2, 1, f_out, dout);
-    if (marks) c.get_all(1, 1, marks, dmark);
-    if (tri) c.get_all(1, 1, tri, dtri);
+    advect_pairs_unit(*C(ctx), {PUCFEM_ADV_MACCORMACK, PUCFEM_TRJ_EULER}, f, u, dt, f_out, marks, tri);
   });
 }
 
@@ -9227,39 +9166,11 @@ int pucfem_advection_probe(void* ctx, int32_t what, int32_t nch, int32_t iters, 
     else c.inertia_ready();
     require(iters >= 1 && out4 != nullptr, "iters < 1 or null output");
     const i64 N = c.mesh.N;
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    if (what == PUCFEM_ADV_DYE) {
-      require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
-      const size_t tot = (size_t)nch * (size_t)N;
-      double* din = c.smp_scratch<double>(14, tot);
-      double* dout = c.smp_scratch<double>(15, tot);
-      double* dch = c.smp_scratch<double>(17, tot);
-      HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
-      auto p1 = [&] { c.mc_fwd(0, N, c.ux, c.uy, c.prm.dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr); };
-      auto p2 = [&] {
-        c.mc_bwd(0, N, c.ux, c.uy, c.prm.dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, nullptr, nullptr,
-                 dcnt);
-      };
-      p1();  // (untimed: the first launches)
-      p2();
-      out4[0] = time_launches(c, iters, p1);
-      out4[1] = time_launches(c, iters, p2);
-      out4[2] = c.mc_bytes1(nch, N);
-      out4[3] = c.mc_bytes2(nch, N);
-    } else {
-      double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-      double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
-      auto pass = [&](int which) {
-        c.mc_vel_launch(0, N, c.ux, c.prm.dt, c.ux, dch, dout, drec, nullptr, nullptr, dpart, dcnt, which);
-      };
-      pass(3);  // (untimed: the first launches)
-      out4[0] = time_launches(c, iters, [&] { pass(1); });
-      out4[1] = time_launches(c, iters, [&] { pass(2); });
-      out4[2] = c.mcv_bytes1(N);
-      out4[3] = c.mcv_bytes2(N);
-    }
+    const bool dye = what == PUCFEM_ADV_DYE;
+    if (dye) require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    transport_probe(c, {PUCFEM_ADV_MACCORMACK, PUCFEM_TRJ_EULER}, dye ? nch : 0, iters, out4);
+    out4[2] = dye ? c.mc_bytes1(nch, N) : c.mcv_bytes1(N);
+    out4[3] = dye ? c.mc_bytes2(nch, N) : c.mcv_bytes2(N);
   });
 }
 
@@ -9302,86 +9213,16 @@ void trj_check(int32_t order, int32_t scheme) {
 int pucfem_sl_advect_traj(void* ctx, int32_t order, int32_t scheme, int32_t nch, const double* cin, const double* u,
                           double dt, double* cout, int32_t* marks, int32_t* tri) {
   return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
     trj_check(order, scheme);
-    c.dye_ready();
-    require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
-    require(cin != nullptr && u != nullptr && cout != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    const size_t tot = (size_t)nch * (size_t)N;
-    const bool mc = scheme == PUCFEM_ADV_MACCORMACK, mid = order == PUCFEM_TRJ_MIDPOINT;
-    double *tx = c.u_scratch(), *ty = tx + 1;
-    double* din = c.smp_scratch<double>(14, tot);
-    double* dout = c.smp_scratch<double>(15, tot);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    double* dch = mc ? c.smp_scratch<double>(17, tot) : nullptr;
-    int4* drec = mc ? c.smp_scratch<int4>(18, (size_t)N) : nullptr;
-    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
-    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
-    c.put_all(1, nch, cin, din);
-    c.put_all(2, 1, u, tx);
-    if (mid) {
-      c.trj_fwd(0, N, tx, dt, nullptr, nullptr, nch, din, mc ? dch : dout, drec, dmark, dpart, nullptr, dmid);
-      if (mc)
-        c.trj_bwd(0, N, tx, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt, dmid + SLB);
-    } else if (mc) {
-      c.mc_fwd(0, N, tx, ty, dt, nullptr, nullptr, nch, din, dch, drec, dpart, nullptr);
-      c.mc_bwd(0, N, tx, ty, dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, dmark, dtri, dcnt);
-    } else {
-      c.dye_launch(0, N, tx, ty, dt, nch, din, dout, dmark, dpart);
-    }
-    c.get_all(1, nch, cout, dout);
-    if (marks) c.get_all(1, 1, marks, dmark);
-    if (tri) {
-      if (mc) {
-        c.get_all(1, 1, tri, dtri);
-      } else {
-        for (i64 i = 0; i < N; ++i) tri[i] = -1;  // (T1 belongs to the two-pass scheme)
-      }
-    }
+    advect_fields_unit(*C(ctx), {scheme, order}, nch, cin, u, dt, cout, marks, tri);
   });
 }
 
 int pucfem_sl_advect_vel_traj(void* ctx, int32_t order, int32_t scheme, const double* f, const double* u, double dt,
                               double* f_out, int32_t* marks, int32_t* tri) {
   return guard(ctx, [&] {
-    Ctx& c = *C(ctx);
     trj_check(order, scheme);
-    c.inertia_ready();
-    require(f != nullptr && u != nullptr && f_out != nullptr, "null fields");
-    const i64 N = c.mesh.N;
-    const bool mc = scheme == PUCFEM_ADV_MACCORMACK, mid = order == PUCFEM_TRJ_MIDPOINT;
-    double* tu = c.u_scratch();
-    double* din = c.smp_scratch<double>(14, 2 * (size_t)N);
-    double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    double* dch = mc ? c.smp_scratch<double>(17, 2 * (size_t)N) : nullptr;
-    int4* drec = mc ? c.smp_scratch<int4>(18, (size_t)N) : nullptr;
-    int32_t* dmark = c.smp_scratch<int32_t>(19, (size_t)N);
-    int32_t* dtri = c.smp_scratch<int32_t>(20, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
-    c.put_all(2, 1, f, din);
-    c.put_all(2, 1, u, tu);
-    if (mid) {
-      if (mc) c.trj_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt, dmid);
-      else c.trj_vel_launch(0, N, tu, dt, din, dout, nullptr, nullptr, dmark, nullptr, dpart, nullptr, dmid, 1);
-    } else if (mc) {
-      c.mc_vel_launch(0, N, tu, dt, din, dch, dout, drec, dmark, dtri, dpart, dcnt);
-    } else {
-      c.vel_launch(0, N, tu, dt, din, dout, dmark, dpart);
-    }
-    c.get_all(2, 1, f_out, dout);
-    if (marks) c.get_all(1, 1, marks, dmark);
-    if (tri) {
-      if (mc) {
-        c.get_all(1, 1, tri, dtri);
-      } else {
-        for (i64 i = 0; i < N; ++i) tri[i] = -1;
-      }
-    }
+    advect_pairs_unit(*C(ctx), {scheme, order}, f, u, dt, f_out, marks, tri);
   });
 }
 
@@ -9394,50 +9235,12 @@ int pucfem_trajectory_probe(void* ctx, int32_t what, int32_t scheme, int32_t nch
     else c.inertia_ready();
     require(iters >= 1 && out4 != nullptr, "iters < 1 or null output");
     const i64 N = c.mesh.N;
-    const bool mc = scheme == PUCFEM_ADV_MACCORMACK;
-    int32_t* dpart = c.smp_scratch<int32_t>(16, (size_t)SLB);
-    int4* drec = c.smp_scratch<int4>(18, (size_t)N);
-    int32_t* dcnt = c.smp_scratch<int32_t>(21, 3 * (size_t)SLB);
-    int32_t* dmid = c.smp_scratch<int32_t>(23, 2 * (size_t)SLB);
+    const bool dye = what == PUCFEM_TRJ_DYE, mc = scheme == PUCFEM_ADV_MACCORMACK;
     out4[0] = out4[1] = out4[2] = out4[3] = 0.0;
-    if (what == PUCFEM_TRJ_DYE) {
-      require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
-      const size_t tot = (size_t)nch * (size_t)N;
-      double* din = c.smp_scratch<double>(14, tot);
-      double* dout = c.smp_scratch<double>(15, tot);
-      double* dch = c.smp_scratch<double>(17, tot);
-      HIPCHK(hipMemsetAsync(din, 0, sizeof(double) * tot, c.st));
-      auto p1 = [&] {
-        c.trj_fwd(0, N, c.ux, c.prm.dt, nullptr, nullptr, nch, din, dch, mc ? drec : nullptr, nullptr, dpart, nullptr,
-                  dmid);
-      };
-      auto p2 = [&] {
-        c.trj_bwd(0, N, c.ux, c.prm.dt, nullptr, nullptr, nullptr, nch, din, dch, dout, drec, nullptr, nullptr, dcnt,
-                  dmid + SLB);
-      };
-      p1();  // (untimed: the first launches)
-      out4[0] = time_launches(c, iters, p1);
-      out4[2] = c.trj_bytes1(nch, N, mc);
-      if (mc) {
-        p2();
-        out4[1] = time_launches(c, iters, p2);
-        out4[3] = c.trj_bytes2(nch, N);
-      }
-    } else {
-      double* dout = c.smp_scratch<double>(15, 2 * (size_t)N);
-      double* dch = c.smp_scratch<double>(17, 2 * (size_t)N);
-      auto pass = [&](int which) {
-        c.trj_vel_launch(0, N, c.ux, c.prm.dt, c.ux, dch, dout, mc ? drec : nullptr, nullptr, nullptr, dpart, dcnt, dmid,
-                         which);
-      };
-      pass(mc ? 3 : 1);  // (untimed: the first launches)
-      out4[0] = time_launches(c, iters, [&] { pass(1); });
-      out4[2] = c.trjv_bytes1(N, mc);
-      if (mc) {
-        out4[1] = time_launches(c, iters, [&] { pass(2); });
-        out4[3] = c.trjv_bytes2(N);
-      }
-    }
+    if (dye) require(nch >= 1 && nch <= DYE_MAX, "nch must be in 1 .. PUCFEM_MAX_DYES (16)");
+    transport_probe(c, {scheme, PUCFEM_TRJ_MIDPOINT}, dye ? nch : 0, iters, out4);
+    out4[2] = dye ? c.trj_bytes1(nch, N, mc) : c.trjv_bytes1(N, mc);
+    if (mc) out4[3] = dye ? c.trj_bytes2(nch, N) : c.trjv_bytes2(N);
   });
 }
 

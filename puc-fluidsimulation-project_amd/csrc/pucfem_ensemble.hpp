@@ -39,6 +39,24 @@ constexpr int32_t ENS_DYE_SL = 0, ENS_DYE_MC = 1, ENS_DYE_SL_MID = 2, ENS_DYE_MC
 // rows without midpoint; 4..7 the same of the last velocity launch (5 / 6 copied into vals 13 / 14); 8 the tracers of
 // the last launch that fell back to their Euler step
 constexpr int ENS_TRJ_DYE = 0, ENS_TRJ_VEL = 4, ENS_TRJ_FELL = 8;
+// The slots above by name, for the host code that places reductions and reads counts (no kernel reads these names).
+// ENS_V_*: a member's vals; ENS_T_*: within the dye's or the velocity's four slots of its trj_vals.
+enum : int {
+  ENS_V_DIV_STAR = 0,   // max |div u*|
+  ENS_V_FINAL_DIV = 1,  // max |final div|
+  ENS_V_SL = 2,         // sum wc, sum w (and k_ens_sl's not-found rows behind them)
+  ENS_V_DYE_NF = 4,     // not-found rows of the last dye launch
+  ENS_V_MIX = 5,        // the mixing variance
+  ENS_V_EATEN = 6,      // tracers eaten
+  ENS_V_SCRATCH = 8,    // a maximum that is not recorded
+  ENS_V_BSUM = 9,       // sum(braw)
+  ENS_V_VEL_NF = 10,    // not-found rows of the last inertial launch
+  ENS_V_DYE_MC = 11,    // rows without T2, clamped values: the last MacCormack dye launch
+  ENS_V_VEL_MC = 13,    // ... velocity launch
+  ENS_T_MID1 = 0,       // rows without pass 1's midpoint
+  ENS_T_MC = 1,         // pass 2's rows without T2, clamped values
+  ENS_T_MID2 = 3,       // rows without pass 2's midpoint
+};
 
 // the member's reduction: the launch's RedOut template moved to the member's values, counter and partials
 // (NP partial arrays of gridDim.x blocks per member)

@@ -326,6 +326,39 @@ def test_chain_composition():
         sim.close()
 
 
+def test_mixed_dye_and_velocity_flags():
+    """Four inertial members on mesh.1 with K = 2 (the blob and the smooth field), every dye flag and every velocity
+    flag present in one ensemble and no member with the same mode for both, two steps (the second reads the swapped
+    sets): every member against its own StokesSimulation bit for bit -- fields, channels, u_a, records and counts."""
+    mesh = pf.load_mesh("mesh1")
+    P = channels(mesh)[1:]
+    dye = [(SL, EULER), (MC, EULER), (SL, MID), (MC, MID)]
+    vel = [(MC, MID), (SL, MID), (MC, EULER), (SL, EULER)]
+    ens = flagged_ensemble(mesh, COLOR[:4], dye, P, inertia=True, velocity_advection=[v[0] for v in vel],
+                           velocity_trajectory=[v[1] for v in vel])
+    try:
+        st = ens.step(2)
+        for m in range(4):
+            sim = make_single(mesh, color_bc(COLOR[m]), P, *dye[m], inertia=True)
+            try:
+                sim.velocity_advection, sim.velocity_trajectory = vel[m]
+                ref = single_result(sim, sim.step(2))
+                assert same_fields(member_snapshot(ens, m), ref["at"]) == [], m
+                assert same_stats(st, m, ref["st"]) == [], m
+                adv_m = ens.advection_info(m)
+                check_counts("mixed", m, adv_m, ens.trajectory_info(m), ens.dyes_info(m), ref)
+                if vel[m][0] == MC:
+                    assert adv_m["velocity_steps"] == ref["adv"]["velocity_steps"] == 2, m
+                    assert tuple(adv_m["velocity_counts"]) == tuple(ref["adv"]["velocity_counts"]), (m, adv_m)
+                assert np.array_equal(ens.get(L.F_U_ADV, 2, m), sim.u_advected), m
+            finally:
+                sim.close()
+        d = ens.dyes
+        assert not np.array_equal(d[0], d[1]) and not np.array_equal(d[2], d[3])
+    finally:
+        ens.close()
+
+
 # ---- 5. switching
 def test_flags_changed_mid_run():
     """step(5), two members' scheme and trajectory changed with channels present, step(8): every member equals a single

@@ -1,7 +1,9 @@
 """One sha256 per C entry point that moves caller-numbered arrays, on fixed seeded inputs (compare two builds bit for
 bit: run once per PUCFEM_LIB_VARIANT, each run in a process of its own, and diff the outputs).  mesh1 takes the dense
-small-mesh path, fine refined once the SELL / lattice / multigrid paths; timings are not hashed.
+small-mesh path, fine refined once the SELL / lattice / multigrid paths; timings are not hashed.  The transport
+sections cover the four (scheme, order) modes: unit operations, two-step runs with their counts, and ensembles.
   python tools/entry_hash.py > profiles/entry_hash.txt"""
+import ctypes as ct
 import hashlib
 import os
 import sys
@@ -168,6 +170,101 @@ def ens_inertia(tag, mesh, rng):
     ens.close()
 
 
+MODES = (("sl", "euler"), ("maccormack", "euler"), ("sl", "midpoint"), ("maccormack", "midpoint"))
+
+
+def transport_units(tag, sim, rng):
+    """the transport layer's unit operations: the four (scheme, order) modes x {1 field, 3 fields, pairs} through the
+    _traj entry points, and the first-order and MacCormack entry points themselves"""
+    isim = S.StokesSimulation(sim.mesh, S.SquirmerBC(), 0.05, "color", 0,
+                              None if tag == "mesh1" else S.Tolerances.production(), inertia=True)
+    ctx, N, Lc = isim.ctx, sim.mesh.N, isim.ctx.L
+    u = np.ascontiguousarray(0.3 * rng.standard_normal((N, 2)))
+    f = np.ascontiguousarray(rng.standard_normal((N, 2)))
+    C = {k: np.ascontiguousarray(rng.random((k, N))) for k in (1, 3)}
+    marks, tri = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+    for scheme, order in MODES:
+        a, o = S.advection_scheme(scheme), S.trajectory_order(order)
+        for k, cin in C.items():
+            out = np.zeros((k, N))
+            L.check(Lc.pucfem_sl_advect_traj(ctx.h, o, a, k, L.dptr(cin), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks),
+                                             L.iptr(tri)), ctx.h)
+            line(tag, f"sl_advect_traj {scheme} {order} {k}", out, marks, tri)
+        out = np.zeros((N, 2))
+        L.check(Lc.pucfem_sl_advect_vel_traj(ctx.h, o, a, L.dptr(f), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks),
+                                             L.iptr(tri)), ctx.h)
+        line(tag, f"sl_advect_vel_traj {scheme} {order}", out, marks, tri)
+    for k, cin in C.items():
+        out = np.zeros((k, N))
+        L.check(Lc.pucfem_sl_advect_multi(ctx.h, k, L.dptr(cin), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks)), ctx.h)
+        line(tag, f"sl_advect_multi {k}", out, marks)
+        L.check(Lc.pucfem_sl_advect_mc(ctx.h, k, L.dptr(cin), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks), L.iptr(tri)),
+                ctx.h)
+        line(tag, f"sl_advect_mc {k}", out, marks, tri)
+    out = np.zeros((N, 2))
+    L.check(Lc.pucfem_sl_advect_vel(ctx.h, L.dptr(f), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks)), ctx.h)
+    line(tag, "sl_advect_vel", out, marks)
+    L.check(Lc.pucfem_sl_advect_vel_mc(ctx.h, L.dptr(f), L.dptr(u), 0.05, L.dptr(out), L.iptr(marks), L.iptr(tri)), ctx.h)
+    line(tag, "sl_advect_vel_mc", out, marks, tri)
+    isim.close()
+
+
+def info_ints(fn, h, n, *member):
+    o = (ct.c_int64 * n)()
+    L.check(fn(h, *member, o), h)
+    return np.array(list(o), dtype=np.int64)
+
+
+def transport_runs(tag, mesh, rng):
+    """two inertial steps beside three dye channels under each mode (the second step reads the swapped sets), with
+    the counts and the launch and byte counters"""
+    dyes, c0 = rng.random((3, mesh.N)), rng.random(mesh.N)
+    for scheme, order in MODES:
+        sim = S.StokesSimulation(mesh, S.SquirmerBC(), 0.05, "color", 0,
+                                 None if tag == "mesh1" else S.Tolerances.production(), inertia=True, advection=scheme,
+                                 trajectory=order)
+        sim.c = c0
+        sim.dyes = dyes
+        n0, b0 = sim.ctx.counters()
+        sim.step(2)
+        n1, b1 = sim.ctx.counters()
+        ctx = sim.ctx
+        line(tag, f"run {scheme} {order}", sim.u, sim.c, sim.dyes, sim.u_advected)
+        line(tag, f"run {scheme} {order} info", info_ints(ctx.L.pucfem_advection_info, ctx.h, 11),
+             info_ints(ctx.L.pucfem_trajectory_info, ctx.h, 10), info_ints(ctx.L.pucfem_dyes_info, ctx.h, 4),
+             np.array([n1 - n0], dtype=np.int64), np.array([b1 - b0]))
+        sim.close()
+
+
+def transport_ensembles(tag, mesh, rng):
+    """colour ensembles of five members whose dye flags cover the four modes and whose velocity flags cover them on
+    four inertial members (one member without inertia), without and with two channels; one food ensemble with one
+    member's tracers on the midpoint"""
+    b2 = (0.0, -5.0, 5.0, -2.0, 2.0)
+    bcs = [S.SquirmerBC(B1=-2.0, B2=b, nu=1.0) for b in b2]
+    dsch, dord = ["sl", "maccormack", "sl", "maccormack", "maccormack"], ["euler", "euler", "midpoint", "midpoint", "euler"]
+    vsch, vord = ["maccormack", "sl", "maccormack", "sl", "sl"], ["midpoint", "midpoint", "euler", "euler", "euler"]
+    c0, d0 = rng.random((5, mesh.N)), rng.random((5, 2, mesh.N))
+    for K in (0, 2):
+        ens = S.StokesEnsemble(mesh, bcs, 0.01, "color", inertia=[True, True, True, True, False], dye_advection=dsch,
+                               velocity_advection=vsch, dye_trajectory=dord, velocity_trajectory=vord,
+                               dyes=d0 if K else None)
+        ens.set(L.F_C, c0)
+        ens.step(2)
+        h, Lc = ens.ctx.h, ens.ctx.L
+        info = [a for m in range(5) for a in (info_ints(Lc.pucfem_ens_advection_info, h, 11, m)[:10],
+                                              info_ints(Lc.pucfem_ens_trajectory_info, h, 10, m)[:9])]
+        line(tag, f"ens transport K={K}", ens.u, ens.c, *[ens.get(L.F_U_ADV, 2, m) for m in range(4)],
+             *([ens.dyes] if K else []), *info)
+        ens.close()
+    ens = S.StokesEnsemble(mesh, bcs[:3], 0.01, "food", tracers=0.2 + 0.6 * rng.random((40, 2)),
+                           tracer_trajectory=["euler", "midpoint", "euler"])
+    ens.step(2)
+    info = [info_ints(ens.ctx.L.pucfem_ens_trajectory_info, ens.ctx.h, 10, m)[:9] for m in range(3)]
+    line(tag, "ens transport food", ens.u, ens.tracers, ens.tracer_status, ens.capture_step, *info)
+    ens.close()
+
+
 def main():
     print("# library variant:", os.environ.get("PUCFEM_LIB_VARIANT", "default"), file=sys.stderr)
     for tag, mesh in (("mesh1", pf.load_mesh("mesh1")), ("fine1", pf.load_mesh("fine", refine=1))):
@@ -179,7 +276,10 @@ def main():
                     lambda: (ensemble if small else mg_pieces)(tag, mesh, rng),
                     lambda: inertia(tag, mesh, rng),
                     # (ensembles take the dense small-mesh path: beside fine1, mesh_fine unrefined)
-                    lambda: ens_inertia(tag, mesh, rng) if small else ens_inertia("fine", pf.load_mesh("fine"), rng)]
+                    lambda: ens_inertia(tag, mesh, rng) if small else ens_inertia("fine", pf.load_mesh("fine"), rng),
+                    lambda: transport_units(tag, sim, rng), lambda: transport_runs(tag, mesh, rng),
+                    lambda: (transport_ensembles(tag, mesh, rng) if small
+                             else transport_ensembles("fine", pf.load_mesh("fine"), rng))]
         for k, section in enumerate(sections):  # (a refusal ends its section and is recorded by its message)
             try:
                 section()
