@@ -923,6 +923,13 @@ int pucfem_bench_dir(void* ctx, int32_t variant, int32_t nblocks, int32_t iters,
    kernel + 16*F: F untimed launches of a coarse level's smoother follow every timed launch
    (ms_batch then includes them; ms_each still times the kernel's own launches) */
 int pucfem_bench_kernel(void* ctx, int32_t kernel, int32_t iters, double* ms_batch, double* ms_each, double* bytes);
+/* timing of the pressure projection's two basis passes outside the step (tools/proj_bench.py), at the first
+   pressure solve's current basis size m and in the step's form (a pending direction, the right-hand side formed in
+   the multi-dot pass); the context's state is not changed (outputs go to scratch).  Each kernel is launched once
+   untimed, then `iters` times between two events: out6[0] / [1] = ms per launch of k_mdot2<m> / k_pcomb<m'>,
+   [2] / [3] = their algorithmic bytes per launch, [4] = m, [5] = m' = min(m, capacity - 1).  Needs a multigrid
+   context with a pressure projection basis, else PUCFEM_EINVAL; meant to be called after steps. */
+int pucfem_proj_probe(void* ctx, int32_t iters, double* out6);
 /* timing and pixel bookkeeping of pucfem_raster's kernel (tools/raster_bench.py; arguments as pucfem_raster,
    the image stays on the device): out4[0] = ms per launch of `iters` back-to-back launches between two events
    (after one untimed launch), [1] = pixels no triangle holds, [2] = pixels the lattice locator answers with the

@@ -9988,4 +9988,43 @@ int pucfem_bench_kernel(void* ctx, int32_t kernel, int32_t iters, double* ms_bat
   });
 }
 
+// the pressure projection's two basis passes outside the step (tools/proj_bench.py): k_mdot2 and k_pcomb at the
+// first pressure solve's current basis size, in the step's form (a pending direction with an accumulated v, the
+// right-hand side formed in the multi-dot pass).  Outputs go to scratch (a CG work vector, the re-seed target, the
+// k_reduce-layout partials), so the context's state stays as it was
+int pucfem_proj_probe(void* ctx, int32_t iters, double* out6) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.need_dev();
+    c.need_built();
+    require(c.use_mg && c.proj_k > 0 && c.projX[1] && c.pv[1] && c.braw && iters > 0,
+            "proj_probe needs a multigrid context with a pressure projection basis");
+    const i64 n = c.lp.n_own;
+    const int m = c.proj_m[1], mp = std::min(m, c.proj_k - 1);
+    const int nb = Ctx::grid_ew(n);
+    double* tmp = c.cg_q[0];
+    const PendDir pd{nullptr, (const double*)c.proj_x0[1], (const double*)c.cg_r[0], (const double*)c.pv[1]};
+    const RhsIn rin{c.braw, c.dslave_of, c.redbuf + 24, 1.0 / (double)c.n_free, tmp};
+    double ms[2];
+    time_passes(c, iters, 2, ms, [&](int mask) {
+      if (mask & 1)
+        hipLaunchKernelGGL(mdot2_kernel(m), dim3(nb), dim3(BS), 0, c.st, (int64_t)n, (const ProjT*)c.projX[1],
+                           (int64_t)c.pld(1), (const double*)c.bh, (const double*)c.pav[1], (const double*)c.pv[1],
+                           (const int32_t*)c.dmaster_of, c.proj_part, RedOut{}, pd, rin);
+      if (mask & 2)
+        hipLaunchKernelGGL(pcomb_kernel(mp), dim3(nb), dim3(BS), 0, c.st, (int64_t)n, (const ProjT*)c.projX[1],
+                           (int64_t)c.pld(1), (const double*)c.proj_coef, (const double*)c.pv[1],
+                           (const int32_t*)c.dmaster_of, c.projXalt[1] + c.pcol(1, mp), tmp, (double*)nullptr,
+                           (const double*)nullptr, (double*)nullptr);
+      KCHK();
+    });
+    out6[0] = ms[0];
+    out6[1] = ms[1];
+    out6[2] = (4.0 * m + 44.0) * (double)n;   // X, braw, slave_of, master_of, r0, r_final, v read; b written
+    out6[3] = (4.0 * mp + 24.0) * (double)n;  // X, v, master_of read; the new direction and the guess written
+    out6[4] = m;
+    out6[5] = mp;
+  });
+}
+
 }  // extern "C"

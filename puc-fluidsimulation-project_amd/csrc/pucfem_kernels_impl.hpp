@@ -744,7 +744,11 @@ using ProjT = float;
 
 // Basis layout: tiles of 64 rows, inside a tile each of the basis' kcap vectors holds 64 consecutive values --
 // element (i, r) at ((r / 64) kcap + i) 64 + r % 64, ld = kcap: a wave's 64 rows of all vectors are one contiguous
-// block (one DRAM stream instead of one per vector), a new vector's 64 values one 256-B segment
+// block (one DRAM stream instead of one per vector), a new vector's 64 values one 256-B segment.
+// The three passes over the basis (k_mdot2, k_pcomb, k_reseed) read it with non-temporal loads: every value is read
+// once per pass and the basis is far larger than the L2 and the Infinity Cache, so lines kept of it only evict the
+// pass's fp64 vectors (tools/proj_lab.hip, profiles/proj_lab.txt: k_pcomb -12 .. -15 %, k_mdot2 -5 .. -7 % at the
+// L7 size, the same bits; 16-byte loads from a grouped layout and a prefetched next row did not pay)
 __host__ __device__ __forceinline__ int64_t pxi(int i, int64_t r, int64_t ld) {
   return (((r >> 6) * ld + i) << 6) + (r & 63);
 }
@@ -767,7 +771,7 @@ __global__ __launch_bounds__(BS) void k_reseed(int64_t n, const ProjT* __restric
 #pragma unroll
     for (int i = 0; i < PROJ_KEEP_MAX; ++i) acc[i] = 0.0;
     for (int j = 0; j < m; ++j) {
-      const double x = (double)X[pxi(j, r, ld)];
+      const double x = (double)ldnt(X + pxi(j, r, ld));
 #pragma unroll
       for (int i = 0; i < PROJ_KEEP_MAX; ++i) acc[i] += q[i * PROJ_MAX + j] * x;
     }
@@ -821,24 +825,35 @@ __global__ __launch_bounds__(BS) void k_mdot2(int64_t n, const ProjT* __restrict
 #pragma unroll
   for (int i = 0; i < NA; ++i) acc[i] = 0.0;
   for (int64_t r = (int64_t)blockIdx.x * BS + threadIdx.x; r < n; r += step) {
+    // every operand of the row is loaded before its first use and before the row's store (which the loads behind
+    // it could not pass): the row map and the right-hand side's operands unconditionally, where the row's branches
+    // took one memory round trip each (master_of, then braw and slave_of) before the basis loads were issued.
+    // The values and the operations on them are the same (profiles/proj_lab.txt: -8 % at 31 directions)
+    const int32_t mo = master_of ? master_of[r] : 0;
+    const double b0 = R.braw ? R.braw[r] : b[r];
+    const int32_t so = R.braw ? R.slave_of[r] : -1;
+    const double a0 = av[r];
+    const double f0 = D.rf ? D.rf[r] : 0.0;
+    const double v0 = D.v ? D.v[r] : (D.y ? D.y[r] : (v ? v[r] : 0.0));  // (all null: v = 0)
+    const double v1 = !D.v && D.y ? D.x0[r] : 0.0;
+    ProjT x[M > 0 ? M : 1];
+#pragma unroll
+    for (int i = 0; i < M; ++i) x[i] = ldnt(X + pxi(i, r, ld));
     double br;
     if (R.braw) {  // (k_pres_rhs's row)
-      if (master_of[r] >= 0) {
+      if (mo >= 0) {
         br = 0.0;
       } else {
-        br = R.braw[r];
-        if (R.slave_of[r] >= 0) br += R.braw[R.slave_of[r]];
+        br = b0;
+        if (so >= 0) br += R.braw[so];
         br = br - mean;
       }
       stnt(R.bh + r, br);
     } else {
-      br = b[r];
+      br = b0;
     }
-    const double ar = D.rf ? av[r] - D.rf[r] : av[r];
-    const double vr = D.v ? D.v[r] : (D.y ? D.y[r] - D.x0[r] : (v ? v[r] : 0.0));  // (all null: v = 0)
-    ProjT x[M > 0 ? M : 1];
-#pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = X[pxi(i, r, ld)];
+    const double ar = D.rf ? a0 - f0 : a0;
+    const double vr = !D.v && D.y ? v0 - v1 : v0;
 #pragma unroll
     for (int i = 0; i < M; ++i) {
       acc[i] += (double)x[i] * br;
@@ -846,7 +861,7 @@ __global__ __launch_bounds__(BS) void k_mdot2(int64_t n, const ProjT* __restrict
     }
     acc[2 * M] += vr * br;
     acc[2 * M + 1] += vr * ar;
-    if (master_of && master_of[r] < 0) {
+    if (master_of && mo < 0) {
       acc[2 * M + 2] += vr;
       acc[2 * M + 3] += br;
     }
@@ -916,7 +931,7 @@ __global__ __launch_bounds__(BS) void k_pcomb(int64_t n, const ProjT* __restrict
   for (int64_t r = (int64_t)blockIdx.x * BS + threadIdx.x; r < n; r += (int64_t)gridDim.x * BS) {
     ProjT x[M > 0 ? M : 1];
 #pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = X[pxi(i, r, ld)];
+    for (int i = 0; i < M; ++i) x[i] = ldnt(X + pxi(i, r, ld));
     const double vr = yp ? yp[r] - x0[r] : (v ? v[r] : 0.0);  // (both null: v = 0)
     double sa = 0.0, sc = 0.0;
 #pragma unroll

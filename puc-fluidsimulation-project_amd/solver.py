@@ -599,6 +599,12 @@ class Context:
                     pending_pressure_directions=bool(o[7] & 64),
                     single_reduction_pcg=bool(o[7] & 128))
 
+    def proj_probe(self, iters=20):
+        """The pressure projection's two basis passes timed outside the step (pucfem_proj_probe); the state stays."""
+        o = (ct.c_double * 6)()
+        self._c(self.L.pucfem_proj_probe(self.h, int(iters), o))
+        return dict(mdot2_ms=o[0], pcomb_ms=o[1], mdot2_bytes=o[2], pcomb_bytes=o[3], m=int(o[4]), m_pcomb=int(o[5]))
+
     def visc_interval(self):
         """[lo, hi] of the viscous Chebyshev iteration (pucfem_visc_interval)."""
         o = (ct.c_double * 2)()
