@@ -160,6 +160,12 @@ enum pucfem_field {
   /* channel k is field PUCFEM_F_DYE0 + k (N values, k < K) */
   PUCFEM_F_DYE0 = 64
 };
+/* Fields added since count on from PUCFEM_F_U_RHS in an enumeration of their own (the numbers of pucfem_field above
+   are closed: 0 .. 16 and the channels from 64).
+   PUCFEM_F_DEFGRAD (17): the tracers' deformation gradient F (n_tr,4) row-major, F00 F01 F10 F11 per tracer, see
+   "tracer stretching" below.  Read and set (count = 4 * n_tr; setting it resumes a run and leaves the stretch step
+   count alone); PUCFEM_ESTATE while stretching is off. */
+enum pucfem_field_more { PUCFEM_F_DEFGRAD = PUCFEM_F_U_RHS + 1 };
 #define PUCFEM_MAX_DYES 16
 
 /* operators for pucfem_apply / pucfem_solve / pucfem_host_get_csr */
@@ -561,6 +567,65 @@ int pucfem_get_tracer_diffusion(void* ctx, int32_t member /* -1 = the context */
    dt), launched once untimed and then `iters` times back to back between two events; the tracers move.
    out2[0]: milliseconds per launch; out2[1]: tracers. */
 int pucfem_tracer_probe(void* ctx, double dt, int32_t iters, double* out2);
+
+/* ---- tracer stretching: the deformation gradient and the FTLE per tracer ---- */
+/* The dye's mixing index is mostly the interpolation's diffusion.  The diffusion-free measure of mixing is the
+   stretching of material lines: the deformation gradient F = dPhi/dX of the flow map along each tracer's path, its
+   largest singular value, and the finite-time Lyapunov exponent built from it.  The velocity is P1, so its gradient is
+   constant per triangle and the tracer step is piecewise affine in the tracer's position: the update below is the
+   exact Jacobian of the discrete step.  With stretching on, every tracer whose iteration of the tracer launch runs
+   carries a row F00 F01 F10 F11 of F (n_tr x 4, row-major, the identity at first).  Every product and sum is as
+   written, in double, without contraction.
+   Per tracer and tracer step: the tracer is at p in triangle t; (ax, bx) are the plane coefficients of ux in t
+   (ux = ax x + bx y + cx there), (ay, by) those of uy -- the values the interpolation of the velocity forms.
+     Euler step          J00 = 1 + dt*ax   J01 = dt*bx   J10 = dt*ay   J11 = 1 + dt*by
+     midpoint step (pucfem_set_trajectory, PUCFEM_TRJ_TRACERS), the midpoint found in triangle tm with the
+     coefficients (cx, dx) of ux and (cy, dy) of uy there; hdt = 0.5 * dt from the host:
+                         A00 = 1 + hdt*ax  A01 = hdt*bx  A10 = hdt*ay  A11 = 1 + hdt*by
+                         B00 = cx*A00 + dx*A10   B01 = cx*A01 + dx*A11
+                         B10 = cy*A00 + dy*A10   B11 = cy*A01 + dy*A11
+                         J00 = 1 + dt*B00  J01 = dt*B01  J10 = dt*B10  J11 = 1 + dt*B11
+     midpoint not found (the tracer fell back to its Euler step): the Euler J
+     then                F00' = J00*F00 + J01*F10   F01' = J00*F01 + J01*F11
+                         F10' = J10*F00 + J11*F10   F11' = J10*F01 + J11*F11
+   A tracer without a velocity (outside the mesh, or not finite): all four entries become NaN, as its position does.
+   The periodic wrap in x has unit Jacobian; the Brownian increment does not depend on p, so its Jacobian is the
+   identity: neither changes F.  With Brownian food F is the Jacobian of the drift map only: the wall reflection would
+   negate the second row, which changes no singular value, and is not applied.  An absorbed tracer (status 1, D > 0)
+   skips its iteration, so its F freezes with it; with D = 0 an eaten tracer keeps moving and its F keeps evolving.
+   Stretching only reads the path: positions, status, capture steps, eaten and fell-back counts are those of the run
+   without it, bit for bit; with it off the step is the step without this call, launch for launch.
+   pucfem_set_tracer_stretch governs pucfem_step, pucfem_tracer_step and pucfem_tracer_probe of a single-rank
+   PUCFEM_STOKES_FOOD context with tracers.  Switching it on allocates F as the identity and sets the stretch step
+   count to 0; switching it off frees F.  Setting PUCFEM_F_TRACERS resets F to the identity and the count to 0; setting
+   PUCFEM_F_STATUS or PUCFEM_F_DEFGRAD leaves both alone.  PUCFEM_ESTATE -- decided before the device is asked for --
+   on multi-rank contexts (their tracer step is another pair of kernels), heat, Poisson and PUCFEM_STOKES_COLOR
+   contexts (no tracers) and before the build; PUCFEM_ESTATE on a context whose tracer set is empty, while the context
+   has an ensemble (for on and off alike), and for pucfem_ens_create while it is on: members carry their own flags.
+   PUCFEM_ENODEV on a host-only context.  pucfem_build_operators and pucfem_ctx_destroy switch it off.  A small-mesh
+   context steps uncaptured while it is on.  Not done: F along pucfem_streamlines, multi-rank contexts. */
+int pucfem_set_tracer_stretch(void* ctx, int32_t on);
+/* The same per ensemble member (member = -1: every member), off at first.  A member whose flag is on is bit for bit
+   in F a pucfem_step run with its settings and the flag on; everything else of every member is the ensemble without
+   this call.  The members' F (members x n_tr x 4, identity rows for a member that is off), their flags and the
+   summary's buffers are allocated when a member is first switched on, counted in pucfem_ens_info's bytes and freed
+   with the ensemble.  Switching a member on or off sets its rows to the identity and its count to 0; so does setting
+   its tracers.  The step stays one captured chain, the STRETCH instantiation of the tracer launch while any member is
+   on, captured again only between "no member on" and "some member on".  pucfem_ens_get_field / pucfem_ens_set_field
+   serve PUCFEM_F_DEFGRAD (4 * n_tr values per member) while a member is on.  PUCFEM_ESTATE as above, without an
+   ensemble and on an ensemble without tracers; PUCFEM_EINVAL for a member out of range. */
+int pucfem_ens_set_tracer_stretch(void* ctx, int32_t member /* -1 = all */, int32_t on);
+/* The summary of the context's F (member = -1) or of ensemble member 0 .. members - 1, reduced on the device when
+   called (never inside a step).  Per tracer
+     C00 = F00*F00 + F10*F10,  C01 = F00*F01 + F10*F11,  C11 = F01*F01 + F11*F11
+     lam = 0.5*((C00 + C11) + sqrt((C00 - C11)*(C00 - C11) + 4.0*(C01*C01)))      (the larger Cauchy-Green eigenvalue)
+     det = F00*F11 - F01*F10
+   out8[0] the flag; [1] the tracer steps taken with it on since F was last reset; [2] the tracers whose four entries
+   are finite; [3] of those, the ones with det <= 0 (the discrete map folded there: dt is too large for a Lagrangian
+   statement); [4] the largest and [5] the smallest lam over the finite ones (0 and +inf when there is none); [6] the
+   sum of log(lam) over the finite ones with lam > 0 and [7] the number of its terms.  All zeros while the flag was
+   never on.  The FTLE over an elapsed time T is log(lam) / (2 T) per tracer.  Readiness as pucfem_set_tracer_stretch. */
+int pucfem_tracer_stretch_info(void* ctx, int32_t member /* -1 = the context */, double* out8);
 
 /* ---- MacCormack advection: second-order transport of the dye and of the velocity ---- */
 /* advect_semilagrange (StokesColor.py:347-389) is first order and its linear interpolation a diffusion of order

@@ -21,6 +21,6 @@ from .solver import (LOADS_KEYS, SAMPLE_FIELDS, Buoyancy, Context, HeatSimulatio
                      pixel_centres, poisson_solve, solve, solve_ensemble, squirmer_values, streamline_segments,
                      stroke_geometry)
 from .frames import FrameRecorder, load_npz, render, save_npz, write_vtk  # noqa: F401
-from .tracers import capture_map, tracer_init  # noqa: F401
+from .tracers import capture_map, ftle, seed_map, stretch, tracer_init  # noqa: F401
 
 __version__ = "0.1.0"

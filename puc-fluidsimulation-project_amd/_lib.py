@@ -24,6 +24,9 @@ F_DYE0 = 64
 F_U_ADV = 14  # u_a (N, 2) of the last inertial step, read only
 F_FORCE = 15  # the total body force f (N, 2) of the current state, read only
 F_U_RHS = 16  # r (N, 2) of the last forced step, read only
+F_DEFGRAD = 17  # the tracers' deformation gradient (n_tr, 4) while pucfem_set_tracer_stretch is on
+# pucfem_tracer_stretch_info: the eight values, in order
+STRETCH_KEYS = ("on", "steps", "finite", "folded", "lam_max", "lam_min", "sum_log", "terms")
 FORCE_UNIFORM, FORCE_NODAL, FORCE_BUOYANCY = 1, 2, 4  # pucfem_force_info: the terms present (a mask)
 MAX_DYES = 16
 STROKE_MAX_MODES, STROKE_MAX_PERIOD = 8, 65536  # pucfem_set_stroke: K and P at the most
@@ -145,6 +148,9 @@ SIGNATURES = {
     "pucfem_ens_set_tracer_diffusion": ([_P, ct.c_int32, ct.c_double, ct.c_uint64], ct.c_int),
     "pucfem_get_tracer_diffusion": ([_P, ct.c_int32, _D, ct.POINTER(ct.c_uint64)], ct.c_int),
     "pucfem_tracer_probe": ([_P, ct.c_double, ct.c_int32, _D], ct.c_int),
+    "pucfem_set_tracer_stretch": ([_P, ct.c_int32], ct.c_int),
+    "pucfem_ens_set_tracer_stretch": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
+    "pucfem_tracer_stretch_info": ([_P, ct.c_int32, _D], ct.c_int),
     "pucfem_set_advection": ([_P, ct.c_int32, ct.c_int32], ct.c_int),
     "pucfem_advection_info": ([_P, _I64], ct.c_int),
     "pucfem_sl_advect_mc": ([_P, ct.c_int32, _D, _D, ct.c_double, _D, _I32, _I32], ct.c_int),

@@ -279,6 +279,18 @@ struct Ens {
     dy_bytes = 0;
     dy_steps.clear();
   }
+  // tracer stretching per member (pucfem_ens_set_tracer_stretch; the STRETCH tracer kernels and k_tracer_stretch),
+  // allocated when a member is first switched on and kept: the members' F (M x ntr x 4, identity rows for a member that
+  // is off), their flags as the kernels read them (M) and what the summary reduces with (per member STRETCH_NV
+  // TRACER_CLOUD_MAXB partials, STRETCH_NV values and a ticket)
+  double *str_F = nullptr, *str_part = nullptr, *str_out = nullptr;
+  int32_t* str_on_dev = nullptr;
+  unsigned* str_cnt = nullptr;
+  size_t str_bytes = 0;
+  std::vector<int32_t> str_on;     // the flags (empty: never switched on)
+  std::vector<int64_t> str_steps;  // per member: tracer steps taken with it on since its F was last reset
+  int str_any = 0;                 // members with their flag on
+  bool chain_str = false;          // the captured graphs hold the STRETCH tracer launch
   int nb_tr = 1;             // blocks in x of the tracer launch (1: k_ens_tracer)
   int tr_blocks = 0, tr_threads = 0;  // the last tracer launch (pucfem_tracer_info)
   int* count = nullptr;     // per member: records in the ring
@@ -952,6 +964,7 @@ struct Ctx {
       drop_stroke(false);
       drop_advection();
       drop_trajectory();
+      drop_stretch();
       drop_loads();
       for (void* a : smp_buf)
         if (a) (void)hipFree(a);
@@ -1839,6 +1852,76 @@ struct Ctx {
     state(!dist() && world == 1, "midpoint trajectories are single-rank (the midpoint would need a wide halo of u)");
     need_dev();
     state(has_tgrid, "the context has no tracer grid");
+  }
+
+  // ------------------------------------------------------------------ tracer stretching
+  // pucfem_set_tracer_stretch: every tracer carries the deformation gradient F of the flow map along its path, updated
+  // by the STRETCH instantiations of the tracer kernels in the tracer launch itself.  str_F (ntr x 4) is allocated
+  // when the setting is switched on and freed when it is switched off (not in `allocs`); the summary's partials,
+  // values and ticket are allocated at the first pucfem_tracer_stretch_info and freed with F.
+  bool str_on = false;
+  double* str_F = nullptr;
+  i64 str_rows = 0;   // the rows str_F holds
+  i64 str_steps = 0;  // tracer steps taken with it on since F was last reset
+  double *str_part = nullptr, *str_out = nullptr;
+  unsigned* str_cnt = nullptr;
+  // the single-rank STOKES_FOOD context with tracers it lives on (decided before the device is asked for)
+  void stretch_ready() const {
+    need_built();
+    auto state = [](bool ok, const char* msg) {
+      if (!ok) throw Error(PUCFEM_ESTATE, msg);
+    };
+    state(scheme == PUCFEM_STOKES_FOOD, "tracer stretching needs a STOKES_FOOD context (the tracers)");
+    state(!dist() && world == 1, "tracer stretching is single-rank (the multi-rank tracer step has no STRETCH form)");
+    need_dev();
+    state(has_tgrid, "the context has no tracer grid");
+  }
+  // n rows of F at `first` <- the identity (ordered on st)
+  void stretch_identity(double* F, i64 first, i64 n) {
+    if (n <= 0) return;
+    std::vector<double> id(4 * (size_t)n, 0.0);
+    for (i64 k = 0; k < n; ++k) id[4 * k] = id[4 * k + 3] = 1.0;
+    h2d(F + 4 * first, id.data(), sizeof(double) * id.size());
+  }
+  void drop_stretch() {
+    str_on = false;
+    str_steps = 0;
+    str_rows = 0;
+    if (!str_F && !str_part) return;
+    if (st) (void)hipStreamSynchronize(st);
+    for (void* q : {(void*)str_F, (void*)str_part, (void*)str_out, (void*)str_cnt})
+      if (q) (void)hipFree(q);
+    str_F = str_part = str_out = nullptr;
+    str_cnt = nullptr;
+  }
+  // F for the context's ntr tracers, the identity
+  void stretch_fit() {
+    if (str_rows != ntr || !str_F) {
+      HIPCHK(hipStreamSynchronize(st));
+      if (str_F) (void)hipFree(str_F);
+      str_F = nullptr;
+      mc_alloc(str_F, 4 * (size_t)std::max<i64>(1, ntr));
+      str_rows = ntr;
+    }
+    stretch_identity(str_F, 0, ntr);
+    str_steps = 0;
+  }
+  void set_stretch(bool on) {
+    stretch_ready();
+    if (ens)
+      throw Error(PUCFEM_ESTATE,
+                  "tracer stretching cannot be set while the context has an ensemble (members carry their own: "
+                  "pucfem_ens_set_tracer_stretch)");
+    if (ntr <= 0) throw Error(PUCFEM_ESTATE, "tracer stretching needs a context with tracers (set PUCFEM_F_TRACERS)");
+    if (on == str_on) return;
+    if (on) {
+      stretch_fit();
+      HIPCHK(hipStreamSynchronize(st));
+      str_on = true;
+    } else {
+      drop_stretch();
+    }
+    // (a small-mesh context steps uncaptured while it is on; its captured graphs hold the plain step and are kept)
   }
 
   // ------------------------------------------------------------------ the transport layer
@@ -4203,6 +4286,42 @@ struct Ctx {
       KCHK();
       return;
     }
+    if (str_on) {  // tracer stretching: the same launch, the STRETCH instantiation of whichever kernel is due
+      const MeshDev M{mx, my, mtri, mesh.T};
+      const bool mid = trj_trc == PUCFEM_TRJ_MIDPOINT;
+      if (mid) HIPCHK(hipMemsetAsync(trjt_fell, 0, sizeof(int32_t), st));
+      const Stretch sa{str_F};
+      auto go = [&](auto brown, auto midp) {
+        constexpr bool B = decltype(brown)::value, MI = decltype(midp)::value;
+        BrownArg<B> br{};
+        if constexpr (B)
+          br = Brown{std::sqrt(6.0 * tr_D * dt), (uint32_t)(tr_seed & 0xffffffffu), (uint32_t)(tr_seed >> 32), tr_ylo,
+                     tr_yhi};
+        TrjMidArg<MI> md{};
+        if constexpr (MI) md = TrjMid{0.5 * dt, trjt_fell};
+        if (cloud)
+          hipLaunchKernelGGL((k_tracer_cloud<B, MI, true>), dim3(nbt), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx,
+                             try_, trs, trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, part_tr, rt,
+                             br, md, sa);
+        else
+          hipLaunchKernelGGL((k_tracer<B, MI, true>), dim3(1), dim3(BS), 0, st, M, tgrid, fx, fy, ntr, trx, try_, trs,
+                             trcap, trstep, dt, prm.center_x, prm.center_y, prm.capture_radius, vals + 6, br, md, sa);
+      };
+      if (tr_D > 0.0) {
+        if (mid) go(std::true_type{}, std::true_type{});
+        else go(std::true_type{}, std::false_type{});
+      } else {
+        if (mid) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+      }
+      KCHK();
+      if (mid) {
+        trjt_ran = true;
+        ++trjt_steps;
+      }
+      ++str_steps;
+      return;
+    }
     if (trj_trc == PUCFEM_TRJ_MIDPOINT) {  // midpoint trajectories: the same launch, the MID instantiations
       const MeshDev M{mx, my, mtri, mesh.T};
       const TrjMid md{0.5 * dt, trjt_fell};
@@ -6291,6 +6410,7 @@ int pucfem_build_operators(void* ctx, const pucfem_params* prm) {
     if (!c.host_only) c.drop_stroke(false);
     if (!c.host_only) c.drop_advection();
     if (!c.host_only) c.drop_trajectory();
+    if (!c.host_only) c.drop_stretch();
     if (!c.host_only) c.drop_loads();
     build(c);
   });
@@ -6302,6 +6422,8 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
     Ctx& c = *C(ctx);
     const bool dyef = field == PUCFEM_F_DYES || (field >= PUCFEM_F_DYE0 && field < PUCFEM_F_DYE0 + DYE_MAX);
     if (dyef) c.dye_ready();
+    if (field == PUCFEM_F_DEFGRAD && !c.str_on)
+      throw Error(PUCFEM_ESTATE, "tracer stretching is off: there is no deformation gradient (pucfem_set_tracer_stretch)");
     c.need_dev();
     c.need_built();
     const i64 N = c.mesh.N, no = c.lp.n_own;
@@ -6361,11 +6483,16 @@ int pucfem_set_field(void* ctx, int32_t field, const double* buf, int64_t count)
           c.trcensus = c.dalloc<unsigned long long>(2);
         }
         tracers_put(c, c.trx, c.try_, c.trs, c.trcap, c.trstep, 1, 0, n, buf);
+        if (c.str_on) c.stretch_fit();  // (new tracers: F is the identity again, and its step count 0)
         break;
       }
       case PUCFEM_F_STATUS:
         require(count == c.ntr, "status must match the tracer count");
         c.h2d(c.trs, buf, sizeof(double) * count);
+        break;
+      case PUCFEM_F_DEFGRAD:  // (a run resumed: the rows as they were read; the step count stays)
+        require(count == 4 * (i64)c.ntr, "the deformation gradient must be (n, 4)");
+        if (count > 0) c.h2d(c.str_F, buf, sizeof(double) * count);
         break;
       default: throw Error(PUCFEM_EINVAL, "field cannot be set");
     }
@@ -6378,6 +6505,8 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
     Ctx& c = *C(ctx);
     const bool dyef = field == PUCFEM_F_DYES || (field >= PUCFEM_F_DYE0 && field < PUCFEM_F_DYE0 + DYE_MAX);
     if (dyef) c.dye_ready();
+    if (field == PUCFEM_F_DEFGRAD && !c.str_on)
+      throw Error(PUCFEM_ESTATE, "tracer stretching is off: there is no deformation gradient (pucfem_set_tracer_stretch)");
     c.need_dev();
     c.need_built();
     const i64 N = c.mesh.N, no = c.lp.n_own;
@@ -6453,6 +6582,10 @@ int pucfem_get_field(void* ctx, int32_t field, double* buf, int64_t count) {
         require(count == c.ntr, "capture steps are (n,)");
         capture_steps_get(c, c.trcap, 0, c.ntr, buf);
         break;
+      case PUCFEM_F_DEFGRAD:
+        require(count == 4 * (i64)c.ntr, "the deformation gradient is (n, 4)");
+        if (count > 0) c.d2h(buf, c.str_F, sizeof(double) * count);
+        break;
       default: throw Error(PUCFEM_EINVAL, "unknown field");
     }
   });
@@ -6476,9 +6609,10 @@ int pucfem_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       // by-value terms and dye pointers change between steps; and one with a stroke: the same launches behind
       // k_stroke_bc, so that the captured graphs stay the unstroked step's, launch for launch; and one with a
       // midpoint trajectory on: the captured graphs hold the Euler launches; and one whose loads record is on: the same
-      // launches in front of k_loads, so that the captured graphs stay the unrecorded step's)
+      // launches in front of k_loads, so that the captured graphs stay the unrecorded step's; and one with tracer
+      // stretching on: the captured graphs hold the plain tracer launch)
       if (c.dense && !c.timer.on && !c.dye_impl && c.ndye == 0 && !c.inertia && !c.adv_dye && !c.forced() &&
-          !c.stroked() && !c.trj_any() && c.ld_cap == 0) {
+          !c.stroked() && !c.trj_any() && c.ld_cap == 0 && !c.str_on) {
         // direct-solve small-mesh path: every step is the same sequence of ~25 launches with no
         // host synchronisation -> capture it once (and GK steps of it once), replay them
         // capture `count` consecutive steps into one graph (the steps' buffers are fixed in graph mode)
@@ -6834,6 +6968,33 @@ void ens_enqueue_step(Ctx& c) {
     const RedOut rt{e.vals + ENS_V_EATEN, nullptr, e.cnt + 3 * (size_t)M, 1, 0, 0u};
     auto launch = [&](auto brown, auto eb) {
       constexpr bool B = decltype(brown)::value;
+      if (e.str_any > 0) {
+        // with at least one member's stretching on: the STRETCH instantiation of whichever launch is due below (which
+        // members carry F the kernel reads from device memory)
+        const EnsStretch es{(const int32_t*)e.str_on_dev, e.str_F};
+        if (e.trjt_any > 0) {
+          const EnsMid em{(const int32_t*)e.trj_trc_dev, 0.5 * c.prm.dt, e.trj_vals + ENS_TRJ_FELL};
+          const RedOut rm{e.vals + ENS_V_EATEN, e.trj_vals + ENS_TRJ_FELL, e.cnt + 3 * (size_t)M, 2, 0, 0u};
+          if (e.nb_tr > 1)
+            hipLaunchKernelGGL((k_ens_tracer_cloud<B, true, true>), dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid,
+                               (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep,
+                               c.prm.dt, c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rm, eb, em,
+                               es);
+          else
+            hipLaunchKernelGGL((k_ens_tracer<B, true, true>), dim3(1, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
+                               (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                               c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.vals, eb, em, es);
+        } else if (e.nb_tr > 1) {
+          hipLaunchKernelGGL((k_ens_tracer_cloud<B, false, true>), dim3(e.nb_tr, M), dim3(BS), 0, st, Mh, c.tgrid,
+                             (int64_t)n, (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                             c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.part_tr, rt, eb, EnsMidOff{}, es);
+        } else {
+          hipLaunchKernelGGL((k_ens_tracer<B, false, true>), dim3(1, M), dim3(BS), 0, st, Mh, c.tgrid, (int64_t)n,
+                             (const double*)e.u, e.ntr, e.trx, e.try_, e.trs, e.trcap, e.trstep, c.prm.dt,
+                             c.prm.center_x, c.prm.center_y, c.prm.capture_radius, e.vals, eb, EnsMidOff{}, es);
+        }
+        return;
+      }
       if (e.trjt_any > 0) {
         // with at least one member's tracer part on: the MID instantiation of the same launch (which members take the
         // midpoint the kernel reads from device memory); the members' fell-back counts beside the eaten counts
@@ -6921,10 +7082,14 @@ EnsField ens_field(Ctx& c, Ens& e, int32_t field) {
     case PUCFEM_F_TRACERS: return {nullptr, 2 * (i64)e.ntr, 0};
     case PUCFEM_F_STATUS: return {e.trs, (i64)e.ntr, 0};
     case PUCFEM_F_CAPTURE_STEP: return {nullptr, (i64)e.ntr, 0};
+    case PUCFEM_F_DEFGRAD:  // (the members' F; identity rows for a member whose flag is off)
+      if (e.str_any == 0)
+        throw Error(PUCFEM_ESTATE, "no member's tracer stretching is on: there is no deformation gradient");
+      return {e.str_F, 4 * (i64)e.ntr, 0};
     default:
       throw Error(PUCFEM_EINVAL,
                   "not an ensemble field (U, USTAR, P, P2, C, VORTICITY, U_ADV, FORCE, U_RHS, TRACERS, STATUS, "
-                  "CAPTURE_STEP)");
+                  "CAPTURE_STEP, DEFGRAD)");
   }
 }
 }  // namespace
@@ -6954,6 +7119,9 @@ int pucfem_ens_create(void* ctx, int32_t members, const double* dir_values) {
           "ensembles step the first-order advection: switch MacCormack off first (pucfem_set_advection)");
     state(!c.trj_any(), "the context's midpoint is on: switch it off first (members carry their own: pucfem_ens_set_trajectory)");
     state(!c.stroked(), "the context's stroke is on: clear it first (members carry their own: pucfem_ens_set_stroke)");
+    state(!c.str_on,
+          "the context's tracer stretching is on: switch it off first (members carry their own: "
+          "pucfem_ens_set_tracer_stretch)");
     state(c.dense, "ensembles need the dense small-mesh path (N <= 1500, solver_path auto, no multigrid)");
     state(c.dir_ncomp == 2 && c.dbcsrc && c.fK.items == 0 && !c.p_from_y && c.fused_red && !c.lat_sl &&
               c.sl_rec_wave(c.lp.n_own) && (c.scheme != PUCFEM_STOKES_FOOD || c.has_tgrid),
@@ -7583,12 +7751,17 @@ int pucfem_ens_set_field(void* ctx, int32_t field, int32_t member, const double*
     const i64 m0 = member < 0 ? 0 : member, nm = member < 0 ? e.M : 1;
     require(count == nm * f.per, "count does not match the field's shape (members x values per member)");
     if (f.per == 0) return;
-    if (field == PUCFEM_F_TRACERS)
+    if (field == PUCFEM_F_TRACERS) {
       tracers_put(c, e.trx, e.try_, e.trs, e.trcap, e.trstep + m0, nm, m0 * e.ntr, nm * e.ntr, buf);
-    else if (f.comp > 0)  // (the members are the planes)
+      if (e.str_F) {  // (new tracers: the members' F is the identity again, and their step counts 0)
+        c.stretch_identity(e.str_F, m0 * e.ntr, nm * e.ntr);
+        for (i64 m = m0; m < m0 + nm; ++m) e.str_steps[(size_t)m] = 0;
+      }
+    } else if (f.comp > 0) {  // (the members are the planes)
       c.put_all(f.comp, nm, buf, f.a + m0 * f.per);
-    else
+    } else {
       c.h2d(f.a + m0 * f.per, buf, sizeof(double) * nm * f.per);
+    }
     HIPCHK(hipStreamSynchronize(c.st));
   });
 }
@@ -7660,12 +7833,13 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     // (and for MacCormack: the dye's three launches iff a member's dye scheme is on, the velocity's two iff an
     // inertial member's velocity scheme is)
     // (and for the midpoint trajectories: each of their launches iff a member runs it, Ens::trj_chain)
+    // (and for the tracer stretching: the STRETCH tracer launch iff a member's flag is on)
     // (and for the strokes: the stroke launch iff a member has one; pucfem_ens_set_stroke drops the graphs itself when
     // it reallocates the tables or the shared shapes)
     if (e.chain_adv != (e.adv_any > 0) || e.chain_br != (e.br_any > 0) || e.chain_force != (e.force_any > 0) ||
         e.chain_fnod != (e.fnod != nullptr) || e.chain_mcd != (e.dye_n[ENS_DYE_MC] > 0) ||
         e.chain_mcv != (e.vel_n[ENS_ADV_MC] > 0) || e.chain_stroke != (e.stroke_any > 0) ||
-        e.chain_trj != e.trj_chain()) {
+        e.chain_trj != e.trj_chain() || e.chain_str != (e.str_any > 0)) {
       HIPCHK(hipStreamSynchronize(c.st));
       e.drop_graphs();
       e.chain_stroke = e.stroke_any > 0;
@@ -7676,6 +7850,7 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
       e.chain_mcd = e.dye_n[ENS_DYE_MC] > 0;
       e.chain_mcv = e.vel_n[ENS_ADV_MC] > 0;
       e.chain_trj = e.trj_chain();
+      e.chain_str = e.str_any > 0;
     }
     // (and for the loads record: k_loads behind the chain iff the record is on; a changed capacity drops the graphs)
     ens_loads_ring_fit(c, e, false);
@@ -7717,6 +7892,7 @@ int pucfem_ens_step(void* ctx, int32_t nsteps, pucfem_step_stats* stats) {
     count(e.trjv_steps, e.trj_vel, PUCFEM_TRJ_MIDPOINT, true);
     count(e.trjt_steps, e.trj_trc, PUCFEM_TRJ_MIDPOINT, false);
     if (e.trj_vals) e.trj_stale = e.adv_stale = true;
+    count(e.str_steps, e.str_on, 1, false);
     for (size_t m = 0; m < sM && e.force_any > 0; ++m)
       if (e.fmask[m]) e.fsteps[m] += nsteps;
     for (size_t m = 0; m < sM && e.dy_K > 0; ++m) e.dy_steps[m] += nsteps;
@@ -8584,6 +8760,101 @@ int pucfem_tracer_probe(void* ctx, double dt, int32_t iters, double* out2) {
     launch();  // (untimed: the first launch)
     out2[0] = time_launches(c, iters, launch);
     out2[1] = (double)c.ntr;
+  });
+}
+
+// ---- tracer stretching (the STRETCH tracer kernels and k_tracer_stretch, pucfem_kernels_impl.hpp)
+int pucfem_set_tracer_stretch(void* ctx, int32_t on) {
+  return guard(ctx, [&] { C(ctx)->set_stretch(on != 0); });
+}
+
+int pucfem_ens_set_tracer_stretch(void* ctx, int32_t member, int32_t on) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.stretch_ready();
+    Ens& e = *ens_of(c);
+    if (e.ntr <= 0) throw Error(PUCFEM_ESTATE, "tracer stretching needs a STOKES_FOOD ensemble with tracers");
+    require(member >= -1 && member < e.M, "member index out of range");
+    const size_t sM = (size_t)e.M;
+    const size_t m0 = member < 0 ? 0 : (size_t)member, m1 = member < 0 ? sM : m0 + 1;
+    const int32_t flag = on != 0 ? 1 : 0;
+    if (e.str_on.empty()) {  // (nothing was ever on: nothing is allocated until now)
+      if (!flag) return;
+      const size_t before = e.bytes;
+      e.str_F = e.alloc<double>(sM * 4 * (size_t)e.ntr, c.st);
+      e.str_on_dev = e.alloc<int32_t>(sM, c.st);
+      e.str_part = e.alloc<double>(sM * STRETCH_NV * TRACER_CLOUD_MAXB, c.st);
+      e.str_out = e.alloc<double>(sM * STRETCH_NV, c.st);
+      e.str_cnt = e.alloc<unsigned>(sM, c.st);
+      e.str_bytes = e.bytes - before;
+      c.stretch_identity(e.str_F, 0, (i64)sM * e.ntr);
+      e.str_on.assign(sM, 0);
+      e.str_steps.assign(sM, 0);
+    }
+    bool changed = false;
+    for (size_t m = m0; m < m1; ++m) {
+      if (e.str_on[m] == flag) continue;
+      e.str_on[m] = flag;
+      changed = true;
+      // (switched on: F starts from the identity; switched off: the member's rows read as the identity again)
+      c.stretch_identity(e.str_F, (i64)m * e.ntr, e.ntr);
+      e.str_steps[m] = 0;
+    }
+    if (changed) {
+      e.str_any = (int)std::count(e.str_on.begin(), e.str_on.end(), 1);
+      c.h2d(e.str_on_dev, e.str_on.data(), sizeof(int32_t) * sM);
+    }
+    HIPCHK(hipStreamSynchronize(c.st));
+  });
+}
+
+int pucfem_tracer_stretch_info(void* ctx, int32_t member, double* out8) {
+  return guard(ctx, [&] {
+    Ctx& c = *C(ctx);
+    c.stretch_ready();
+    require(out8 != nullptr, "out is null");
+    require(member >= -1, "member index out of range");
+    for (int k = 0; k < 8; ++k) out8[k] = 0.0;
+    i64 n = c.ntr;
+    const double* F = c.str_on ? c.str_F : nullptr;
+    double *part = nullptr, *out = nullptr;
+    unsigned* cnt = nullptr;
+    if (member >= 0) {
+      Ens& e = *ens_of(c);
+      require(member < e.M, "member index out of range");
+      if (e.str_on.empty()) return;
+      const size_t m = (size_t)member;
+      n = e.ntr;
+      F = e.str_F + m * 4 * (size_t)n;
+      part = e.str_part + m * STRETCH_NV * TRACER_CLOUD_MAXB;
+      out = e.str_out + m * STRETCH_NV;
+      cnt = e.str_cnt + m;
+      out8[0] = e.str_on[m];
+      out8[1] = (double)e.str_steps[m];
+    } else {
+      if (!F) return;
+      if (!c.str_part) {
+        c.mc_alloc(c.str_part, (size_t)STRETCH_NV * TRACER_CLOUD_MAXB);
+        c.mc_alloc(c.str_out, (size_t)STRETCH_NV);
+        c.mc_alloc(c.str_cnt, (size_t)1);
+      }
+      part = c.str_part;
+      out = c.str_out;
+      cnt = c.str_cnt;
+      out8[0] = 1.0;
+      out8[1] = (double)c.str_steps;
+    }
+    const unsigned nb = (unsigned)std::max<i64>(1, std::min<i64>(TRACER_CLOUD_MAXB, (n + BS - 1) / BS));
+    hipLaunchKernelGGL(k_tracer_stretch, dim3(nb, 1), dim3(BS), 0, c.st, (int64_t)n, F, part, out, cnt);
+    KCHK();
+    double v[STRETCH_NV];
+    c.d2h(v, out, sizeof(v));
+    out8[2] = v[0];
+    out8[3] = v[1];
+    out8[4] = v[2];
+    out8[5] = stretch_min_key(v[3]);
+    out8[6] = v[4];
+    out8[7] = v[5];
   });
 }
 

@@ -760,16 +760,26 @@ struct EnsMid {
 struct EnsMidOff {};  // the Euler kernels' (empty) argument
 template <bool MID>
 using EnsMidArg = std::conditional_t<MID, EnsMid, EnsMidOff>;
+// tracer stretching per member (pucfem_ens_set_tracer_stretch), the STRETCH variants' argument: on[m] != 0: member m's
+// tracers carry F (M x ntr x 4), a block-uniform branch as MID's; a member that is off leaves its rows alone
+struct EnsStretch {
+  const int32_t* on;
+  double* F;
+};
+struct EnsStretchOff {};  // the plain kernels' (empty) argument
+template <bool STRETCH>
+using EnsStretchArg = std::conditional_t<STRETCH, EnsStretch, EnsStretchOff>;
 
 // k_tracer per member (one block each): the single path's locate / interpolate / move.  tx, ty, status: M x ntr.
 // BROWN (pucfem_brownian.hpp): the member's amplitude and key from device memory; a block-uniform branch, a[m] == 0
 // the plain move.  MID: tracer_mid itself for the members whose flag is set, and their count of the launch.
-template <bool BROWN, bool MID = false>
+template <bool BROWN, bool MID = false, bool STRETCH = false>
 __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                    int32_t ntr, double* tx, double* ty, double* status,
                                                    int32_t* capstep, int32_t* stepctr, double dt, double cx, double cy,
                                                    double capture, double* vals, EnsBrownArg<BROWN> eb,
-                                                   EnsMidArg<MID> em) {
+                                                   EnsMidArg<MID> em,
+                                                   EnsStretchArg<STRETCH> es = EnsStretchArg<STRETCH>{}) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -784,6 +794,12 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
   [[maybe_unused]] int32_t fell = 0;
   [[maybe_unused]] bool mid = false;
   if constexpr (MID) mid = em.on[m] != 0;
+  [[maybe_unused]] bool str = false;
+  [[maybe_unused]] double* Fm = nullptr;
+  if constexpr (STRETCH) {
+    str = es.on[m] != 0;
+    Fm = es.F + (int64_t)m * 4 * ntr;
+  }
   for (int32_t k = threadIdx.x; k < ntr; k += blockDim.x) {
     if (BROWN && br.a != 0.0) {
       if (stm[k] == 1.0) {
@@ -793,10 +809,16 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
     }
     const double px = txm[k], py = tym[k];
     double vx = NAN, vy = NAN;
-    const int32_t found = tracer_locate(Mh, G, px, py);
-    if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
-    if constexpr (MID) {
-      if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+    if constexpr (STRETCH) {  // (the same velocity; a member whose flag is on: F[k] <- J F[k])
+      double hdt = 0.0;
+      if constexpr (MID) hdt = em.hdt;
+      tracer_velocity<MID, true>(Mh, G, ux, uy, px, py, mid, hdt, dt, str, Fm, k, vx, vy, fell);
+    } else {
+      const int32_t found = tracer_locate(Mh, G, px, py);
+      if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+      if constexpr (MID) {
+        if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+      }
     }
     if (BROWN && br.a != 0.0)
       eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
@@ -815,12 +837,13 @@ __global__ __launch_bounds__(BS) void k_ens_tracer(MeshDev Mh, GridDev G, int64_
 }
 // k_tracer_cloud per member: grid (blocks, M), the member's partials, ticket and step count (ro.out: vals + 6; MID:
 // value 1 of the reduction is the member's fell-back count, into ro.out1)
-template <bool BROWN, bool MID = false>
+template <bool BROWN, bool MID = false, bool STRETCH = false>
 __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, int64_t n, const double* __restrict__ u,
                                                          int32_t ntr, double* tx, double* ty, double* status,
                                                          int32_t* capstep, int32_t* stepctr, double dt, double cx,
                                                          double cy, double capture, double* part, RedOut ro,
-                                                         EnsBrownArg<BROWN> eb, EnsMidArg<MID> em) {
+                                                         EnsBrownArg<BROWN> eb, EnsMidArg<MID> em,
+                                                         EnsStretchArg<STRETCH> es = EnsStretchArg<STRETCH>{}) {
   __shared__ double sh[4];
   const int32_t m = (int32_t)blockIdx.y;
   const double* ux = u + (int64_t)m * 2 * n;
@@ -839,6 +862,12 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
     mid = em.on[m] != 0;
     if (!mid) R.nv = 1;  // (the launch reduces two values: a member off keeps its count of its last midpoint launch)
   }
+  [[maybe_unused]] bool str = false;
+  [[maybe_unused]] double* Fm = nullptr;
+  if constexpr (STRETCH) {
+    str = es.on[m] != 0;
+    Fm = es.F + (int64_t)m * 4 * ntr;
+  }
   for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < ntr; i += (int64_t)gridDim.x * BS) {
     const int32_t k = (int32_t)i;
     if (BROWN && br.a != 0.0) {
@@ -849,10 +878,16 @@ __global__ __launch_bounds__(BS) void k_ens_tracer_cloud(MeshDev Mh, GridDev G, 
     }
     const double px = txm[k], py = tym[k];
     double vx = NAN, vy = NAN;
-    const int32_t found = tracer_locate(Mh, G, px, py);
-    if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
-    if constexpr (MID) {
-      if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+    if constexpr (STRETCH) {  // (the same velocity; a member whose flag is on: F[k] <- J F[k])
+      double hdt = 0.0;
+      if constexpr (MID) hdt = em.hdt;
+      tracer_velocity<MID, true>(Mh, G, ux, uy, px, py, mid, hdt, dt, str, Fm, k, vx, vy, fell);
+    } else {
+      const int32_t found = tracer_locate(Mh, G, px, py);
+      if (found >= 0) tracer_interp(Mh, found, ux, uy, VS, px, py, vx, vy);
+      if constexpr (MID) {
+        if (mid && !tracer_mid(Mh, G, ux, uy, px, py, em.hdt, vx, vy) && found >= 0) ++fell;
+      }
     }
     if (BROWN && br.a != 0.0)
       eaten += tracer_move_brownian(txm, tym, stm, cpm, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);

@@ -2653,6 +2653,32 @@ __device__ __forceinline__ void tracer_interp(const MeshDev& M, int32_t t, const
   vx = zv[0];
   vy = zv[1];
 }
+// tracer_interp that keeps what it forms on the way: g = (pa, pb) of ux then (pa, pb) of uy, the velocity's gradient
+// in triangle t.  The velocity's expressions are tracer_interp's, operation for operation, so its bits are too.
+__device__ __forceinline__ void tracer_interp_grad(const MeshDev& M, int32_t t, const double* __restrict__ ux,
+                                                   const double* __restrict__ uy, int vs, double px, double py,
+                                                   double& vx, double& vy, double (&g)[4]) {
+  const int32_t a = M.tri[3 * t], b = M.tri[3 * t + 1], d = M.tri[3 * t + 2];
+  const double x0 = M.x[a], y0 = M.y[a];
+  const double s1x = M.x[b] - x0, s1y = M.y[b] - y0, s2x = M.x[d] - x0, s2y = M.y[d] - y0;
+  const double nz = s1x * s2y - s1y * s2x;
+  double zv[2];
+  const double* uu[2] = {ux, uy};
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const double z0 = uu[q][(int64_t)vs * a];
+    const double s1z = uu[q][(int64_t)vs * b] - z0, s2z = uu[q][(int64_t)vs * d] - z0;
+    const double nx = s1y * s2z - s1z * s2y;
+    const double ny = s1z * s2x - s1x * s2z;
+    const double pa = -nx / nz, pb = -ny / nz;
+    const double pc = (nx * x0 + ny * y0 + nz * z0) / nz;
+    zv[q] = pa * px + pb * py + pc;
+    g[2 * q] = pa;
+    g[2 * q + 1] = pb;
+  }
+  vx = zv[0];
+  vy = zv[1];
+}
 // forward Euler, x mod 1, sticky capture (StokesFood.py:488-499).  capstep[k] = stepno (the 1-based tracer step being
 // taken) in the step whose move first brings status[k] to 1: one extra store, on that transition only
 __device__ __forceinline__ double tracer_move(double* tx, double* ty, double* status, int32_t* capstep, int32_t k,
@@ -2705,16 +2731,97 @@ __device__ __forceinline__ bool tracer_mid(const MeshDev& M, const GridDev& G, c
   tracer_interp(M, t, ux, uy, VS, mx, my, vx, vy);
   return true;
 }
+// tracer_mid that also returns the midpoint triangle's plane coefficients (h, as tracer_interp_grad's g); h is not
+// written where the midpoint is not found
+__device__ __forceinline__ bool tracer_mid_grad(const MeshDev& M, const GridDev& G, const double* __restrict__ ux,
+                                                const double* __restrict__ uy, double px, double py, double hdt,
+                                                double& vx, double& vy, double (&h)[4]) {
+  const double mx = py_mod(px + vx * hdt, 1.0), my = py + vy * hdt;
+  const int32_t t = tracer_locate(M, G, mx, my);
+  if (t < 0) return false;
+  tracer_interp_grad(M, t, ux, uy, VS, mx, my, vx, vy, h);
+  return true;
+}
+
+// Tracer stretching (pucfem_set_tracer_stretch), the compile-time variant STRETCH of the tracer
+// kernels: each tracer carries the deformation gradient F of the flow map along its path, row k of F (ntr x 4,
+// F00 F01 F10 F11).  The step is piecewise affine in the tracer's position, so its Jacobian J is formed from the plane
+// coefficients the velocity was interpolated with, and F <- J F.  Only the path is read: the position, the status and
+// the counts are those of the kernels without it.
+struct Stretch {
+  double* F;
+};
+struct StretchOff {};  // the plain kernels' (empty) argument
+template <bool STRETCH>
+using StretchArg = std::conditional_t<STRETCH, Stretch, StretchOff>;
+// F[k] <- J F[k], two 16-byte loads and stores.  have: the tracer has a velocity (else the row becomes NaN, as the
+// position does); g: the coefficients at the tracer; mid: the midpoint was found, h its triangle's coefficients
+// (else the Euler J).  Every product and sum as in include/pucfem.h.
+__device__ __forceinline__ void stretch_update(double* F, int64_t k, bool have, const double (&g)[4], bool mid,
+                                               const double (&h)[4], double dt, double hdt) {
+  double2* Fk = reinterpret_cast<double2*>(F + 4 * k);
+  if (!have) {
+    Fk[0] = make_double2(NAN, NAN);
+    Fk[1] = make_double2(NAN, NAN);
+    return;
+  }
+  double J00, J01, J10, J11;
+  if (mid) {
+    const double A00 = 1.0 + hdt * g[0], A01 = hdt * g[1], A10 = hdt * g[2], A11 = 1.0 + hdt * g[3];
+    const double B00 = h[0] * A00 + h[1] * A10, B01 = h[0] * A01 + h[1] * A11;
+    const double B10 = h[2] * A00 + h[3] * A10, B11 = h[2] * A01 + h[3] * A11;
+    J00 = 1.0 + dt * B00;
+    J01 = dt * B01;
+    J10 = dt * B10;
+    J11 = 1.0 + dt * B11;
+  } else {
+    J00 = 1.0 + dt * g[0];
+    J01 = dt * g[1];
+    J10 = dt * g[2];
+    J11 = 1.0 + dt * g[3];
+  }
+  const double2 r0 = Fk[0], r1 = Fk[1];  // (F00 F01) (F10 F11)
+  Fk[0] = make_double2(J00 * r0.x + J01 * r1.x, J00 * r0.y + J01 * r1.y);
+  Fk[1] = make_double2(J10 * r0.x + J11 * r1.x, J10 * r0.y + J11 * r1.y);
+}
+// one tracer's velocity for its move, the kernels' shared sequence: locate, interpolate, MID: the midpoint (fell
+// counted), STRETCH (str: this launch's tracer carries F): the same with the coefficients kept and F updated
+template <bool MID, bool STRETCH>
+__device__ __forceinline__ void tracer_velocity(const MeshDev& M, const GridDev& G, const double* __restrict__ ux,
+                                                const double* __restrict__ uy, double px, double py, bool mid,
+                                                double hdt, double dt, bool str, double* F, int64_t k, double& vx,
+                                                double& vy, int32_t& fell) {
+  const int32_t found = tracer_locate(M, G, px, py);
+  if constexpr (STRETCH) {
+    if (str) {
+      double g[4], h[4];
+      bool got = false;
+      if (found >= 0) tracer_interp_grad(M, found, ux, uy, VS, px, py, vx, vy, g);
+      if constexpr (MID) {
+        if (mid) {
+          got = tracer_mid_grad(M, G, ux, uy, px, py, hdt, vx, vy, h);
+          if (!got && found >= 0) ++fell;
+        }
+      }
+      stretch_update(F, k, found >= 0, g, got, h, dt, hdt);
+      return;
+    }
+  }
+  if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+  if constexpr (MID) {
+    if (mid && !tracer_mid(M, G, ux, uy, px, py, hdt, vx, vy) && found >= 0) ++fell;
+  }
+}
 
 // stepctr: the set's tracer steps so far, in device memory (a captured step's arguments are fixed); the step being
 // taken is *stepctr + 1.  Every thread reads it before the block's barrier, thread 0 stores the new count after it.
 // BROWN (pucfem_brownian.hpp): the move with the random increment of setting br; false is the plain step.  An
 // absorbed tracer leaves its loop iteration only: every thread reaches the barriers behind the loop.
-template <bool BROWN, bool MID = false>
+template <bool BROWN, bool MID = false, bool STRETCH = false>
 __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, const double* __restrict__ uy,
                          int32_t ntr, double* tx, double* ty, double* status, int32_t* capstep, int32_t* stepctr,
                          double dt, double cx, double cy, double capture, double* eaten_out, BrownArg<BROWN> br,
-                         TrjMidArg<MID> md) {
+                         TrjMidArg<MID> md, StretchArg<STRETCH> sa = StretchArg<STRETCH>{}) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
@@ -2728,10 +2835,16 @@ __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, co
     }
     const double px = tx[k], py = ty[k];
     double vx = NAN, vy = NAN;
-    const int32_t found = tracer_locate(M, G, px, py);
-    if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
-    if constexpr (MID) {
-      if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+    if constexpr (STRETCH) {  // (the same velocity, and F[k] <- J F[k])
+      double hdt = 0.0;
+      if constexpr (MID) hdt = md.hdt;
+      tracer_velocity<MID, true>(M, G, ux, uy, px, py, MID, hdt, dt, true, sa.F, k, vx, vy, fell);
+    } else {
+      const int32_t found = tracer_locate(M, G, px, py);
+      if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+      if constexpr (MID) {
+        if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+      }
     }
     if constexpr (BROWN)
       eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
@@ -2751,12 +2864,13 @@ __global__ void k_tracer(MeshDev M, GridDev G, const double* __restrict__ ux, co
 // k_tracer on a grid: one tracer per thread, grid-stride past the capped grid; the eaten count from per-block
 // partials (red_finish; ro.out is never null here).  The block that finishes the reduction stores the new step
 // count: every block read the old one before it drew its ticket.
-template <bool BROWN, bool MID = false>
+template <bool BROWN, bool MID = false, bool STRETCH = false>
 __global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const double* __restrict__ ux,
                                                      const double* __restrict__ uy, int32_t ntr, double* tx,
                                                      double* ty, double* status, int32_t* capstep, int32_t* stepctr,
                                                      double dt, double cx, double cy, double capture, double* part,
-                                                     RedOut ro, BrownArg<BROWN> br, TrjMidArg<MID> md) {
+                                                     RedOut ro, BrownArg<BROWN> br, TrjMidArg<MID> md,
+                                                     StretchArg<STRETCH> sa = StretchArg<STRETCH>{}) {
   __shared__ double sh[4];
   const int32_t stepno = *stepctr + 1;
   double eaten = 0.0;
@@ -2771,10 +2885,16 @@ __global__ __launch_bounds__(BS) void k_tracer_cloud(MeshDev M, GridDev G, const
     }
     const double px = tx[k], py = ty[k];
     double vx = NAN, vy = NAN;
-    const int32_t found = tracer_locate(M, G, px, py);
-    if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
-    if constexpr (MID) {
-      if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+    if constexpr (STRETCH) {  // (the same velocity, and F[k] <- J F[k])
+      double hdt = 0.0;
+      if constexpr (MID) hdt = md.hdt;
+      tracer_velocity<MID, true>(M, G, ux, uy, px, py, MID, hdt, dt, true, sa.F, k, vx, vy, fell);
+    } else {
+      const int32_t found = tracer_locate(M, G, px, py);
+      if (found >= 0) tracer_interp(M, found, ux, uy, VS, px, py, vx, vy);
+      if constexpr (MID) {
+        if (!tracer_mid(M, G, ux, uy, px, py, md.hdt, vx, vy) && found >= 0) ++fell;
+      }
     }
     if constexpr (BROWN)
       eaten += tracer_move_brownian(tx, ty, status, capstep, k, px, py, vx, vy, dt, cx, cy, capture, stepno, br);
@@ -2861,6 +2981,56 @@ __global__ __launch_bounds__(BS) void k_tracer_census(int64_t ntr, const double*
     if (e > 0.0) atomicAdd(out, (unsigned long long)e);
     if (l > 0.0) atomicAdd(out + 1, (unsigned long long)l);
   }
+}
+// pucfem_tracer_stretch_info's summary of F (sets x ntr x 4; the set -- an ensemble's member -- in blockIdx.y), per
+// tracer with every product and sum as written:
+//   C00 = F00*F00 + F10*F10, C01 = F00*F01 + F10*F11, C11 = F01*F01 + F11*F11
+//   lam = 0.5*((C00 + C11) + sqrt((C00 - C11)*(C00 - C11) + 4.0*(C01*C01))),  det = F00*F11 - F01*F10
+// out[STRETCH_NV * set + ..]: 0 the tracers with four finite entries, 1 those of them with det <= 0, 2 the largest
+// lam, 3 the smallest lam in stretch_min_key's form, 4 the sum of log(lam) over those with lam > 0, 5 its terms.
+// Per-block partials (set-major, STRETCH_NV gridDim.x each), red_finish in block order; cnt: a ticket per set.
+constexpr int STRETCH_NV = 6;
+// red_finish combines maxima of values >= 0 only.  For 0 <= lam <= inf the bit pattern grows with lam, so
+// K - bits(lam), K = bits(inf), read as a double is >= 0 and falls as lam grows: its maximum is the smallest lam,
+// exactly, and 0.0 (the start of a maximum) stands for lam = inf, "none".  The map is its own inverse.
+__host__ __device__ __forceinline__ double stretch_min_key(double lam) {
+  union {
+    double d;
+    unsigned long long u;
+  } a;
+  a.d = lam;
+  a.u = 0x7FF0000000000000ull - a.u;
+  return a.d;
+}
+__global__ __launch_bounds__(BS) void k_tracer_stretch(int64_t ntr, const double* __restrict__ F, double* part,
+                                                       double* out, unsigned* cnt) {
+  __shared__ double sh[4];
+  const int64_t set = blockIdx.y;
+  const double2* Fs = reinterpret_cast<const double2*>(F) + set * 2 * ntr;
+  double nfin = 0.0, nfold = 0.0, lmax = 0.0, lmin = 0.0, slog = 0.0, nlog = 0.0;
+  for (int64_t k = (int64_t)blockIdx.x * BS + threadIdx.x; k < ntr; k += (int64_t)gridDim.x * BS) {
+    const double2 r0 = Fs[2 * k], r1 = Fs[2 * k + 1];
+    const double F00 = r0.x, F01 = r0.y, F10 = r1.x, F11 = r1.y;
+    if (!(isfinite(F00) && isfinite(F01) && isfinite(F10) && isfinite(F11))) continue;
+    const double C00 = F00 * F00 + F10 * F10, C01 = F00 * F01 + F10 * F11, C11 = F01 * F01 + F11 * F11;
+    const double lam = 0.5 * ((C00 + C11) + sqrt((C00 - C11) * (C00 - C11) + 4.0 * (C01 * C01)));
+    const double det = F00 * F11 - F01 * F10;
+    nfin += 1.0;
+    if (det <= 0.0) nfold += 1.0;
+    lmax = fmax(lmax, lam);
+    lmin = fmax(lmin, stretch_min_key(lam));
+    if (lam > 0.0) {
+      slog += log(lam);
+      nlog += 1.0;
+    }
+  }
+  const RedOut R{out + STRETCH_NV * set, nullptr, cnt + set, STRETCH_NV, (int)gridDim.x, 0xCu};
+  double* ps = part + set * STRETCH_NV * gridDim.x;
+  const double v[STRETCH_NV] = {block_sum(nfin, sh), block_sum(nfold, sh), block_max(lmax, sh),
+                                block_max(lmin, sh), block_sum(slog, sh),  block_sum(nlog, sh)};
+  if (threadIdx.x == 0)
+    for (int q = 0; q < STRETCH_NV; ++q) red_part(R, ps, q, v[q]);
+  red_finish(R, ps, sh);
 }
 // ghost values of a local vector into their global positions of a full-size array
 // (vs: the element stride of v)

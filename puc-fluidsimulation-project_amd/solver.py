@@ -53,6 +53,13 @@ def advection_scheme(name):
 TRAJECTORY_NAMES = ("euler", "midpoint")  # pucfem_set_trajectory's orders, PUCFEM_TRJ_EULER / PUCFEM_TRJ_MIDPOINT
 
 
+def _stretch_flag(on):
+    """tracer_stretch= as a bool (a bool or numpy bool only: a name or a number is a mistake)."""
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"tracer_stretch must be True or False, got {on!r}")
+    return bool(on)
+
+
 def trajectory_order(name):
     """The PUCFEM_TRJ_* order of trajectory='euler' | 'midpoint' (an int 1 | 2 passes through)."""
     if isinstance(name, str):
@@ -714,6 +721,32 @@ class Context:
         self._c(self.L.pucfem_tracer_probe(self.h, float(dt), int(iters), o))
         return dict(kernel_ms=o[0], tracers=int(o[1]))
 
+    # ---- tracer stretching (pucfem_set_tracer_stretch)
+    def set_tracer_stretch(self, on, member=None):
+        """Tracer stretching of the context (member=None; pucfem_set_tracer_stretch) or of ensemble member `member`
+        (-1: every member; pucfem_ens_set_tracer_stretch): the tracers carry the deformation gradient F of the flow
+        map along their paths."""
+        if member is None:
+            self._c(self.L.pucfem_set_tracer_stretch(self.h, int(_stretch_flag(on))))
+        else:
+            self._c(self.L.pucfem_ens_set_tracer_stretch(self.h, int(member), int(_stretch_flag(on))))
+
+    def stretch_info(self, member=None, T=None):
+        """pucfem_tracer_stretch_info of the context (member=None) or of an ensemble member: the flag, the tracer steps
+        taken with it on since F was last reset, the tracers with finite F, of those the ones with det F <= 0, the
+        largest and smallest Cauchy-Green eigenvalue lam, the sum of log(lam) and the number of its terms, reduced on
+        the device.  T: the elapsed time; adds ftle_mean = sum_log / (2 T terms) and ftle_max = log(lam_max) / (2 T)."""
+        o = (ct.c_double * 8)()
+        self._c(self.L.pucfem_tracer_stretch_info(self.h, -1 if member is None else int(member), o))
+        d = dict(on=bool(o[0]), steps=int(o[1]), finite=int(o[2]), folded=int(o[3]), lam_max=o[4], lam_min=o[5],
+                 sum_log=o[6], terms=int(o[7]))
+        if T is not None:
+            T = float(T)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                d["ftle_mean"] = float(np.float64(d["sum_log"]) / np.float64(2.0 * T * d["terms"]))
+                d["ftle_max"] = float(np.log(np.float64(d["lam_max"])) / np.float64(2.0 * T))
+        return d
+
     def inertia_probe(self, iters=10):
         """Kernel time of one inertial launch on the current u (pucfem_inertia_probe; tools/inertia_bench.py)."""
         o = (ct.c_double * 2)()
@@ -1029,9 +1062,11 @@ class StokesSimulation:
     def __init__(self, mesh: Mesh, bc: SquirmerBC | None = None, dt=0.05, scheme="color", device=0,
                  tol: Tolerances | None = None, dist=None, tracers=None, nstrips=0, inertia=False, advection="sl",
                  tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None, stroke=None,
-                 trajectory="euler"):
+                 trajectory="euler", tracer_stretch=False):
         adv = advection_scheme(advection)
         trj = trajectory_order(trajectory)
+        if _stretch_flag(tracer_stretch) and scheme != "food":
+            raise ValueError("tracer_stretch belongs to scheme 'food': a 'color' run has no tracers")
         _check_stroke(stroke)
         f_const, f_field = _force_args(force, mesh.N)
         if buoyancy is not None and not isinstance(buoyancy, Buoyancy):
@@ -1081,6 +1116,8 @@ class StokesSimulation:
                 self.ctx.set_trajectory(trj_what, trj)
             if tracer_diffusivity != 0.0 or tracer_seed != 0:
                 self.ctx.set_tracer_diffusion(tracer_diffusivity, tracer_seed)
+            if tracer_stretch:
+                self.ctx.set_tracer_stretch(True)
             self._force = (None, None)
             self._buoyancy = None
             if force is not None:
@@ -1403,6 +1440,36 @@ class StokesSimulation:
     def tracer_info(self):
         return self.ctx.tracer_info()
 
+    # ---- tracer stretching (pucfem_set_tracer_stretch)
+    @property
+    def tracer_stretch(self):
+        """Whether the tracers carry the deformation gradient F = dPhi/dX of the flow map along their paths: the
+        exact Jacobian of the discrete tracer steps (Euler or midpoint), updated in the tracer launch itself.  It only
+        reads the path: positions, status and capture steps are those of the run without it.  Switching it on starts
+        F at the identity, switching it off frees it; setting the tracers resets it."""
+        return self.ctx.stretch_info()["on"]
+
+    @tracer_stretch.setter
+    def tracer_stretch(self, on):
+        self.ctx.set_tracer_stretch(on)
+
+    @property
+    def deformation_gradient(self):
+        """(n, 2, 2) the tracers' F (PUCFEM_F_DEFGRAD); NaN for a tracer that left the mesh.  Setting it resumes a
+        run.  tracers.stretch / tracers.ftle turn it into stretching factors and Lyapunov exponents."""
+        return self.ctx.get_field(_lib.F_DEFGRAD, (self._ntr(), 2, 2))
+
+    @deformation_gradient.setter
+    def deformation_gradient(self, F):
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.shape != (self._ntr(), 2, 2):
+            raise ValueError(f"deformation_gradient must be ({self._ntr()}, 2, 2), got {F.shape}")
+        self.ctx.set_field(_lib.F_DEFGRAD, F)
+
+    def stretch_info(self, T=None):
+        """Context.stretch_info of this run; T: the elapsed time of the stretch steps, for ftle_mean and ftle_max."""
+        return self.ctx.stretch_info(T=T)
+
     def _ntr(self):
         return getattr(self, "n_tracers", 0)
 
@@ -1432,6 +1499,19 @@ def _ensemble_flags(inertia, M):
     if a.shape != (M,):
         raise ValueError(f"inertia must be a bool or one bool per member: {M} members, got shape {a.shape}")
     return a.astype(bool)
+
+
+def _ensemble_stretch(tracer_stretch, M):
+    """The tracer_stretch= argument of an ensemble of M members as an (M,) bool array: one bool for all members or
+    one per member."""
+    if isinstance(tracer_stretch, (bool, np.bool_)):
+        return np.full(M, bool(tracer_stretch))
+    if isinstance(tracer_stretch, (str, bytes)) or not hasattr(tracer_stretch, "__len__"):
+        raise ValueError(f"tracer_stretch must be True, False or one of them per member, got {tracer_stretch!r}")
+    flags = list(tracer_stretch)
+    if len(flags) != M:
+        raise ValueError(f"tracer_stretch must be one flag or one per member: {M} members, got {len(flags)}")
+    return np.array([_stretch_flag(v) for v in flags], dtype=bool)
 
 
 def _ensemble_diffusion(tracer_diffusivity, tracer_seed, M):
@@ -1574,8 +1654,12 @@ class StokesEnsemble:
     def __init__(self, mesh: Mesh, bcs, dt=0.05, scheme="color", device=0, tol: Tolerances | None = None,
                  tracers=None, inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None,
                  buoyancy=None, dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
-                 velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None):
+                 velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None,
+                 tracer_stretch=False):
         _ensemble_advection(advection)
+        stretch = _ensemble_stretch(tracer_stretch, len(_check_ensemble_bcs(bcs)))
+        if stretch.any() and scheme != "food":
+            raise ValueError("tracer_stretch belongs to scheme 'food': a 'color' run has no tracers")
         if buoyancy is not None and scheme != "color":
             raise ValueError("buoyancy belongs to scheme 'color': a 'food' run has no dye")
         self.bcs = _check_ensemble_bcs(bcs)
@@ -1630,6 +1714,8 @@ class StokesEnsemble:
                 self.tracer_trajectory = trj_trc
             if diff.any() or seeds.any():
                 self.set_tracer_diffusion(diff, seeds)
+            if stretch.any():
+                self.tracer_stretch = stretch
             if force is not None:
                 self.set_force(force)
             if buoyancy is not None:
@@ -1650,6 +1736,8 @@ class StokesEnsemble:
             return (self.n_tracers, 2)
         if f in (_lib.F_STATUS, _lib.F_CAPTURE_STEP):
             return (self.n_tracers,)
+        if f == _lib.F_DEFGRAD:
+            return (self.n_tracers, 2, 2)
         return (self.mesh.N, ncomp) if ncomp > 1 else (self.mesh.N,)
 
     def get(self, f, ncomp=1, member=None):
@@ -2111,6 +2199,46 @@ class StokesEnsemble:
     def tracer_info(self, member=0):
         return self.ctx.tracer_info(member)
 
+    # ---- tracer stretching per member (pucfem_ens_set_tracer_stretch)
+    def set_tracer_stretch(self, on, member=None):
+        """Tracer stretching of one member (or, member=None, of all): its tracers carry the deformation gradient F
+        as StokesSimulation(..., tracer_stretch=True) does, bit for bit; everything else of every member is the
+        ensemble without it.  Switching a member on or off sets its F to the identity and its step count to 0.  The
+        step stays one captured chain."""
+        self.ctx.set_tracer_stretch(on, -1 if member is None else int(member))
+
+    @property
+    def tracer_stretch(self):
+        """(M,) bool: the members' stretching flags.  Set it with one bool for all or one per member."""
+        return np.array([self.ctx.stretch_info(m)["on"] for m in range(self.M)], dtype=bool)
+
+    @tracer_stretch.setter
+    def tracer_stretch(self, on):
+        flags = _ensemble_stretch(on, self.M)
+        if (flags == flags[0]).all():
+            self.set_tracer_stretch(bool(flags[0]))
+        else:
+            for m, v in enumerate(flags):
+                self.set_tracer_stretch(bool(v), m)
+
+    @property
+    def deformation_gradient(self):
+        """(M, n, 2, 2) the members' F (identity for a member whose flag is off); needs a member with the flag on."""
+        return self.get(_lib.F_DEFGRAD)
+
+    @deformation_gradient.setter
+    def deformation_gradient(self, F):
+        F = np.ascontiguousarray(F, dtype=np.float64)
+        if F.shape != (self.M, self.n_tracers, 2, 2):
+            raise ValueError(f"deformation_gradient must be ({self.M}, {self.n_tracers}, 2, 2), got {F.shape}")
+        self.set(_lib.F_DEFGRAD, F)
+
+    def stretch_info(self, member=None, T=None):
+        """Context.stretch_info of one member, or (member=None) the list over all members."""
+        if member is not None:
+            return self.ctx.stretch_info(int(member), T)
+        return [self.ctx.stretch_info(m, T) for m in range(self.M)]
+
     def raster(self, width, height, fields=("c", "u"), window=None, member=None):
         """Every member's fields as images (pucfem_ens_raster: the swimmers side by side, each pixel located once
         for all members): {name: float32 (M, height, width) or (M, 2, height, width)}; member = m: that member's
@@ -2167,7 +2295,8 @@ class StokesEnsemble:
 def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, tol: Tolerances | None = None,
                    inertia=False, advection="sl", tracer_diffusivity=0.0, tracer_seed=0, force=None, buoyancy=None,
                    dye_advection="sl", velocity_advection="sl", stroke=None, dye_trajectory=None,
-                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None, loads=False):
+                   velocity_trajectory=None, tracer_trajectory=None, trajectory="euler", dyes=None, loads=False,
+                   tracer_stretch=False):
     """solve() for several squirmers at once (StokesEnsemble): one Result per member of `bcs`.  inertia: one bool
     for all members or one per member (StokesEnsemble.inertia).  dye_advection, velocity_advection: 'sl' or
     'maccormack', one name for all members or one per member (StokesEnsemble.set_advection); advection: 'sl' only (it
@@ -2178,7 +2307,9 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
     'midpoint', one name for all members or one per member; trajectory: StokesSimulation's keyword per member
     (StokesEnsemble.set_trajectory).  dyes (scheme 'color'): (K, N) dye channels for all members or (M, K, N)
     (StokesEnsemble.dyes); each member's Result.dyes holds its channels after the last step.  loads: every step records
-    every member's loads on the device (StokesEnsemble.record_loads); each member's Result.loads holds its rows."""
+    every member's loads on the device (StokesEnsemble.record_loads); each member's Result.loads holds its rows.
+    tracer_stretch (scheme 'food'): one bool for all members or one per member (StokesEnsemble.set_tracer_stretch);
+    the Result.deformation_gradient of a member whose flag is on holds its F after the last step."""
     _ensemble_advection(advection)
     if scheme not in ("color", "food"):
         raise ValueError("ensembles step the Stokes schemes 'color' and 'food'")
@@ -2187,7 +2318,7 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
                          tracer_seed=tracer_seed, force=force, buoyancy=buoyancy, dye_advection=dye_advection,
                          velocity_advection=velocity_advection, stroke=stroke, dye_trajectory=dye_trajectory,
                          velocity_trajectory=velocity_trajectory, tracer_trajectory=tracer_trajectory,
-                         trajectory=trajectory, dyes=dyes)
+                         trajectory=trajectory, dyes=dyes, tracer_stretch=tracer_stretch)
     try:
         if loads:
             ens.record_loads(max(int(steps), 1))
@@ -2197,6 +2328,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
         dy = ens.dyes if dyes is not None else None
         c = ens.c if scheme == "color" else None
         tr, ts, cs = (ens.tracers, ens.tracer_status, ens.capture_step) if scheme == "food" else (None, None, None)
+        on = ens.tracer_stretch if scheme == "food" else np.zeros(ens.M, dtype=bool)
+        dg = ens.deformation_gradient if on.any() else None
     finally:
         ens.close()
     res = []
@@ -2210,6 +2343,8 @@ def solve_ensemble(mesh: Mesh, bcs, dt=None, steps=1, scheme="color", device=0, 
                 r.dyes = dy[m]
         else:
             r.tracers, r.tracer_status, r.capture_step = tr[m], ts[m], cs[m]
+            if on[m]:
+                r.deformation_gradient = dg[m]
         res.append(r)
     return res
 
@@ -2329,12 +2464,14 @@ class Result:
     scalar: np.ndarray | None = None
     stats: list = field(default_factory=list)
     dyes: np.ndarray | None = None  # scheme 'color' with dyes=: the final dye channels (K, N)
+    deformation_gradient: np.ndarray | None = None  # scheme 'food' with tracer_stretch=True: (n, 2, 2) per tracer
     loads: np.ndarray | None = None  # Stokes schemes with loads=True: (steps, 11), the row number and LOADS_KEYS per step
 
 
 def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="color", device=0,
           tol: Tolerances | None = None, log=None, dyes=None, inertia=False, advection="sl", tracer_diffusivity=0.0,
-          tracer_seed=0, force=None, buoyancy=None, stroke=None, trajectory="euler", loads=False):
+          tracer_seed=0, force=None, buoyancy=None, stroke=None, trajectory="euler", loads=False,
+          tracer_stretch=False):
     """The north-star call surface: run `steps` steps of a reference script's loop on the GPU.
 
     scheme 'color' = StokesColor.py, 'food' = StokesFood.py, 'heat' = heatEq.py (steps of
@@ -2353,7 +2490,11 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
     trajectory 'euler' | 'midpoint' (schemes 'color' and 'food'): the path of whatever the run transports -- the dye
     on 'color', the velocity with inertia, the tracers on 'food' (StokesSimulation.dye_trajectory and its kin).
     loads (schemes 'color' and 'food'): every step records the swimmer's loads on the device
-    (StokesSimulation.record_loads); the result's `loads` holds the (steps, 11) rows."""
+    (StokesSimulation.record_loads); the result's `loads` holds the (steps, 11) rows.
+    tracer_stretch (scheme 'food'): the tracers carry their deformation gradient (StokesSimulation.tracer_stretch);
+    the result's `deformation_gradient` holds it after the last step."""
+    if _stretch_flag(tracer_stretch) and scheme != "food":
+        raise ValueError("tracer_stretch belongs to scheme 'food'")
     if loads and scheme not in ("color", "food"):
         raise ValueError("loads belong to the Stokes schemes 'color' and 'food'")
     if trajectory_order(trajectory) != _lib.TRJ_EULER and scheme not in ("color", "food"):
@@ -2378,7 +2519,7 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
         dt = dt if dt is not None else (0.05 if scheme == "color" else 0.01)
         sim = StokesSimulation(mesh, bc, dt, scheme, device, tol, inertia=inertia, advection=advection,
                                tracer_diffusivity=tracer_diffusivity, tracer_seed=tracer_seed, force=force,
-                               stroke=stroke, trajectory=trajectory)
+                               stroke=stroke, trajectory=trajectory, tracer_stretch=tracer_stretch)
         if dyes is not None:
             sim.dyes = dyes
         if buoyancy is not None:  # (behind the channels its terms may name)
@@ -2400,6 +2541,8 @@ def solve(mesh: Mesh, bc: SquirmerBC | None = None, dt=None, steps=1, scheme="co
                         f"Color mixing progress={1.0 - s.mix_var / (var0 + 1e-16):.3f}")
         else:
             res.tracers, res.tracer_status, res.capture_step = sim.tracers, sim.tracer_status, sim.capture_step
+            if tracer_stretch:
+                res.deformation_gradient = sim.deformation_gradient
             if log:
                 for k, s in enumerate(st):
                     log(f"Step: {k}, Div(u*): {s.max_div_star:.2e}, Final Div(u): {s.max_final_div:.2e}, "
